@@ -18,6 +18,14 @@ Warm-up: every stream gets its work-queue state (rt_stream_prepare) and at
 least one full launch before t0, whatever --warmup is. The K timed frames are
 ceil(K / group) launches of near-equal size, bracketed by synchronize().
 
+A plain run (`--gpus 1 --steps K --warmup W`) sets up, warms up, times the K
+frames and prints the line with the headline figures (metric, value, unit,
+ms_per_step, ...); `--dump-outputs DIR` also writes the last timed frame (see
+dump_outputs). Everything below -- output checks, frame latency, roofline and
+counter passes, the one-stream leg, extra workloads, drop_in, CPU baselines,
+the N>1 kernel times and single-process leg, the --detail file -- runs only
+with `--full` (the --no-* options trim a full run).
+
 At N=1 the other BASELINE configs are measured the same way under "extra"
 (rank 0): the grid (configs[2]: 256^3 stand-in and the shipped 65^3), the
 octree (configs[3]: depth-8 stand-in and the shipped sdf_6, both 3840x2160),
@@ -120,6 +128,31 @@ EXTRAS = ["grid", "grid_shipped", "octree", "octree_shipped", "mesh_large", "def
 CPU_SAMPLES = [("default_mode", 0.25, 16), ("grid_shipped", 0.25, 16), ("octree_shipped", 0.25, 8)]
 
 
+def use_writable_data_dir():
+    """rtamd.data unpacks a shipped input (data/*.gz) on first use into
+    data/_unpacked/, which build() fills. The benchmark may run as a user who
+    cannot write to a checkout where that was never done: then the inputs go
+    to a private directory (mkdtemp, mode 0700, removed when this process
+    exits), named to the processes this one starts (ranks, the single-process
+    leg, the PMC passes) by RTAMD_DATA_DIR."""
+    import atexit
+    import shutil
+    import tempfile
+    from rtamd import data
+    d = os.environ.get("RTAMD_DATA_DIR")
+    if d:  # from the process that started this one; assigned too, for a package that does not read it
+        data.UNPACKED = d
+        return
+    d = data.UNPACKED
+    if all(os.path.exists(os.path.join(d, f)) for f in data.FILES):
+        return
+    if os.access(d if os.path.isdir(d) else os.path.dirname(d), os.W_OK):
+        return
+    d = tempfile.mkdtemp(prefix="rtamd_data_")
+    atexit.register(shutil.rmtree, d, ignore_errors=True)
+    os.environ["RTAMD_DATA_DIR"] = data.UNPACKED = d
+
+
 def workload_entry(name):
     """A WORKLOADS key, or a shipped input file name (1920x1080 primary rays)."""
     if name in WORKLOADS:
@@ -162,6 +195,13 @@ def parse():
                     help="N>1: skip rank 0's single-process measurement over all N devices")
     ap.add_argument("--dist", action="store_true",
                     help="use the banded + gather path even at WORLD_SIZE 1 (protocol test)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: output checks, latency, roofline and PMC passes, one-stream leg, "
+                         "drop_in, the extra workloads, CPU baselines, the N>1 single-process leg and the "
+                         "--detail file (the --no-* options trim these)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed frame (the caller's colour and t buffers, as finite float32: "
+                         "colour bytes, hit mask, t with 0 at misses) to DIR/<name>.npy")
     return ap.parse_args()
 
 
@@ -315,6 +355,39 @@ def run_single(scene, params, warmup, steps, W, H, inflight=2, tile=None, batch=
     return wall, launches, bufs[jl % inflight][nl - 1]
 
 
+DUMP_BYTES = 60_000_000  # --dump-outputs: all files together stay under 64 MB
+
+
+def dump_outputs(dirname, color, t):
+    """--dump-outputs: the frame the last timed step left in the caller's
+    buffers. color.npy: float32 (..., 4), the packed pixel's R, G, B, A bytes
+    (R is the low byte); hit.npy: float32 1 where the pixel's t is a hit
+    distance, 0 where it is the cleared +inf (nothing hit); t.npy: float32 hit
+    distance, 0 at those misses, so that every file holds finite values only
+    (t as the caller holds it = where(hit, t, inf); a NaN or -inf would be a
+    fault and is written as it is). A frame above DUMP_BYTES (the 4K workloads) is written as a fixed
+    sample of its pixels, drawn once with seed 0: pixel_index.npy (float64)
+    holds their row-major indices, in ascending order."""
+    import numpy as np
+    c = np.ascontiguousarray(color.detach().cpu().numpy()).view(np.uint32)
+    d = np.ascontiguousarray(t.detach().cpu().numpy()).astype(np.float32, copy=False)
+    os.makedirs(dirname, exist_ok=True)
+    per_px = 4 * 4 + 4 + 4
+    idx_file = os.path.join(dirname, "pixel_index.npy")
+    if c.size * per_px > DUMP_BYTES:
+        keep = DUMP_BYTES // (per_px + 8)
+        idx = np.sort(np.random.default_rng(0).choice(c.size, keep, replace=False))
+        c, d = c.reshape(-1)[idx], d.reshape(-1)[idx]
+        np.save(idx_file, idx.astype(np.float64))
+    elif os.path.exists(idx_file):  # a sampled dump of an earlier run in the same directory
+        os.remove(idx_file)
+    rgba = np.stack([(c >> s) & 0xFF for s in (0, 8, 16, 24)], axis=-1).astype(np.float32)
+    np.save(os.path.join(dirname, "color.npy"), rgba)
+    miss = np.isposinf(d)
+    np.save(os.path.join(dirname, "hit.npy"), (~miss).astype(np.float32))
+    np.save(os.path.join(dirname, "t.npy"), np.where(miss, np.float32(0), d))
+
+
 def verify_frames(a, warmup):
     """N>1 warm-up = verification pass: enough frames to reuse every slot group
     at least twice and end on a partial group."""
@@ -394,6 +467,8 @@ def _timed_distributed(make, nverify, params, warmup, steps, a, W, H, scene):
     rs.drain()
     dist.barrier()
     wall = time.perf_counter() - t0
+    if not a.full:
+        return wall, None, rs
     # render-launch duration of this rank's bands: the same launches (a.group frames each,
     # a.streams streams) rendered locally, HIP events on each launch's stream
     n = min(steps, 64)
@@ -561,7 +636,8 @@ def pmc_counters(keys, group):
             cmd = ["timeout", "-k", "10", "240", prof, "--pmc", *ctrs, "--output-format", "csv", "-d", d,
                    "-o", "p", "--", sys.executable, os.path.join(ROOT, "tools", "prof_frames.py"),
                    "--plan", plan, "--group", str(group), "--launches", str(PMC_LAUNCHES)]
-            r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True)
+            # (rocprofv3 leaves a scratch directory in its working directory: not in the tree)
+            r = subprocess.run(cmd, cwd=tmp, env=env, capture_output=True, text=True)
             if r.returncode != 0:
                 return out, f"pass {ctrs[0]} rc={r.returncode}: {r.stderr[-200:]}"
             rows, cal = {}, {}
@@ -825,12 +901,16 @@ def single_process_main(a, json_out):
     scene.set_plane(rtamd.Plane((0.0, 1.0, 0.0), off) if mode == "default" else None)
     params = orbit_params(max(a.warmup + a.steps, 16), W, H, mode)
     wall, exch, (lc, lt) = run_multi(scene, params, a.warmup, a.steps, W, H, devices, a.band_rows)
-    k = a.warmup + a.steps - 1
-    _, _, (c1, t1) = run_single(scene, params[k:k + 1], 0, 1, W, H, inflight=1)
-    ok = bool(torch.equal(c1, lc) and torch.equal(t1.view(torch.int32), lt.view(torch.int32)))
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, lc, lt)
     ms_step = wall * 1e3 / a.steps
-    algo, _ = work_model(scene, params[a.warmup:a.warmup + min(a.steps, 64)], None, W, H)
-    dropin = None if a.no_drop_in else drop_in_multi(scene, params, W, H, devices)
+    ok, algo, dropin = True, None, None
+    if a.full:
+        k = a.warmup + a.steps - 1
+        _, _, (c1, t1) = run_single(scene, params[k:k + 1], 0, 1, W, H, inflight=1)
+        ok = bool(torch.equal(c1, lc) and torch.equal(t1.view(torch.int32), lt.view(torch.int32)))
+        algo, _ = work_model(scene, params[a.warmup:a.warmup + min(a.steps, 64)], None, W, H)
+        dropin = None if a.no_drop_in else drop_in_multi(scene, params, W, H, devices)
     out = {
         "metric": METRIC, "value": round(W * H * a.steps / wall / 1e6, 1), "unit": "Mrays/s",
         "n_gpus": len(set(devices)), "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(ms_step, 4),
@@ -842,11 +922,12 @@ def single_process_main(a, json_out):
                    "resolution": [W, H], "camera": "orbit r=2.5 h=0.5 fovy 45",
                    "parallelism": f"one process, {len(devices)} slots on devices {devices}, row bands of "
                                   f"{a.band_rows} rows, exchange {exch} (rt_multi)"},
-        "roofline": roofline(algo, ms_step, scene.device_bytes(), None, "skipped (single-process leg)"),
-        "frame_check": {"last_timed_frame_equals_one_frame_kernel": ok},
         "exchange": exch, "slots": len(devices),
         "build_id": rtamd.lib().rt_build_id().decode(),
     }
+    if a.full:
+        out["roofline"] = roofline(algo, ms_step, scene.device_bytes(), None, "skipped (single-process leg)")
+        out["frame_check"] = {"last_timed_frame_equals_one_frame_kernel": ok}
     if dropin is not None:
         out["drop_in"] = dropin
     scene.close()
@@ -859,7 +940,7 @@ def single_process_leg(a, world):
     devices from ONE child process (bench.py --single-process), so the
     driver's multi-GPU run also measures the single-process C-ABI path."""
     import subprocess
-    cmd = [sys.executable, os.path.abspath(__file__), "--gpus", str(world), "--single-process",
+    cmd = [sys.executable, os.path.abspath(__file__), "--gpus", str(world), "--single-process", "--full",
            "--steps", str(a.steps), "--warmup", str(a.warmup), "--workload", a.workload,
            "--band-rows", str(a.band_rows)]
     env = {k: v for k, v in os.environ.items()
@@ -975,6 +1056,7 @@ def main():
     json_out = os.fdopen(os.dup(1), "w")
     os.dup2(2, 1)
     a = parse()
+    use_writable_data_dir()
     if a.group is None:
         # the timed frames split evenly over the streams, at most 16 per launch
         # (RT_MAX_BATCH): the driver's 20 frames go out as 10 + 10 on two streams,
@@ -1001,7 +1083,7 @@ def main():
         raise SystemExit(f"bench.py: --gpus {a.gpus} but WORLD_SIZE {world}")
     use_dist = world > 1 or a.dist
     pmc, pmc_err = {}, "skipped (--no-pmc or N>1)"
-    if not use_dist and not a.no_pmc:
+    if a.full and not use_dist and not a.no_pmc:
         WORKLOADS.setdefault(key, entry)
         keys = [key] + ([] if a.no_extra else [k for k in EXTRAS if k != key])
         pmc, pmc_err = pmc_counters(keys, a.group)  # child processes, before this one initialises the GPU
@@ -1037,14 +1119,17 @@ def main():
                                               batch=a.group)
         detail["headline_launch_ms"] = [round(ms, 5) for ms, _ in launches]
         detail["headline_issue_us"] = list(LAST_RUN["issue_each_us"])
-        # the last timed frame (the persistent multi-frame kernel) must equal the
-        # same frame rendered alone by the one-frame kernel (render_kernel): both
-        # are bit-exact against the oracle in tests/, so a timed path that drops
-        # or alters work shows here
-        k = a.warmup + a.steps - 1
-        _, _, (c1, t1) = run_single(scene, params[k:k + 1], 0, 1, W, H, inflight=1)
-        frame_ok = bool(torch.equal(c1, lc) and torch.equal(t1.view(torch.int32), lt.view(torch.int32)))
-        if a.streams * a.group > 1:  # one frame at a time (latency), reported beside
+        if a.dump_outputs:
+            dump_outputs(a.dump_outputs, lc, lt)
+        if a.full:
+            # the last timed frame (the persistent multi-frame kernel) must equal the
+            # same frame rendered alone by the one-frame kernel (render_kernel): both
+            # are bit-exact against the oracle in tests/, so a timed path that drops
+            # or alters work shows here
+            k = a.warmup + a.steps - 1
+            _, _, (c1, t1) = run_single(scene, params[k:k + 1], 0, 1, W, H, inflight=1)
+            frame_ok = bool(torch.equal(c1, lc) and torch.equal(t1.view(torch.int32), lt.view(torch.int32)))
+        if a.full and a.streams * a.group > 1:  # one frame at a time (latency), reported beside
             nl = min(a.steps, 64)
             lwall, ll, _ = run_single(scene, params, min(a.warmup, 8), nl, W, H, inflight=1)
             lat = [ms for ms, _ in ll]
@@ -1056,11 +1141,15 @@ def main():
         t = torch.tensor([wall], dtype=torch.float64, device=dev_t)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         wall = float(t.item())
-        kall = torch.zeros(world, dtype=torch.float64, device=dev_t)
-        kall[rank] = kms
-        dist.all_reduce(kall, op=dist.ReduceOp.SUM)
-        rank_kms = [round(float(x), 5) for x in kall.cpu()]
-        if rank == 0:  # the assembled last frame must equal a whole-frame render of it
+        rank_kms, check_equal = None, None
+        if a.full:  # (every rank takes the same branch: the collectives pair up)
+            kall = torch.zeros(world, dtype=torch.float64, device=dev_t)
+            kall[rank] = kms
+            dist.all_reduce(kall, op=dist.ReduceOp.SUM)
+            rank_kms = [round(float(x), 5) for x in kall.cpu()]
+        if rank == 0 and a.dump_outputs:
+            dump_outputs(a.dump_outputs, *rs.last())
+        if rank == 0 and a.full:  # the assembled last frame must equal a whole-frame render of it
             _, _, (c1, t1) = run_single(scene, params[a.warmup + a.steps - 1:a.warmup + a.steps], 0, 1, W, H,
                                         inflight=1)
             fc, ft = rs.last()
@@ -1069,12 +1158,14 @@ def main():
         rs.close()
 
     ms_step = wall * 1e3 / a.steps
-    # algorithmic bytes of the WHOLE frame (every rank's bands) over the max-over-ranks wall time
-    algo, per_ray = work_model(scene, params[a.warmup:a.warmup + min(a.steps, 64)], None, W, H)
-    rl = roofline(algo, ms_step, scene.device_bytes(), pmc.get(key), pmc_err, a.group, pmc.get("_calib"))
-    detail["headline_work_per_ray"] = per_ray
-    detail["headline_pmc_per_launch"] = pmc.get(key)
-    detail["pmc_calibration"] = {str(w): v for w, v in (pmc.get("_calib") or {}).items()}
+    rl = None
+    if a.full:
+        # algorithmic bytes of the WHOLE frame (every rank's bands) over the max-over-ranks wall time
+        algo, per_ray = work_model(scene, params[a.warmup:a.warmup + min(a.steps, 64)], None, W, H)
+        rl = roofline(algo, ms_step, scene.device_bytes(), pmc.get(key), pmc_err, a.group, pmc.get("_calib"))
+        detail["headline_work_per_ray"] = per_ray
+        detail["headline_pmc_per_launch"] = pmc.get(key)
+        detail["pmc_calibration"] = {str(w): v for w, v in (pmc.get("_calib") or {}).items()}
     value = W * H * a.steps / wall / 1e6
     out = {
         "metric": METRIC, "value": round(value, 1), "unit": "Mrays/s", "n_gpus": world,
@@ -1089,20 +1180,23 @@ def main():
                                    f"{rs.exchange}, {a.group} frames per launch and signal, {a.streams} streams")
                    if use_dist else "1 GPU, 1 thread per pixel",
                    "frames_per_launch": a.group, "streams": a.streams},
-        "roofline": rl,
         # sha256 of the loaded library's sources (rt_build_id): ties the line to a source tree
         "build_id": rtamd.lib().rt_build_id().decode(),
     }
+    if rl is not None:
+        out["roofline"] = rl
     if frame_ok is not None:
         out["frame_check"] = {"last_timed_frame_equals_one_frame_kernel": frame_ok}
     if latency is not None:
         out["frame_latency"] = latency
-    if not use_dist and a.streams > 1:
+    if a.full and not use_dist and a.streams > 1:
         out["roofline"]["one_stream"] = one_stream_leg(scene, params, a.warmup, a.steps, W, H, a.group, algo,
                                                        rl["peak"], rl["peak_kind"])
-    if use_dist:
+    if use_dist and rank_kms is not None:
         out["rank_kernel_ms_per_frame"] = {"per_rank": rank_kms, "max": max(rank_kms)}
     if use_dist and rank == 0:
+        out["host_issue_ms_per_frame"] = round(rs.host_issue_s * 1e3 / a.steps, 4)
+    if a.full and use_dist and rank == 0:  # (a plain run has no frame_check at any N)
         v = rs.verified
         out["frame_check"] = {"assembled_equals_single_render": check_equal and not v["differing"],
                               "last_timed_frame": check_equal,
@@ -1111,17 +1205,16 @@ def main():
                                                  if "p2p_differing" in v else {})},
                               "backend": dist.get_backend(), "exchange": rs.exchange,
                               "fallback": getattr(rs, "fallback", None)}
-        out["host_issue_ms_per_frame"] = round(rs.host_issue_s * 1e3 / a.steps, 4)
-    if rank == 0 and not use_dist and not a.no_drop_in:
+    if a.full and rank == 0 and not use_dist and not a.no_drop_in:
         out["drop_in"] = drop_in(scene, params, W, H)
         # rt_multi_render's host-buffer path, rehearsed with two slots on this GPU
         out["drop_in"]["multi_rehearsal"] = drop_in_multi(scene, params, W, H, [device, device])
     scene.close()
-    if rank == 0 and not use_dist and not a.no_extra:
+    if a.full and rank == 0 and not use_dist and not a.no_extra:
         out["extra"] = {k: measure(k, WORKLOADS[k], min(a.warmup, 16), min(a.steps, 64), a.streams, a.group, pmc,
                                    pmc_err, detail)
                         for k in EXTRAS if k != key}
-    if rank == 0 and not use_dist and not a.no_cpu_baseline:
+    if a.full and rank == 0 and not use_dist and not a.no_cpu_baseline:
         share = 1.0 - sum(s for _, s, _ in CPU_SAMPLES) if not a.no_extra else 1.0
         cb, why = cpu_baseline(entry, a.cpu_seconds * share, 64)
         cb.update({"nproc": os.cpu_count(), "cpu_model": cpu_model(), "threads_from": why,
@@ -1134,18 +1227,20 @@ def main():
         out["cpu_baseline"] = cb
     if use_dist:
         dist.barrier()
-        sp_leg = (rank == 0 and not a.no_single_process_leg and dist.get_backend() == "nccl" and ndev >= world)
+        sp_leg = (a.full and rank == 0 and not a.no_single_process_leg and dist.get_backend() == "nccl"
+                  and ndev >= world)
         dist.destroy_process_group()
         if sp_leg:  # the other ranks exit now; their GPUs are free for the child
             out["single_process"] = single_process_leg(a, world)
     if rank == 0:
-        try:
-            os.makedirs(os.path.dirname(a.detail), exist_ok=True)
-            with open(a.detail, "w") as f:
-                json.dump(detail, f, indent=1)
-            out["detail_file"] = os.path.relpath(a.detail, ROOT)
-        except OSError as e:
-            out["detail_file"] = f"not written: {e}"
+        if a.full:
+            try:
+                os.makedirs(os.path.dirname(a.detail), exist_ok=True)
+                with open(a.detail, "w") as f:
+                    json.dump(detail, f, indent=1)
+                out["detail_file"] = os.path.relpath(a.detail, ROOT)
+            except OSError as e:
+                out["detail_file"] = f"not written: {e}"
         line = json.dumps(out, separators=(",", ":"))
         print(f"bench line: {len(line)} bytes", file=sys.stderr, flush=True)
         print(line, file=json_out, flush=True)

@@ -2,7 +2,7 @@
 
 The reference's shipped resources (resources/*.obj, *.grid, *.octree) are kept
 gzip-compressed under <repo>/data/ and unpacked on first use into
-<repo>/data/_unpacked/ (git-ignored). Nothing here reads /root/reference.
+<repo>/data/_unpacked/ (git-ignored; build() unpacks them all). Nothing here reads /root/reference.
 """
 from __future__ import annotations
 
@@ -12,7 +12,9 @@ import shutil
 
 REPO = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 DATA = os.path.join(REPO, "data")
-UNPACKED = os.path.join(DATA, "_unpacked")
+# RTAMD_DATA_DIR: unpack there instead (bench.py sets it, for itself and the
+# processes it starts, when the tree cannot be written and was never unpacked)
+UNPACKED = os.environ.get("RTAMD_DATA_DIR") or os.path.join(DATA, "_unpacked")
 
 FILES = ("cube.obj", "stanford-bunny.obj", "spot.obj", "example_grid.grid", "sdf_5.octree",
          "sdf_6.octree")
