@@ -1,4 +1,11 @@
-// rt_device.hip -- HIP kernels (gfx950) and the C ABI (include/rtamd.h).
+// rt_device.hip -- the renderer: its HIP kernels (gfx950), struct rt_scene,
+// the launchers and schedules that instantiate the kernels, and the entry
+// points of include/rtamd.h that reach them (scene create / replicate /
+// destroy with the BVH builder choice, rt_render*, rt_untile_device,
+// rt_intersect_rays, rt_count_work, rt_bench_frames, the rtx_set_* switches
+// of the launchers, rti::). The rest of the C ABI is in rt_runtime.hip
+// (errors, streams, host memory, devices), rt_abi_host.hip (loaders, camera,
+// output) and rt_diag.hip (device self-checks).
 //
 // One thread per pixel; a 256-thread workgroup renders a 16x16 pixel block as
 // four 8x8 wave tiles (coherent rays share BVH / octree nodes and grid
@@ -29,213 +36,7 @@
 
 using namespace rtd;
 
-namespace rterr {
-thread_local std::string g_err;
-int set(int code, const std::string &msg) {
-  g_err = msg;
-  return code;
-}
-const char *get() { return g_err.c_str(); }
-thread_local std::string g_noted;
-thread_local hipError_t g_noted_err = hipSuccess;
-hipError_t note(const char *call, hipError_t e) {
-  if (e != hipSuccess) {
-    g_noted = call;
-    g_noted_err = e;
-  }
-  return e;
-}
-std::string take_stale() {
-  const hipError_t e = hipGetLastError();
-  if (e == hipSuccess) return {};
-  std::string m = std::string("stale HIP error ") + hipGetErrorName(e) + " (" + hipGetErrorString(e) +
-                  ") was pending from an earlier call: ";
-  m += e == g_noted_err ? "librtamd's " + g_noted : std::string("a HIP call outside librtamd");
-  g_noted.clear();
-  g_noted_err = hipSuccess;
-  return m;
-}
-
 namespace {
-struct StreamInfo {
-  int device;
-  std::string label;
-  const char *last;  // the last library call that queued work on it (static strings)
-};
-std::mutex g_stream_mu;
-std::map<hipStream_t, StreamInfo> g_streams;
-
-// errors HIP keeps for the context once raised (a faulting kernel or copy):
-// every later call may report them, whichever work raised them
-bool sticky(hipError_t e) {
-  return e == hipErrorIllegalAddress || e == hipErrorLaunchFailure || e == hipErrorLaunchTimeOut ||
-         e == hipErrorAssert || e == hipErrorIllegalState || e == hipErrorUnknown;
-}
-}  // namespace
-
-void stream_add(hipStream_t s, int device, const std::string &label) {
-  std::lock_guard<std::mutex> lk(g_stream_mu);
-  g_streams[s] = StreamInfo{device, label, "(nothing queued yet)"};
-}
-void stream_remove(hipStream_t s) {
-  std::lock_guard<std::mutex> lk(g_stream_mu);
-  g_streams.erase(s);
-}
-void stream_mark(hipStream_t s, const char *what) {
-  std::lock_guard<std::mutex> lk(g_stream_mu);
-  auto it = g_streams.find(s);
-  if (it != g_streams.end()) it->second.last = what;
-}
-hipError_t streams_sync() {
-  std::vector<std::pair<hipStream_t, int>> all;
-  {
-    std::lock_guard<std::mutex> lk(g_stream_mu);
-    for (const auto &kv : g_streams) all.emplace_back(kv.first, kv.second.device);
-  }
-  int prev = 0;
-  if (const hipError_t e = hipGetDevice(&prev)) return e;
-  hipError_t first = hipSuccess;
-  for (const auto &[s, dev] : all) {
-    hipError_t e = hipSetDevice(dev);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess && first == hipSuccess) first = e;
-  }
-  (void)hipSetDevice(prev);
-  return first;
-}
-std::string stream_faults() {
-  std::vector<std::pair<hipStream_t, StreamInfo>> all;
-  {
-    std::lock_guard<std::mutex> lk(g_stream_mu);
-    for (const auto &kv : g_streams) all.emplace_back(kv.first, kv.second);
-  }
-  int prev = 0;
-  (void)hipGetDevice(&prev);
-  std::string m;
-  for (const auto &[s, info] : all) {
-    if (hipSetDevice(info.device) != hipSuccess) continue;
-    const hipError_t e = hipStreamQuery(s);
-    if (e == hipSuccess || e == hipErrorNotReady) continue;
-    m += (m.empty() ? "" : "; ") + info.label + " (device " + std::to_string(info.device) + ", last queued: " +
-         info.last + "): " + hipGetErrorName(e);
-  }
-  (void)hipSetDevice(prev);
-  (void)hipGetLastError();  // (the queries' errors are reported here, not left pending)
-  return m.empty() ? std::string("; no librtamd stream reports an error (the fault came from work queued "
-                                 "by this call itself or outside librtamd)")
-                   : "; librtamd streams reporting errors: " + m;
-}
-std::string hip_fail(const char *expr, hipError_t e) {
-  std::string m = std::string(expr) + ": " + hipGetErrorString(e);
-  if (sticky(e)) m += stream_faults();
-  return m;
-}
-}  // namespace rterr
-
-// ------------------------------------------------ caller host memory (rtdma) --
-namespace {
-// Host ranges pinned through rt_host_pin (base -> bytes): rt_render writes a
-// cleared frame's hits straight into such buffers, and rtdma DMAs them directly.
-std::mutex g_pin_mu;
-std::map<uintptr_t, size_t> g_pins;
-
-// The process-wide bounce buffer of rtdma: two halves of kBounce bytes of
-// pinned host memory (allocated on first use, kept for the process).
-constexpr size_t kBounce = 8u << 20;
-std::mutex g_bounce_mu;
-char *g_bounce[2] = {nullptr, nullptr};
-
-hipError_t bounce_ready() {
-  for (char *&b : g_bounce)
-    if (!b)
-      if (const hipError_t e = hipHostMalloc((void **)&b, kBounce, hipHostMallocPortable)) {
-        b = nullptr;
-        return e;
-      }
-  return hipSuccess;
-}
-}  // namespace
-
-namespace rtdma {
-void *pinned_device_ptr(const void *p, size_t bytes) {
-  const uintptr_t a = (uintptr_t)p;
-  uintptr_t base = 0;
-  {
-    std::lock_guard<std::mutex> lk(g_pin_mu);
-    auto it = g_pins.upper_bound(a);
-    if (it == g_pins.begin()) return nullptr;
-    --it;
-    if (a < it->first || a + bytes > it->first + it->second) return nullptr;
-    base = it->first;
-  }
-  void *d = nullptr;
-  if (hipHostGetDevicePointer(&d, (void *)base, 0) != hipSuccess || !d) {
-    (void)hipGetLastError();  // (not mapped: take the staged path)
-    return nullptr;
-  }
-  return (char *)d + (a - base);
-}
-bool pinned(const void *p, size_t bytes) {
-  const uintptr_t a = (uintptr_t)p;
-  std::lock_guard<std::mutex> lk(g_pin_mu);
-  auto it = g_pins.upper_bound(a);
-  if (it == g_pins.begin()) return false;
-  --it;
-  return a >= it->first && a + bytes <= it->first + it->second;
-}
-hipError_t h2d(void *d, const void *h, size_t n, hipStream_t st) {
-  if (n == 0) return hipSuccess;
-  if (pinned(h, n)) {
-    hipError_t e = hipMemcpyAsync(d, h, n, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    return e;
-  }
-  std::lock_guard<std::mutex> lk(g_bounce_mu);
-  if (const hipError_t e = bounce_ready()) return e;
-  // chunk k fills half k & 1 while the DMA of chunk k - 1 runs from the other
-  for (size_t off = 0, k = 0; off < n; off += kBounce, ++k) {
-    const size_t m = std::min(kBounce, n - off);
-    if (k >= 2)
-      if (const hipError_t e = hipStreamSynchronize(st)) return e;
-    std::memcpy(g_bounce[k & 1], (const char *)h + off, m);
-    if (const hipError_t e = hipMemcpyAsync((char *)d + off, g_bounce[k & 1], m, hipMemcpyHostToDevice, st)) {
-      (void)hipStreamSynchronize(st);
-      return e;
-    }
-  }
-  return hipStreamSynchronize(st);
-}
-hipError_t d2h(void *h, const void *d, size_t n, hipStream_t st) {
-  if (n == 0) return hipSuccess;
-  if (pinned(h, n)) {
-    hipError_t e = hipMemcpyAsync(h, d, n, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    return e;
-  }
-  std::lock_guard<std::mutex> lk(g_bounce_mu);
-  if (const hipError_t e = bounce_ready()) return e;
-  // two chunks per round trip: both DMAs queued, then both copied out
-  for (size_t off = 0; off < n; off += 2 * kBounce) {
-    size_t m[2] = {0, 0};
-    for (int k = 0; k < 2 && off + k * kBounce < n; ++k) {
-      m[k] = std::min(kBounce, n - off - k * kBounce);
-      if (const hipError_t e = hipMemcpyAsync(g_bounce[k], (const char *)d + off + k * kBounce, m[k],
-                                              hipMemcpyDeviceToHost, st)) {
-        (void)hipStreamSynchronize(st);
-        return e;
-      }
-    }
-    if (const hipError_t e = hipStreamSynchronize(st)) return e;
-    for (int k = 0; k < 2; ++k)
-      if (m[k]) std::memcpy((char *)h + off + k * kBounce, g_bounce[k], m[k]);
-  }
-  return hipSuccess;
-}
-}  // namespace rtdma
-
-namespace {
-
-inline int set_err(int code, const std::string &msg) { return rterr::set(code, msg); }
 
 constexpr int kBlock = 256;  // 4 waves, 16x16 pixels
 // Workgroup of the persistent multi-frame kernel (render_persist_kernel), in
@@ -1390,78 +1191,6 @@ __global__ void clear_spans_kernel(uint32_t *c, float *t, int32_t *span, int32_t
   }
 }
 
-// rtx_rcp_check: out[0] += floats checked, out[1] += mismatches, out[2] = bits
-// of a mismatching x
-// rtx_calib_read: a grid-stride pass, each element loaded once; the xor of
-// everything is stored only if it equals a value a zeroed buffer never gives
-// (the loads cannot be dropped, and no store lands)
-__device__ __forceinline__ uint32_t fold(uint32_t v) { return v; }
-__device__ __forceinline__ uint32_t fold(uint4 v) { return v.x ^ v.y ^ v.z ^ v.w; }
-template <class T>
-__global__ __launch_bounds__(256) void calib_read_kernel(const T *__restrict__ p, int64_t n, uint32_t *out) {
-  uint32_t acc = 0;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) acc ^= fold(p[i]);
-  if (acc == 0x9E3779B9u) out[0] = acc;
-}
-
-__global__ void rcp_check_kernel(uint32_t base, unsigned long long *out) {
-  const uint32_t bits = base + blockIdx.x * blockDim.x + threadIdx.x;
-  const float x = __uint_as_float(bits);
-  const float ax = __builtin_fabsf(x);
-  const bool in = ax >= 1e-8f && ax < 0x1p126f;
-  const bool bad = in && __float_as_uint(1.0f / x) != __float_as_uint(rtm::rcp_rn(x));
-  const unsigned long long nin = __popcll(__ballot(in)), nbad = __popcll(__ballot(bad));
-  if ((threadIdx.x & 63) == 0) {
-    if (nin) atomicAdd(out, nin);
-    if (nbad) atomicAdd(out + 1, nbad);
-  }
-  if (bad) out[2] = bits;
-}
-
-// rtx_div_check: rtm::div_mk against the division. mode 0: 2 (x + 1/2) / W for
-// every W in [1, 32768] and x < W (blockIdx.y = W - 1); mode 1: random pairs in
-// the eye ray's ranges (|a| in [2^-72, 2^24] or +-0, |b| in [2^-20, 2^24],
-// random signs and mantissas). out[0] += checked, out[1] += mismatches,
-// out[2] = a mismatching pair (a's bits | b's bits << 32)
-__device__ __forceinline__ uint64_t mix64(uint64_t z) {
-  z += 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-__global__ void div_check_kernel(int mode, uint64_t base, uint64_t seed, unsigned long long *out) {
-  uint64_t n_in = 0, n_bad = 0, bad_ab = 0;
-  if (mode == 0) {
-    const int W = (int)blockIdx.y + 1;
-    for (int x = (int)threadIdx.x; x < W; x += (int)blockDim.x) {
-      const float a = 2.0f * ((float)x + 0.5f), b = (float)W;
-      ++n_in;
-      if (__float_as_uint(rtm::div_mk(a, b)) != __float_as_uint(a / b)) {
-        ++n_bad;
-        bad_ab = __float_as_uint(a) | ((uint64_t)__float_as_uint(b) << 32);
-      }
-    }
-  } else {
-    const uint64_t i = base + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const uint64_t h = mix64(i ^ (seed << 40)), g = mix64(h);
-    const uint32_t ea = 127 - 72 + (uint32_t)(g % 97), eb = 127 - 20 + (uint32_t)((g >> 16) % 45);
-    uint32_t ua = ((uint32_t)h & 0x807FFFFFu) | (ea << 23);
-    const uint32_t ub = ((uint32_t)(h >> 32) & 0x807FFFFFu) | (eb << 23);
-    if (((g >> 32) & 63) == 0) ua &= 0x80000000u;  // +-0 numerators
-    const float a = __uint_as_float(ua), b = __uint_as_float(ub);
-    n_in = 1;
-    if (__float_as_uint(rtm::div_mk(a, b)) != __float_as_uint(a / b)) {
-      n_bad = 1;
-      bad_ab = ua | ((uint64_t)ub << 32);
-    }
-  }
-  if (n_in) atomicAdd(out, (unsigned long long)n_in);
-  if (n_bad) {
-    atomicAdd(out + 1, (unsigned long long)n_bad);
-    out[2] = bad_ab;
-  }
-}
-
 __global__ void untile_kernel(const uint32_t *pc, const float *pt, int64_t per_rank, uint32_t *c,
                               float *t, int W, int H, int band_rows, int nranks) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1503,40 +1232,6 @@ __global__ __launch_bounds__(1024) void order_kernel(uint32_t *cost, uint32_t *o
   for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) {
     order[atomicAdd(&hist[cost_class(cost[i])], 1u)] = i;
     cost[i] = 0;
-  }
-}
-
-// Diagnostic: the world-space primary ray of every pixel, as render_kernel
-// computes it (image row yo, loop row y = H - yo - 1).
-__global__ void eye_rays_kernel(rt_render_params P, int W, int H, float *out) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= W * H) return;
-  const int yo = i / W, x = i - yo * W;
-  const f3 d = eye_ray(x, H - yo - 1, W, H, P.proj_inv, P.view_inv);
-  out[3 * i] = d.x;
-  out[3 * i + 1] = d.y;
-  out[3 * i + 2] = d.z;
-}
-
-// Diagnostic: the 8-lane group primitives of the cooperative tail on test
-// vectors (one 8-lane group per vector of 8 keys): sort8 across lanes, the
-// first-wins min, the OR reduction. Checked against the scalar forms in tests.
-__global__ void grp_test_kernel(const float *keys, int n, float *st, uint32_t *sid, float *mt,
-                                uint32_t *mk, uint32_t *orv) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;  // blockDim = 64: 8 groups per wave
-  const int g = i >> 3, k = i & 7;
-  const bool ok = g < n;
-  float t = ok ? keys[8 * g + k] : 0.0f;
-  uint32_t id = (uint32_t)k;
-  grp_sort8(t, id, k);
-  float m = ok ? keys[8 * g + k] : 0.0f;
-  uint32_t kk = (uint32_t)k;
-  grp_min_first(m, kk, k);
-  const uint32_t o = grp_or(1u << (3 * k), k);
-  if (ok) {
-    st[8 * g + k] = t;
-    sid[8 * g + k] = id;
-    if (k == 0) { mt[g] = m; mk[g] = kk; orv[g] = o; }
   }
 }
 
@@ -1587,11 +1282,7 @@ struct rt_scene {
   int32_t span_cap = 0;
   // rt_render's staging frame for a cleared frame on pageable buffers: pinned
   // host memory the kernel stores its hits into (zero-copy), kept cleared
-  uint32_t *stage_c = nullptr;
-  float *stage_t = nullptr;
-  size_t stage_cap = 0;
-  int32_t stage_W = 0, stage_H = 0;
-  bool stage_dirty = true;
+  rtdma::HostStage stage{hipHostMallocDefault};
   // cost-ordered block schedule (see launch_render), double-buffered: frame k
   // of the scene's one-frame kernel records its tiles' costs into d_cost[k & 1]
   // and dispatches in the order d_order[k & 1] that frame k - 2's costs gave;
@@ -1743,40 +1434,15 @@ void launch_render_t(const S &sc, const PlaneDev &pl, const FrameArgs &fa, bool 
   }
 }
 
-// The pageable drop-in path's staging frame (render_cleared_zero_copy) freed;
-// the caller has synchronised the streams that use it.
-void stage_free(rt_scene *s) {
-  for (void **q : {(void **)&s->stage_c, (void **)&s->stage_t}) {
-    if (*q) {
-      HIP_NOTE(hipHostFree(*q));
-      *q = nullptr;
-    }
-  }
-  s->stage_cap = 0;
-}
-
-// The scene's staging frame for px pixels: pinned, mapped host memory the
-// runtime owns (hipHostMalloc), never handed back to the process heap, so no
-// caller buffer can later land on pages this library registered and
-// unregistered (aligned_alloc + hipHostRegister did that in round 5). Used by
-// rt_render on pageable caller buffers: the zero-copy cleared frame stores its
-// hits into it, and the other frames' uploads / downloads go through it (host
-// copies on one side, DMA on the other). Its stream xs[0] is synchronised
-// before a smaller frame is replaced.
+// The scene's staging frame (rtdma::HostStage) for px pixels, used by
+// rt_render on pageable caller buffers (host copies on one side, DMA on the
+// other). Its streams are synchronised before a smaller frame is replaced.
 int ensure_stage(rt_scene *s, size_t px) {
-  if (px <= s->stage_cap) return RT_OK;
+  if (px <= s->stage.cap) return RT_OK;
   if (s->xs[0]) HIP_TRY(hipStreamSynchronize(s->xs[0]));  // (the previous frame's work on the old frame)
   if (s->xs[1]) HIP_TRY(hipStreamSynchronize(s->xs[1]));
-  stage_free(s);
-  for (void **q : {(void **)&s->stage_c, (void **)&s->stage_t}) {
-    if (const hipError_t e = hipHostMalloc(q, px * 4, hipHostMallocDefault)) {
-      *q = nullptr;
-      stage_free(s);
-      return set_err(RT_E_DEVICE, std::string("staging frame: ") + hipGetErrorString(e));
-    }
-  }
-  s->stage_cap = px;
-  s->stage_dirty = true;
+  if (const hipError_t e = s->stage.ensure(px))
+    return set_err(RT_E_DEVICE, std::string("staging frame: ") + hipGetErrorString(e));
   return RT_OK;
 }
 
@@ -1963,10 +1629,7 @@ struct BandSched {
 };
 std::map<std::pair<int, hipStream_t>, BandSched> g_band_sched;  // (under g_queue_mu)
 
-bool band_order_env() {
-  const char *e = ab_env("RTAMD_BAND_ORDER");
-  return e && e[0] == '1';
-}
+bool band_order_env() { return ab_on("RTAMD_BAND_ORDER"); }
 std::atomic<bool> g_band_order{band_order_env()};
 bool band_order_enabled() { return g_band_order.load(std::memory_order_relaxed); }
 
@@ -1998,10 +1661,7 @@ int64_t g_persist_stamps_cap = 0;
 
 // RTAMD_PERSIST=0 selects the one-block-per-16x16-tile dispatch (A/B switch).
 bool persist_enabled() {
-  static const bool on = [] {
-    const char *e = ab_env("RTAMD_PERSIST");
-    return !(e && e[0] == '0');
-  }();
+  static const bool on = !ab_off("RTAMD_PERSIST");
   return on;
 }
 
@@ -2016,16 +1676,10 @@ bool persist_enabled() {
 // RTAMD_BAND_PERSIST=<N> (ranks) or RTAMD_BAND_PERSIST_PX=<pixels> override the
 // rule (A/B switches).
 // (rtx_set_band_queue_px sets the pixel threshold at run time, for tests)
-std::atomic<int64_t> g_band_queue_px{[] {
-  const char *e = ab_env("RTAMD_BAND_PERSIST_PX");
-  return e ? (int64_t)std::atoll(e) : (int64_t)1000000;
-}()};
+std::atomic<int64_t> g_band_queue_px{ab_int("RTAMD_BAND_PERSIST_PX", 1000000, INT64_MIN, INT64_MAX)};
 bool band_takes_queue(const FrameArgs &f) {
   if (f.nranks <= 1) return true;
-  static const int max_ranks = [] {
-    const char *e = ab_env("RTAMD_BAND_PERSIST");
-    return e ? std::atoi(e) : -1;
-  }();
+  static const int max_ranks = (int)ab_int("RTAMD_BAND_PERSIST", -1, 0, INT32_MAX);
   if (max_ranks >= 0) return f.nranks <= max_ranks;
   return (int64_t)f.rows_local * f.W >= g_band_queue_px.load(std::memory_order_relaxed);
 }
@@ -2033,10 +1687,7 @@ bool band_takes_queue(const FrameArgs &f) {
 // wave tiles per queue item (0: block dispatch); RTAMD_PERSIST_G=1|2|4 overrides
 // the scene's default (A/B switch)
 int persist_group(int dflt) {
-  static const int g = [] {
-    const char *e = ab_env("RTAMD_PERSIST_G");
-    return e ? std::atoi(e) : 0;
-  }();
+  static const int g = (int)ab_int("RTAMD_PERSIST_G", 0, 1, 4);
   return (g == 1 || g == 2 || g == 4) ? g : dflt;
 }
 
@@ -2053,11 +1704,7 @@ int resident_blocks(K kernel, int &blocks, int &dev_cached, int block = kBlock) 
     // RTAMD_PERSIST_OVERSUB=k launches k x the resident workgroups (A/B
     // switch: extra waves start as resident ones leave and exit at once when
     // the queue is drained)
-    static const int oversub = [] {
-      const char *e = ab_env("RTAMD_PERSIST_OVERSUB");
-      const int v = e ? std::atoi(e) : 1;
-      return v >= 1 && v <= 8 ? v : 1;
-    }();
+    static const int oversub = (int)ab_int("RTAMD_PERSIST_OVERSUB", 1, 1, 8);
     blocks = std::max(1, per_cu) * std::max(1, cus) * oversub;
     dev_cached = dev;
   }
@@ -2072,11 +1719,7 @@ int make_queue(const FrameBatch &fb, int n, int group, int blocks, hipStream_t s
   uint32_t *heads = nullptr;
   if (const int rc = stream_queue(stream, &heads)) return rc;
   q.heads = heads;
-  static const uint32_t stride = [] {
-    const char *e = ab_env("RTAMD_QSTRIDE");
-    const int v = e ? std::atoi(e) : 0;
-    return (uint32_t)((v >= 1 && v <= kHeadStrideMax) ? v : kHeadStride);
-  }();
+  static const uint32_t stride = (uint32_t)ab_int("RTAMD_QSTRIDE", kHeadStride, 1, kHeadStrideMax);
   q.stride = stride;
   q.gx = group >= 2 ? 2 : 1;
   q.gy = group >= 4 ? 2 : 1;
@@ -2114,17 +1757,10 @@ int launch_persist_t(rt_scene *s, const S &sc, const PlaneDev &pl, const FrameBa
 // take render_persist_kernel unless RTAMD_PUMP=1 or rtx_set_pump(scene, 1) asks
 // for the pump; RTAMD_REFILL=<lanes> sets its refill threshold.
 bool pump_env() {
-  static const bool on = [] {
-    const char *e = ab_env("RTAMD_PUMP");
-    return e && e[0] == '1';
-  }();
+  static const bool on = ab_on("RTAMD_PUMP");
   return on;
 }
-std::atomic<int> g_refill{[] {
-  const char *e = ab_env("RTAMD_REFILL");
-  const int r = e ? std::atoi(e) : 0;
-  return (r >= 1 && r <= 64) ? r : RT_REFILL_MIN;
-}()};
+std::atomic<int> g_refill{(int)ab_int("RTAMD_REFILL", RT_REFILL_MIN, 1, 64)};
 int refill_min() { return g_refill.load(std::memory_order_relaxed); }
 
 // scenes with a ray-pump adapter (primary-ray batches)
@@ -2248,13 +1884,6 @@ int launch_batch(rt_scene *s, FrameBatch &fb, int n, hipStream_t stream) {
   return RT_OK;
 }
 
-int check_params(const rt_render_params *p, int32_t W, int32_t H) {
-  if (!p) return set_err(RT_E_INVALID, "params is NULL");
-  if (W <= 0 || H <= 0 || (int64_t)W * H > (int64_t)1 << 31) return set_err(RT_E_INVALID, "bad frame size");
-  if (p->shading_mode < 0 || p->shading_mode > 2) return set_err(RT_E_INVALID, "bad shading mode");
-  return RT_OK;
-}
-
 // Whether eye_ray_fast gives eye_ray's bits for every pixel of a W x H frame
 // with this inverse projection: the operand ranges rtm::div_mk needs, bounded
 // over the whole frame. Every entry zero or of magnitude in [2^-10, 2^10] (the
@@ -2266,10 +1895,7 @@ int check_params(const rt_render_params *p, int32_t W, int32_t H) {
 // The reference's projection (perspectiveMatrix(45, W/H, 0.01, 100)) passes.
 // RTAMD_FAST_EYE=0 keeps the divisions (A/B switch)
 bool fast_eye_enabled() {
-  static const bool on = [] {
-    const char *e = ab_env("RTAMD_FAST_EYE");
-    return !(e && e[0] == '0');
-  }();
+  static const bool on = !ab_off("RTAMD_FAST_EYE");
   return on;
 }
 
@@ -2407,72 +2033,6 @@ int upload(T **dst, const T *src, size_t n, int64_t &bytes) {
 }  // namespace
 
 extern "C" {
-
-const char *rt_last_error(void) { return rterr::get(); }
-int rt_abi_version(void) { return RTAMD_ABI_VERSION; }
-
-int rt_device_count(void) {
-  int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess) return 0;
-  return n;
-}
-
-int rt_set_device(int device) {
-  HIP_TRY(hipSetDevice(device));
-  return RT_OK;
-}
-
-int rt_load_obj(const char *path, int scale, float *vpos4, int64_t *nverts, uint32_t *idx,
-                int64_t *nidx) {
-  if (!path || !nverts || !nidx) return set_err(RT_E_INVALID, "NULL argument");
-  rth::Mesh m;
-  std::string err;
-  if (!rth::load_obj(path, scale != 0, m, err)) return set_err(RT_E_IO, err);
-  const int64_t nv = (int64_t)m.vpos4.size() / 4, ni = (int64_t)m.idx.size();
-  if (vpos4 || idx) {
-    if (*nverts < nv || *nidx < ni) return set_err(RT_E_INVALID, "buffers too small");
-    if (vpos4) std::memcpy(vpos4, m.vpos4.data(), m.vpos4.size() * 4);
-    if (idx) std::memcpy(idx, m.idx.data(), m.idx.size() * 4);
-  }
-  *nverts = nv;
-  *nidx = ni;
-  return RT_OK;
-}
-
-int rt_load_grid(const char *path, uint32_t size[3], float *values) {
-  if (!path || !size) return set_err(RT_E_INVALID, "NULL argument");
-  std::vector<float> v;
-  uint32_t sz[3];
-  std::string err;
-  if (!rth::load_grid(path, sz, v, err)) return set_err(RT_E_IO, err);
-  if (values) {
-    if ((uint64_t)size[0] * size[1] * size[2] < v.size()) return set_err(RT_E_INVALID, "buffer too small");
-    std::memcpy(values, v.data(), v.size() * 4);
-  }
-  size[0] = sz[0]; size[1] = sz[1]; size[2] = sz[2];
-  return RT_OK;
-}
-
-int rt_load_octree(const char *path, int64_t *count, void *nodes36) {
-  if (!path || !count) return set_err(RT_E_INVALID, "NULL argument");
-  std::vector<uint8_t> v;
-  std::string err;
-  if (!rth::load_octree(path, v, err)) return set_err(RT_E_IO, err);
-  const int64_t n = (int64_t)v.size() / 36;
-  if (nodes36) {
-    if (*count < n) return set_err(RT_E_INVALID, "buffer too small");
-    std::memcpy(nodes36, v.data(), v.size());
-  }
-  *count = n;
-  return RT_OK;
-}
-
-int rt_camera(const float pos[3], const float target[3], const float up[3], float fovy_deg,
-              float aspect, float znear, float zfar, float view_inv[16], float proj_inv[16]) {
-  if (!pos || !target || !up || !view_inv || !proj_inv) return set_err(RT_E_INVALID, "NULL argument");
-  rth::camera_matrices(pos, target, up, fovy_deg, aspect, znear, zfar, view_inv, proj_inv);
-  return RT_OK;
-}
 
 int rt_set_bvh_builder(int mode) {
   if (mode < RT_BVH_AUTO || mode > RT_BVH_DEVICE) return set_err(RT_E_INVALID, "bad BVH builder mode");
@@ -2771,7 +2331,7 @@ int rt_scene_destroy(rt_scene *s) {
   if (s->h_hit_box) HIP_NOTE(hipHostFree(s->h_hit_box));
   if (s->d_row_span) HIP_NOTE(hipFree(s->d_row_span));
   if (s->h_row_span) HIP_NOTE(hipHostFree(s->h_row_span));
-  stage_free(s);
+  s->stage.release();
   for (hipStream_t x : s->xs)
     if (x) {
       rterr::stream_remove(x);
@@ -2780,17 +2340,6 @@ int rt_scene_destroy(rt_scene *s) {
   HIP_NOTE(hipSetDevice(prev));
   delete s;
   return RT_OK;
-}
-
-int64_t rt_tile_pixels(int32_t W, int32_t H, const rt_tile *tile) {
-  if (W <= 0 || H <= 0) return 0;
-  if (!tile || tile->num_ranks <= 1) return (int64_t)W * H;
-  if (tile->band_rows <= 0) return 0;
-  int64_t rows = 0;
-  const int32_t nb = (H + tile->band_rows - 1) / tile->band_rows;
-  for (int32_t b = tile->rank; b < nb; b += tile->num_ranks)
-    rows += std::min(tile->band_rows, H - b * tile->band_rows);
-  return rows * W;
 }
 
 int rt_render_device(rt_scene *s, const rt_render_params *p, uint32_t *d_color, float *d_t, int32_t W,
@@ -2863,43 +2412,6 @@ int rt_stream_release(void *stream) {
   return RT_OK;
 }
 
-// Exchange slots: uncached device memory, so stores arriving from a peer GPU
-// over xGMI are never shadowed by stale lines in this GPU's L2.
-int rt_exchange_alloc(int64_t bytes, void **d_ptr) {
-  if (!d_ptr || bytes <= 0) return set_err(RT_E_INVALID, "bad arguments");
-  *d_ptr = nullptr;
-  HIP_TRY(hipExtMallocWithFlags(d_ptr, (size_t)bytes, hipDeviceMallocUncached));
-  return RT_OK;
-}
-
-int rt_exchange_free(void *d_ptr) {
-  if (d_ptr) HIP_TRY(hipFree(d_ptr));
-  return RT_OK;
-}
-
-int rt_ipc_get_handle(void *d_ptr, uint8_t handle[RT_IPC_HANDLE_BYTES]) {
-  static_assert(sizeof(hipIpcMemHandle_t) == RT_IPC_HANDLE_BYTES, "IPC handle size");
-  if (!d_ptr || !handle) return set_err(RT_E_INVALID, "bad arguments");
-  hipIpcMemHandle_t h;
-  HIP_TRY(hipIpcGetMemHandle(&h, d_ptr));
-  std::memcpy(handle, &h, sizeof h);
-  return RT_OK;
-}
-
-int rt_ipc_open(const uint8_t handle[RT_IPC_HANDLE_BYTES], void **d_ptr) {
-  if (!d_ptr || !handle) return set_err(RT_E_INVALID, "bad arguments");
-  *d_ptr = nullptr;
-  hipIpcMemHandle_t h;
-  std::memcpy(&h, handle, sizeof h);
-  HIP_TRY(hipIpcOpenMemHandle(d_ptr, h, hipIpcMemLazyEnablePeerAccess));
-  return RT_OK;
-}
-
-int rt_ipc_close(void *d_ptr) {
-  if (d_ptr) HIP_TRY(hipIpcCloseMemHandle(d_ptr));
-  return RT_OK;
-}
-
 // rt_render's failure injection (rtx_render_inject_failure): the next n calls
 // fail after their uploads were issued; g_render_drains counts the returns that
 // waited for both copy streams (rtx_render_drain_count)
@@ -2913,28 +2425,19 @@ using rtdma::pinned_device_ptr;
 // RTAMD_DROPIN_ZC=0: rt_render's cleared frames take the device frame + boxed
 // download instead of the zero-copy path (A/B switch)
 bool dropin_zero_copy() {
-  static const bool on = [] {
-    const char *e = ab_env("RTAMD_DROPIN_ZC");
-    return !(e && e[0] == '0');
-  }();
+  static const bool on = !ab_off("RTAMD_DROPIN_ZC");
   return on;
 }
 
 bool dropin_trace() {
-  static const bool on = [] {
-    const char *e = ab_env("RTAMD_DROPIN_TRACE");
-    return e && e[0] == '1';
-  }();
+  static const bool on = ab_on("RTAMD_DROPIN_TRACE");
   return on;
 }
 
 // The pageable drop-in's staging spans reset by the host threads that copy
 // them; RTAMD_HOST_CLEAR=0: by clear_spans_kernel instead (A/B switch).
 bool host_clears_stage() {
-  static const bool on = [] {
-    const char *e = ab_env("RTAMD_HOST_CLEAR");
-    return !(e && e[0] == '0');
-  }();
+  static const bool on = !ab_off("RTAMD_HOST_CLEAR");
   return on;
 }
 
@@ -2995,8 +2498,8 @@ int render_cleared_zero_copy(rt_scene *s, FrameArgs fa, uint32_t *color, float *
   }
   if (int rc = ensure_stage(s, px)) return rc;
   void *sc = nullptr, *st = nullptr;
-  HIP_TRY(hipHostGetDevicePointer(&sc, s->stage_c, 0));
-  HIP_TRY(hipHostGetDevicePointer(&st, s->stage_t, 0));
+  HIP_TRY(hipHostGetDevicePointer(&sc, s->stage.c, 0));
+  HIP_TRY(hipHostGetDevicePointer(&st, s->stage.t, 0));
   if (H > s->span_cap) {
     HIP_TRY(hipStreamSynchronize(a));  // (the previous frame's span clear reads d_row_span)
     if (s->d_row_span) HIP_NOTE(hipFree(s->d_row_span));
@@ -3007,16 +2510,14 @@ int render_cleared_zero_copy(rt_scene *s, FrameArgs fa, uint32_t *color, float *
     HIP_TRY(hipHostMalloc(&s->h_row_span, (size_t)H * 2 * sizeof(int32_t), hipHostMallocMapped));
     HIP_TRY(hipHostGetDevicePointer((void **)&s->h_row_span_dev, s->h_row_span, 0));
     s->span_cap = H;
-    s->stage_dirty = true;  // (the spans of the frame in the staging frame are gone)
+    s->stage.mark_dirty();  // (the spans of the frame in the staging frame are gone)
   }
-  if (s->stage_dirty || s->stage_W != W || s->stage_H != H) {
-    // (otherwise the previous frame's span reset left both the staging
-    // frame and the span words reset)
-    rth::clear_frame(s->stage_c, s->stage_t, (int64_t)px, 8);
+  // (otherwise the previous frame's span reset left both the staging
+  // frame and the span words reset)
+  if (s->stage.clear_for(W, H)) {
+    s->stage.mark_dirty();  // (a failed reset of the span words leaves the next frame to redo both)
     HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)s->d_row_span, 0x7FFFFFFF, (size_t)H * 2, a));
-    s->stage_W = W;
-    s->stage_H = H;
-    s->stage_dirty = false;
+    s->stage.mark_clean();
   }
   fa.color = (uint32_t *)sc;
   fa.t = (float *)st;
@@ -3028,7 +2529,7 @@ int render_cleared_zero_copy(rt_scene *s, FrameArgs fa, uint32_t *color, float *
   }
   const auto h0 = std::chrono::steady_clock::now();
   HIP_TRY(hipEventRecord(s->ev0, a));
-  s->stage_dirty = true;  // until its spans are cleared again below
+  s->stage.mark_dirty();  // until its spans are cleared again below
   if (int rc = launch_render(s, fa, a)) return rc;
   HIP_TRY(hipEventRecord(s->ev1, a));
   box_out_kernel<<<(unsigned)((2 * H + 255) / 256), 256, 0, a>>>(s->d_row_span, s->h_row_span_dev, 2 * H);
@@ -3044,7 +2545,7 @@ int render_cleared_zero_copy(rt_scene *s, FrameArgs fa, uint32_t *color, float *
   // stores into it, from the next call on), and the span words are reset in
   // stream order before the next frame's kernel; the call does not wait for that
   const bool host_clear = host_clears_stage();
-  rth::copy_spans(color, t, s->stage_c, s->stage_t, W, H, s->h_row_span, 0, host_clear);
+  rth::copy_spans(color, t, s->stage.c, s->stage.t, W, H, s->h_row_span, 0, host_clear);
   const auto h3 = std::chrono::steady_clock::now();
   drain.on = false;
   if (host_clear) {
@@ -3053,7 +2554,7 @@ int render_cleared_zero_copy(rt_scene *s, FrameArgs fa, uint32_t *color, float *
     clear_spans_kernel<<<(unsigned)H, 256, 0, a>>>((uint32_t *)sc, (float *)st, s->d_row_span, W);
     HIP_TRY(hipGetLastError());
   }
-  s->stage_dirty = false;
+  s->stage.mark_clean();
   if (dropin_trace()) {  // RTAMD_DROPIN_TRACE=1: host-side phases of this call (dev switch)
     const auto h4 = std::chrono::steady_clock::now();
     auto us = [](auto x, auto y) { return std::chrono::duration<double, std::micro>(y - x).count(); };
@@ -3092,8 +2593,8 @@ int rt_render(rt_scene *s, const rt_render_params *p, uint32_t *color, float *t,
   // buffers on the host side of each DMA (hc / ht: where the DMAs read / write).
   const bool direct = rtdma::pinned(color, px * 4) && rtdma::pinned(t, px * 4);
   if (!direct && (rc = ensure_stage(s, px))) return rc;
-  uint32_t *hc = direct ? color : s->stage_c;
-  float *ht = direct ? t : s->stage_t;
+  uint32_t *hc = direct ? color : s->stage.c;
+  float *ht = direct ? t : s->stage.t;
   // colour and t move on two streams (two DMA engines, concurrent). Once a copy
   // is queued, every return -- an error included -- first waits for both
   // streams, so the caller may unpin or free its buffers as soon as the call
@@ -3120,7 +2621,7 @@ int rt_render(rt_scene *s, const rt_render_params *p, uint32_t *color, float *t,
   // written whole (a cleared frame) or uploaded whole (tPrev), so the box
   // holds exactly the caller's values outside the hits.
   const bool boxed = !(flags & RT_FLAG_CLEAR) || (flags & RT_FLAG_HITS_ONLY);
-  if (!direct) s->stage_dirty = true;  // (the zero-copy path's cleared staging frame is overwritten)
+  if (!direct) s->stage.mark_dirty();  // (the zero-copy path's cleared staging frame is overwritten)
   if (!(flags & RT_FLAG_CLEAR)) {
     if (!direct) rth::copy_rect(hc, ht, color, t, W, 0, W - 1, 0, H - 1, 0);
     HIP_TRY(hipMemcpyAsync(s->d_color, hc, px * 4, hipMemcpyHostToDevice, a));
@@ -3180,60 +2681,6 @@ int rtx_render_inject_failure(int32_t n) {
   return RT_OK;
 }
 int64_t rtx_render_drain_count(void) { return g_render_drains.load(); }
-
-#ifndef RT_PIN_COARSE
-#define RT_PIN_COARSE 1  // A/B switch: 0 registers caller ranges fine-grained (the HIP default)
-#endif
-int rt_host_pin(void *ptr, int64_t bytes) {
-  if (!ptr || bytes <= 0) return set_err(RT_E_INVALID, "bad host range");
-  {
-    std::lock_guard<std::mutex> lk(g_pin_mu);
-    auto it = g_pins.upper_bound((uintptr_t)ptr + (size_t)bytes - 1);
-    if (it != g_pins.begin() && (--it)->first + it->second > (uintptr_t)ptr)
-      return set_err(RT_E_INVALID, "rt_host_pin: the range overlaps a range pinned earlier and not unpinned "
-                                   "(a buffer freed without rt_host_unpin?)");
-  }
-  // portable: mapped on every device (rt_multi_render's slots store into it).
-  // Coarse-grained (RT_PIN_COARSE): the range is coherent with the host at
-  // kernel and copy boundaries only -- which is all the library relies on: the
-  // host reads or writes a pinned frame only after the stream that used it is
-  // synchronised, and a dispatch's end-of-kernel release covers its stores --
-  // so the GPU's stores into it are not snooped by the host's caches: the
-  // zero-copy cleared frame's kernel (hits stored into the caller's pinned
-  // buffers) ran 0.19-0.24 ms into a fine-grained registration against
-  // ~0.18 into the library's own (coarse-grained) hipHostMalloc staging frame
-  // (profiles/r06/pin_coarse_ab.txt)
-  hipError_t e = hipHostRegister(ptr, (size_t)bytes,
-                                 hipHostRegisterMapped | hipHostRegisterPortable | (RT_PIN_COARSE ? hipExtHostRegisterCoarseGrained : 0u));
-  if (RT_PIN_COARSE && e == hipErrorInvalidValue) {  // (a runtime without the flag)
-    (void)hipGetLastError();
-    e = hipHostRegister(ptr, (size_t)bytes, hipHostRegisterMapped | hipHostRegisterPortable);
-  }
-  if (e == hipErrorHostMemoryAlreadyRegistered) {
-    (void)hipGetLastError();
-    return set_err(RT_E_INVALID, "rt_host_pin: the HIP runtime already holds a registration over this range "
-                                 "(registered outside librtamd, or freed without unregistering)");
-  }
-  HIP_TRY(e);
-  std::lock_guard<std::mutex> lk(g_pin_mu);
-  g_pins[(uintptr_t)ptr] = (size_t)bytes;
-  return RT_OK;
-}
-
-int rt_host_unpin(void *ptr) {
-  if (!ptr) return set_err(RT_E_INVALID, "NULL pointer");
-  {
-    std::lock_guard<std::mutex> lk(g_pin_mu);
-    if (!g_pins.erase((uintptr_t)ptr)) return set_err(RT_E_INVALID, "rt_host_unpin: not a range pinned by rt_host_pin");
-  }
-  // no library stream may still read or write the range when it is unregistered
-  // (every entry point drains its streams before returning; a failed call or a
-  // stream-ordered launch may not have)
-  if (const hipError_t e = rterr::streams_sync())
-    return set_err(RT_E_DEVICE, rterr::hip_fail("rt_host_unpin: draining the library's streams", e));
-  HIP_TRY(hipHostUnregister(ptr));
-  return RT_OK;
-}
 
 int rt_untile_device(const uint32_t *d_packed_color, const float *d_packed_t, int64_t per_rank_pixels,
                      uint32_t *d_color, float *d_t, int32_t W, int32_t H, const rt_tile *tile,
@@ -3354,105 +2801,6 @@ int rtx_wave_stamps(rt_scene *s, const rt_render_params *params, int32_t W, int3
   return RT_OK;
 }
 
-// ---- orbit camera + image output (host-only; rt_host.cpp) ----------------
-static_assert(sizeof(rt_camera_state) == sizeof(rth::CamState), "camera state layout");
-#define CAM(c) (*reinterpret_cast<rth::CamState *>(c))
-int rt_camera_init(const float pos[3], const float target[3], const float up[3], rt_camera_state *c) {
-  if (!pos || !target || !up || !c) return set_err(RT_E_INVALID, "bad arguments");
-  rth::cam_init(CAM(c), pos, target, up);
-  return RT_OK;
-}
-int rt_camera_rotate(rt_camera_state *c, float dx, float dy) {
-  if (!c) return set_err(RT_E_INVALID, "camera is NULL");
-  rth::cam_rotate(CAM(c), dx, dy);
-  return RT_OK;
-}
-int rt_camera_reset_position(rt_camera_state *c, const float pos[3]) {
-  if (!c || !pos) return set_err(RT_E_INVALID, "bad arguments");
-  rth::cam_reset_position(CAM(c), pos);
-  return RT_OK;
-}
-int rt_camera_reset_target(rt_camera_state *c, const float target[3]) {
-  if (!c || !target) return set_err(RT_E_INVALID, "bad arguments");
-  rth::cam_reset_target(CAM(c), target);
-  return RT_OK;
-}
-int rt_camera_set_lock_up(rt_camera_state *c, int on) {
-  if (!c) return set_err(RT_E_INVALID, "camera is NULL");
-  rth::cam_set_lock_up(CAM(c), on != 0);
-  return RT_OK;
-}
-int rt_camera_zoom(rt_camera_state *c, float wheel) {
-  if (!c) return set_err(RT_E_INVALID, "camera is NULL");
-  rth::cam_zoom(CAM(c), wheel);
-  return RT_OK;
-}
-int rt_camera_basis(const rt_camera_state *c, float up[3], float right[3], float forward[3]) {
-  if (!c) return set_err(RT_E_INVALID, "camera is NULL");
-  rth::cam_basis(*reinterpret_cast<const rth::CamState *>(c), up, right, forward);
-  return RT_OK;
-}
-int rt_camera_view_inverse(const rt_camera_state *c, float view_inv[16]) {
-  if (!c || !view_inv) return set_err(RT_E_INVALID, "bad arguments");
-  rth::cam_view_inverse(*reinterpret_cast<const rth::CamState *>(c), view_inv);
-  return RT_OK;
-}
-#undef CAM
-int rt_write_png(const char *path, const uint32_t *color, int32_t W, int32_t H) {
-  std::string err;
-  if (!rth::write_png(path, color, W, H, err)) return set_err(RT_E_IO, err);
-  return RT_OK;
-}
-
-int rt_save_obj(const char *path, const float *vpos4, int64_t nverts, const uint32_t *idx, int64_t nidx,
-                const float *vnorm4, const float *vtex2) {
-  std::string err;
-  if (nverts < 0 || nidx < 0) return set_err(RT_E_INVALID, "bad counts");
-  if (!rth::save_obj(path, vpos4, nverts, idx, nidx, vnorm4, vtex2, err))
-    return set_err(err.rfind("cannot", 0) == 0 || err == "short write" ? RT_E_IO : RT_E_INVALID, err);
-  return RT_OK;
-}
-
-// Diagnostic: primary ray directions as the render kernel computes them (host buffer [H][W][3]).
-int rtx_eye_rays(const rt_render_params *p, int32_t W, int32_t H, float *out) {
-  int rc = check_params(p, W, H);
-  if (rc) return rc;
-  float *d = nullptr;
-  HIP_TRY(hipMalloc(&d, (size_t)W * H * 12));
-  eye_rays_kernel<<<(W * H + 255) / 256, 256>>>(*p, W, H, d);
-  hipError_t e = hipDeviceSynchronize();
-  if (e == hipSuccess) e = hipMemcpy(out, d, (size_t)W * H * 12, hipMemcpyDeviceToHost);
-  HIP_NOTE(hipFree(d));
-  if (e != hipSuccess) return set_err(RT_E_DEVICE, hipGetErrorString(e));
-  return RT_OK;
-}
-
-// Diagnostic: run the 8-lane group primitives on n vectors of 8 keys (host buffers).
-int rtx_grp_test(const float *keys, int32_t n, float *st, uint32_t *sid, float *mt, uint32_t *mk,
-                 uint32_t *orv) {
-  if (n <= 0) return set_err(RT_E_INVALID, "n must be positive");
-  float *dk = nullptr, *dst = nullptr, *dmt = nullptr;
-  uint32_t *dsid = nullptr, *dmk = nullptr, *dor = nullptr;
-  const size_t n8 = (size_t)n * 8;
-  HIP_TRY(hipMalloc(&dk, n8 * 4));
-  HIP_TRY(hipMalloc(&dst, n8 * 4));
-  HIP_TRY(hipMalloc(&dsid, n8 * 4));
-  HIP_TRY(hipMalloc(&dmt, (size_t)n * 4));
-  HIP_TRY(hipMalloc(&dmk, (size_t)n * 4));
-  HIP_TRY(hipMalloc(&dor, (size_t)n * 4));
-  HIP_TRY(hipMemcpy(dk, keys, n8 * 4, hipMemcpyHostToDevice));
-  grp_test_kernel<<<(unsigned)((n8 + 63) / 64), 64>>>(dk, n, dst, dsid, dmt, dmk, dor);
-  hipError_t e = hipDeviceSynchronize();
-  if (e == hipSuccess) e = hipMemcpy(st, dst, n8 * 4, hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(sid, dsid, n8 * 4, hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(mt, dmt, (size_t)n * 4, hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(mk, dmk, (size_t)n * 4, hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(orv, dor, (size_t)n * 4, hipMemcpyDeviceToHost);
-  for (void *q : {(void *)dk, (void *)dst, (void *)dsid, (void *)dmt, (void *)dmk, (void *)dor}) HIP_NOTE(hipFree(q));
-  if (e != hipSuccess) return set_err(RT_E_DEVICE, hipGetErrorString(e));
-  return RT_OK;
-}
-
 // Row bands with at least this many pixels per frame take the work queue
 // (band_takes_queue); < 0 restores the default threshold.
 int rtx_set_band_queue_px(int64_t px) {
@@ -3460,105 +2808,10 @@ int rtx_set_band_queue_px(int64_t px) {
   return RT_OK;
 }
 
-// The pageable drop-in's host copy (rth::copy_spans) on caller arrays, no GPU:
-// span[2y] = first stored column of row y, span[2y+1] = -last (INT32_MAX,
-// INT32_MAX: none); threads 0 = the library's default; clear_src != 0: the
-// copied spans of the source reset to (0, +inf). Not part of include/rtamd.h.
-int rtx_copy_spans(uint32_t *dc, float *dt, uint32_t *sc, float *st, int64_t W, int32_t H, const int32_t *span,
-                   int32_t threads, int32_t clear_src) {
-  if (!dc || !dt || !sc || !st || !span || W <= 0 || H <= 0) return set_err(RT_E_INVALID, "bad arguments");
-  rth::copy_spans(dc, dt, sc, st, W, H, span, threads, clear_src != 0);
-  return RT_OK;
-}
-
-// Exhaustive check of rtm::rcp_rn (rt_rcp.h, tri_t's reciprocal) on this
-// device: every float x with 1e-8 <= |x| < 2^126 against the IEEE division
-// 1 / x. *checked = floats in that range, *bad = mismatches, *first_bad = the
-// bits of one mismatching x (0 if none). Not part of include/rtamd.h.
-int rtx_rcp_check(uint64_t *checked, uint64_t *bad, uint32_t *first_bad) {
-  if (!checked || !bad || !first_bad) return set_err(RT_E_INVALID, "NULL argument");
-  unsigned long long *d = nullptr;
-  HIP_TRY(hipMalloc(&d, 3 * sizeof(unsigned long long)));
-  hipError_t e = hipMemset(d, 0, 3 * sizeof(unsigned long long));
-  const uint32_t block = 256, chunk = 1u << 28;  // 2^28 bit patterns per launch
-  for (uint64_t base = 0; e == hipSuccess && base < (1ull << 32); base += chunk) {
-    rcp_check_kernel<<<chunk / block, block>>>((uint32_t)base, d);
-    e = hipGetLastError();
-  }
-  unsigned long long h[3] = {0, 0, 0};
-  if (e == hipSuccess) e = hipMemcpy(h, d, sizeof h, hipMemcpyDeviceToHost);
-  HIP_NOTE(hipFree(d));
-  if (e != hipSuccess) return set_err(RT_E_DEVICE, std::string("rcp check: ") + hipGetErrorString(e));
-  *checked = h[0];
-  *bad = h[1];
-  *first_bad = (uint32_t)h[2];
-  return RT_OK;
-}
-
-// Diagnostic (bench.py's PMC calibration, tools/prof_frames.py): one pass of
-// calib_read_kernel over `bytes` of device memory, every byte loaded once
-// (`width` = 4 or 16 bytes per lane, consecutive lanes on consecutive
-// addresses), so the vector L1 misses every line exactly once and the
-// dispatch's TCP_TCC_READ_REQ / TCP_TOTAL_CACHE_ACCESSES counts give the bytes
-// per L1->L2 read request and per L1 access on gfx950. Not part of rtamd.h.
-int rtx_calib_read(int64_t bytes, int32_t width, uint32_t *sink) {
-  if (bytes <= 0 || (width != 4 && width != 16) || bytes % 1024) return set_err(RT_E_INVALID, "bad arguments");
-  void *d = nullptr;
-  uint32_t *o = nullptr;
-  HIP_TRY(hipMalloc(&d, (size_t)bytes));
-  hipError_t e = hipMalloc(&o, 4);
-  if (e == hipSuccess) e = hipMemset(d, 0, (size_t)bytes);
-  if (e == hipSuccess) e = hipMemset(o, 0, 4);
-  if (e == hipSuccess) {
-    const int64_t n = bytes / width;
-    const unsigned blocks = (unsigned)std::min<int64_t>((n + 255) / 256, 4096);
-    if (width == 16)
-      calib_read_kernel<uint4><<<blocks, 256>>>((const uint4 *)d, n, o);
-    else
-      calib_read_kernel<uint32_t><<<blocks, 256>>>((const uint32_t *)d, n, o);
-    e = hipGetLastError();
-  }
-  uint32_t h = 0;
-  if (e == hipSuccess) e = hipMemcpy(&h, o, 4, hipMemcpyDeviceToHost);
-  HIP_NOTE(hipFree(d));
-  if (o) HIP_NOTE(hipFree(o));
-  if (e != hipSuccess) return set_err(RT_E_DEVICE, std::string("calib read: ") + hipGetErrorString(e));
-  if (sink) *sink = h;
-  return RT_OK;
-}
-
 // fast_eye_ok for tests (host only): 1 when a W x H frame with this inverse
 // projection takes eye_ray_fast. Not part of include/rtamd.h.
 int rtx_fast_eye_ok(const float *proj_inv, int32_t W, int32_t H) {
   return proj_inv && fast_eye_ok(proj_inv, W, H) ? 1 : 0;
-}
-
-// The checks behind rtm::div_mk on this device (div_check_kernel's modes; n:
-// pairs for mode 1). out[0] = checked, out[1] = mismatches, out[2] = one
-// mismatching pair's bits. Not part of include/rtamd.h.
-int rtx_div_check(int32_t mode, uint64_t n, uint64_t seed, uint64_t out[3]) {
-  if (!out || mode < 0 || mode > 1) return set_err(RT_E_INVALID, "bad arguments");
-  unsigned long long *d = nullptr;
-  HIP_TRY(hipMalloc(&d, 3 * sizeof(unsigned long long)));
-  hipError_t e = hipMemset(d, 0, 3 * sizeof(unsigned long long));
-  const uint32_t block = 256;
-  if (e == hipSuccess && mode == 0) {
-    div_check_kernel<<<dim3(1, 32768), block>>>(0, 0, seed, d);
-    e = hipGetLastError();
-  } else if (e == hipSuccess) {
-    const uint64_t chunk = 1ull << 28;
-    for (uint64_t b0 = 0; e == hipSuccess && b0 < n; b0 += chunk) {
-      const uint64_t m = std::min(chunk, n - b0);
-      div_check_kernel<<<(unsigned)((m + block - 1) / block), block>>>(mode, b0, seed, d);
-      e = hipGetLastError();
-    }
-  }
-  unsigned long long h[3] = {0, 0, 0};
-  if (e == hipSuccess) e = hipMemcpy(h, d, sizeof h, hipMemcpyDeviceToHost);
-  HIP_NOTE(hipFree(d));
-  if (e != hipSuccess) return set_err(RT_E_DEVICE, std::string("div check: ") + hipGetErrorString(e));
-  for (int i = 0; i < 3; ++i) out[i] = h[i];
-  return RT_OK;
 }
 
 // Heavy-first band order on (1) / off (0) from now on; < 0 restores the

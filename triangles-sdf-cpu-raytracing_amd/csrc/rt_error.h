@@ -1,11 +1,13 @@
 // rt_error.h -- the library's error slot behind rt_last_error() (one per host
 // thread), the HIP error check used by every C entry point, the registry of the
 // library's own HIP streams and the copies between the device and caller host
-// memory (rtdma).
+// memory with their staging frame (rtdma).
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <string>
+
+#include "../../include/rtamd.h"
 
 namespace rterr {
 int set(int code, const std::string &msg);  // stores msg, returns code
@@ -38,6 +40,13 @@ std::string stream_faults();   // "" or "; library streams reporting errors: ...
 // the error is a sticky device fault.
 std::string hip_fail(const char *expr, hipError_t e);
 }  // namespace rterr
+static inline int set_err(int code, const std::string &msg) { return rterr::set(code, msg); }
+static inline int check_params(const rt_render_params *p, int32_t W, int32_t H) {
+  if (!p) return set_err(RT_E_INVALID, "params is NULL");
+  if (W <= 0 || H <= 0 || (int64_t)W * H > (int64_t)1 << 31) return set_err(RT_E_INVALID, "bad frame size");
+  if (p->shading_mode < 0 || p->shading_mode > 2) return set_err(RT_E_INVALID, "bad shading mode");
+  return RT_OK;
+}
 
 // Copies between device memory and CALLER host memory. The runtime's DMA only
 // ever sees pinned memory: host ranges the caller pinned with rt_host_pin are
@@ -53,11 +62,37 @@ void *pinned_device_ptr(const void *p, size_t bytes);
 bool pinned(const void *p, size_t bytes);
 hipError_t h2d(void *d, const void *h, size_t n, hipStream_t st);
 hipError_t d2h(void *h, const void *d, size_t n, hipStream_t st);
+
+// The pinned host frame (colour + t) behind rt_render and rt_multi_render on
+// pageable caller buffers: the zero-copy cleared frame stores its hits into it
+// and the other frames' uploads / downloads go through it. The runtime owns the
+// memory (hipHostMalloc with `flags`), never handed back to the process heap,
+// so no caller buffer can later land on pages this library registered and
+// unregistered (aligned_alloc + hipHostRegister did that in round 5). It stays
+// cleared (0 / +inf) between cleared frames of one size: the host resets each
+// span it copies out.
+struct HostStage {
+  uint32_t *c = nullptr;
+  float *t = nullptr;
+  size_t cap = 0;  // pixels
+  explicit HostStage(unsigned flags) : flags_(flags) {}
+  // room for px pixels; the owner drains the streams that use the frame before
+  // it grows (px > cap)
+  hipError_t ensure(size_t px);
+  void mark_dirty() { dirty_ = true; }
+  void mark_clean() { dirty_ = false; }  // every span stored since clear_for is reset again
+  // a cleared W x H frame: cleared here when it is dirty or was last cleared
+  // for another size (returns true), else left as the span resets kept it
+  bool clear_for(int32_t W, int32_t H);
+  void release();  // the owner has synchronised the streams that use it
+
+ private:
+  unsigned flags_;
+  int32_t W_ = 0, H_ = 0;
+  bool dirty_ = true;
+};
 }  // namespace rtdma
 
-struct rt_scene;
-struct rt_render_params;
-struct rt_tile;
 namespace rti {  // librtamd-internal entry points shared between its translation units
 int render_band_host(rt_scene *s, const rt_render_params *p, uint32_t *dc, float *dt, int32_t W, int32_t H,
                      const rt_tile *tile, int32_t *d_span, hipStream_t stream);

@@ -28,6 +28,21 @@ inline const char *ab_env(const char *name) {
   return nullptr;
 #endif
 }
+// the three forms a switch takes: set to 1... (on), set to 0... (off), an
+// integer in [lo, hi] (anything else, or unset: dflt)
+inline bool ab_on(const char *name) {
+  const char *e = ab_env(name);
+  return e && e[0] == '1';
+}
+inline bool ab_off(const char *name) {
+  const char *e = ab_env(name);
+  return e && e[0] == '0';
+}
+inline long long ab_int(const char *name, long long dflt, long long lo, long long hi) {
+  const char *e = ab_env(name);
+  const long long v = e ? std::atoll(e) : dflt;
+  return v >= lo && v <= hi ? v : dflt;
+}
 
 namespace rth {
 

@@ -85,12 +85,9 @@ struct rt_multi {
   uint32_t *fc = nullptr;  // root: one assembled frame for the host path
   float *ft = nullptr;
   // host frames: the staging frame for pageable caller buffers (pinned, mapped
-  // on every device; kept cleared between zero-copy cleared frames while
-  // hs_dirty is false) and its address on each slot's device
-  uint32_t *hs_c = nullptr;
-  float *hs_t = nullptr;
-  size_t hs_cap = 0;
-  bool hs_dirty = true;
+  // on every device; kept cleared between zero-copy cleared frames) and its
+  // address on each slot's device
+  rtdma::HostStage hs{hipHostMallocPortable | hipHostMallocMapped};
   std::vector<uint32_t *> hs_c_dev;
   std::vector<float *> hs_t_dev;
   // zero-copy cleared frames on the staging frame: per slot, the span of
@@ -139,29 +136,21 @@ void free_host(rt_multi *m) {
   m->d_span.assign(m->n, nullptr);
   m->h_span.assign(m->n, nullptr);
   m->span_rows = 0;
-  if (m->hs_c) HIP_NOTE(hipHostFree(m->hs_c));
-  if (m->hs_t) HIP_NOTE(hipHostFree(m->hs_t));
-  m->hs_c = nullptr;
-  m->hs_t = nullptr;
-  m->hs_cap = 0;
+  m->hs.release();
   m->hs_c_dev.assign(m->n, nullptr);
   m->hs_t_dev.assign(m->n, nullptr);
 }
 
 // the staging frame for px pixels (every slot stream is drained first when it grows)
 int ensure_host_stage(rt_multi *m, size_t px) {
-  if (px <= m->hs_cap) return RT_OK;
+  if (px <= m->hs.cap) return RT_OK;
   free_host(m);
-  const unsigned fl = hipHostMallocPortable | hipHostMallocMapped;
-  HIP_TRY(hipHostMalloc((void **)&m->hs_c, px * 4, fl));
-  HIP_TRY(hipHostMalloc((void **)&m->hs_t, px * 4, fl));
+  HIP_TRY(m->hs.ensure(px));
   for (int32_t i = 0; i < m->n; ++i) {
     HIP_TRY(hipSetDevice(m->dev[i]));
-    HIP_TRY(hipHostGetDevicePointer((void **)&m->hs_c_dev[i], m->hs_c, 0));
-    HIP_TRY(hipHostGetDevicePointer((void **)&m->hs_t_dev[i], m->hs_t, 0));
+    HIP_TRY(hipHostGetDevicePointer((void **)&m->hs_c_dev[i], m->hs.c, 0));
+    HIP_TRY(hipHostGetDevicePointer((void **)&m->hs_t_dev[i], m->hs.t, 0));
   }
-  m->hs_cap = px;
-  m->hs_dirty = true;
   return RT_OK;
 }
 
@@ -440,10 +429,7 @@ int rt_multi_render(rt_multi *m, const rt_render_params *p, uint32_t *color, flo
         rows = std::max(rows, (int32_t)(rt_tile_pixels(W, H, &tl) / W));
       }
       if (int rc = ensure_spans(m, rows)) return rc;
-      if (m->hs_dirty) {  // (a cleared frame stays cleared: the host resets each copied span)
-        rth::clear_frame(m->hs_c, m->hs_t, (int64_t)px, 8);
-        m->hs_dirty = false;
-      }
+      m->hs.clear_for(W, H);  // (a cleared frame stays cleared: the host resets each copied span)
       for (int32_t i = 0; i < m->n; ++i) {
         dc[i] = m->hs_c_dev[i];
         dt[i] = m->hs_t_dev[i];
@@ -451,7 +437,7 @@ int rt_multi_render(rt_multi *m, const rt_render_params *p, uint32_t *color, flo
     }
     HIP_TRY(hipSetDevice(m->dev[0]));
     HIP_TRY(hipEventRecord(m->ev0, m->st[0]));
-    if (!direct) m->hs_dirty = true;  // until the spans are copied and reset below
+    if (!direct) m->hs.mark_dirty();  // until the spans are copied and reset below
     for (int32_t i = 0; i < m->n; ++i) {
       HIP_TRY(hipSetDevice(m->dev[i]));
       if (i > 0) HIP_TRY(hipStreamWaitEvent(m->st[i], m->ev0, 0));
@@ -488,8 +474,8 @@ int rt_multi_render(rt_multi *m, const rt_render_params *p, uint32_t *color, flo
           m->merged[2 * (size_t)yo + 1] = m->h_span[i][2 * yl + 1];
         }
       }
-      rth::copy_spans(color, t, m->hs_c, m->hs_t, W, H, m->merged.data(), 0, true);
-      m->hs_dirty = false;
+      rth::copy_spans(color, t, m->hs.c, m->hs.t, W, H, m->merged.data(), 0, true);
+      m->hs.mark_clean();
     }
     if (ms) HIP_TRY(hipEventElapsedTime(ms, m->ev0, m->ev1));
     return RT_OK;
@@ -497,10 +483,10 @@ int rt_multi_render(rt_multi *m, const rt_render_params *p, uint32_t *color, flo
   if (int rc = ensure(m, W, H, 1, true)) return rc;
   if (!direct) {
     if (int rc = ensure_host_stage(m, px)) return rc;
-    m->hs_dirty = true;
+    m->hs.mark_dirty();
   }
-  uint32_t *hc = direct ? color : m->hs_c;  // where the DMAs read / write on the host
-  float *ht = direct ? t : m->hs_t;
+  uint32_t *hc = direct ? color : m->hs.c;  // where the DMAs read / write on the host
+  float *ht = direct ? t : m->hs.t;
   HIP_TRY(hipSetDevice(m->dev[0]));
   HIP_TRY(hipEventRecord(m->ev0, m->st[0]));
   const bool clear = (flags & RT_FLAG_CLEAR) != 0;
