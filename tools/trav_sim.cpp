@@ -15,7 +15,12 @@
 // it), so the results would be the same bits; the question is the cost.
 // Output: lane utilisation, wave instructions and iterations per policy.
 //
-// build: g++ -O2 -std=c++17 -Iinclude tools/trav_sim.cpp \
+// trav_sim --resume [obj W H]: the loop's second dependent round trip (the
+// reload when a frame resumes) under the loop as it was and with the frame
+// keeping its second child's entry t; see resume_model below
+// (profiles/r07/trav_sim_resume.txt).
+//
+// build: g++ -O2 -std=c++17 -Iinclude tools/trav_sim.cpp
 //          -Ltriangles-sdf-cpu-raytracing_amd/lib -lrtamd -Wl,-rpath,... -o /tmp/trav_sim
 #include <algorithm>
 #include <cmath>
@@ -183,9 +188,279 @@ void replay(const std::vector<std::string> &s, int policy, double cI, double cL,
   }
 }
 
+// ---- --resume: the kernel's iteration structure, with its second round trip --
+// mesh_run (csrc/rt_scenes.h) replayed per ray as a state machine instead of the
+// recursion above: one record per loop iteration. An iteration has a top part
+// -- expand an inner node (I), test a leaf (L), or nothing (P: the pop-only
+// iteration that follows a resume ending in a prune) -- and a "choose the next
+// child" tail. The top part's node or triangle fetch is one dependent global
+// round trip; a tail that resumes a frame at a child whose entry t is not at
+// hand reloads the child's box and word: a second one, exposed after the first.
+// Variants:
+//   V0  the loop as it was: every resume reloads and recomputes the slab test;
+//   V1  the frame keeps its second child's entry t (RT_MESH_T2): a prune there
+//       costs no load and the frames below are unwound in the same iteration,
+//       a visit loads only the 4-byte child word;
+//   V2  V1 + the loads of the frame looked at after a leaf are issued with the
+//       leaf's triangle batch (one wait covers both): not exposed.
+// Per ray: round trips by class. Per wave tile (lockstep, the minority side of
+// a leaf / inner split waits, RT_MESH_MAJ = 1): wave iterations, iterations in
+// which any advancing lane needs the second round trip, exposed round trips
+// (first + second). The cooperative tail is not modelled: its 8-lane groups
+// walk the same per-ray sequence.
+struct Iter {
+  char top;      // 'I', 'L' (leaf, either batch count), 'P'
+  bool second;   // the tail needs a global round trip after the top part's
+};
+struct RayCounts {
+  double inner = 0, leaf = 0, two = 0, pushed = 0, resume_visit = 0, resume_prune = 0, prune_second = 0,
+         visit_second = 0, visit_later = 0, pop_only = 0, prune_stored = 0, visit_stored = 0, hoisted = 0, iters = 0;
+};
+struct Frame {
+  uint32_t node;
+  int id[8];
+  float t[8];
+  int n, next;
+  float best;
+};
+
+// the sorted, entered children of an inner node (expand_node)
+Frame expand(uint32_t ni, V3 o, V3 inv, float tn, float tf) {
+  const Node &nd = nodes[ni];
+  float t[8];
+  int id[8];
+  for (int c = 0; c < 8; ++c) {
+    t[c] = (uint32_t)c < nd.n ? slab(nd.box, c, o, inv, tn, tf) : -1.0f;
+    id[c] = c;
+  }
+  const int net[19][2] = {{0, 1}, {2, 3}, {4, 5}, {6, 7}, {0, 2}, {1, 3}, {4, 6}, {5, 7}, {1, 2}, {5, 6},
+                          {0, 4}, {3, 7}, {1, 5}, {2, 6}, {1, 4}, {3, 6}, {2, 4}, {3, 5}, {3, 4}};
+  for (auto &p : net)
+    if (t[p[0]] > t[p[1]]) {
+      std::swap(t[p[0]], t[p[1]]);
+      std::swap(id[p[0]], id[p[1]]);
+    }
+  Frame f{};
+  f.node = ni;
+  f.best = INFINITY;
+  for (int i = 0; i < 8; ++i)
+    if (!(t[i] < 0.0f) && (uint32_t)id[i] < nd.n) { f.id[f.n] = id[i]; f.t[f.n] = t[i]; ++f.n; }
+  return f;
+}
+
+// one ray through mesh_run's loop; variant 0, 1, 2 as above
+void run_ray(V3 o, V3 d, V3 inv, float tn, float tf, int variant, std::vector<Iter> &seq, RayCounts &rc) {
+  seq.clear();
+  if (nodes[0].leaf) return;
+  std::vector<Frame> st;  // st.back() = the top frame (the kernel keeps it in registers)
+  Frame root = expand(0, o, inv, tn, tf);  // mesh_root: before the loop, not an iteration
+  if (root.n == 0) return;
+  rc.two += root.n >= 2;
+  st.push_back(root);
+  bool have_t = true;
+  int64_t word = -1;
+  for (;;) {
+    Iter it{'P', false};
+    if (word >= 0) {
+      const Node &nd = nodes[(size_t)word];
+      if (nd.leaf) {
+        it.top = 'L';
+        rc.leaf += 1;
+        float lt = INFINITY;
+        for (uint32_t k = 0; k < nd.n / 3; ++k) {
+          const float t = tri(nd.start / 3 + k, o, d);
+          if (lt > t) lt = t;
+        }
+        if (lt < st.back().best) st.back().best = lt;
+      } else {
+        it.top = 'I';
+        rc.inner += 1;
+        Frame f = expand((uint32_t)word, o, inv, tn, tf);
+        rc.two += f.n >= 2;
+        if (f.n != 0) {
+          if (st.back().next == st.back().n) {  // tail call: the top frame is replaced
+            if (st.size() >= 2 && st.back().best < st[st.size() - 2].best) st[st.size() - 2].best = st.back().best;
+            st.back() = f;
+          } else {
+            rc.pushed += 1;
+            st.push_back(f);
+          }
+          have_t = true;
+        }
+      }
+      word = -1;
+    } else if (!seq.empty() || !have_t) {
+      rc.pop_only += 1;
+    }
+    bool done = false, first = true;
+    for (;;) {
+      if (st.back().next == st.back().n) {  // frame done: fold into the one below
+        const float cb = st.back().best;
+        st.pop_back();
+        if (st.empty()) { done = true; break; }
+        if (cb < st.back().best) st.back().best = cb;
+        have_t = false;
+      }
+      Frame &f = st.back();
+      const int k = f.next++;
+      const float t = f.t[k];
+      const int64_t child = (int64_t)nodes[f.node].child[f.id[k]];
+      if (have_t) {  // fresh frame, first child: registers
+        have_t = false;
+        word = child;
+        break;
+      }
+      const bool covered = variant >= 2 && it.top == 'L' && first;  // issued with the leaf's batch
+      first = false;
+      if (variant >= 1 && k == 1) {  // the stored entry t
+        if (f.best < t) {
+          rc.prune_stored += 1;
+          rc.resume_prune += 1;
+          rc.prune_second += 1;
+          f.next = f.n;
+          continue;  // unwound in this iteration
+        }
+        rc.visit_stored += 1;
+        rc.resume_visit += 1;
+        rc.visit_second += 1;
+        if (covered) rc.hoisted += 1; else it.second = true;
+        word = child;
+        break;
+      }
+      if (covered) rc.hoisted += 1; else it.second = true;
+      if (!(f.best < t)) {
+        rc.resume_visit += 1;
+        (k == 1 ? rc.visit_second : rc.visit_later) += 1;
+        word = child;
+      } else {
+        rc.resume_prune += 1;
+        if (k == 1) rc.prune_second += 1;
+        f.next = f.n;  // the next iteration pops
+      }
+      break;
+    }
+    seq.push_back(it);
+    rc.iters += 1;
+    if (done) break;
+  }
+}
+
+struct TileCost {
+  double iters = 0, second = 0, exposed = 0, chain = 0;
+};
+
+// lockstep replay of one tile under the kernel's majority rule (K = 1)
+TileCost replay_resume(const std::vector<std::vector<Iter>> &s) {
+  TileCost c;
+  std::vector<size_t> pos(s.size(), 0);
+  for (auto &q : s) {
+    double ch = 0;
+    for (auto &i : q) ch += (i.top != 'P') + i.second;
+    c.chain = std::max(c.chain, ch);
+  }
+  for (;;) {
+    int nI = 0, nL = 0, live = 0;
+    for (size_t k = 0; k < s.size(); ++k) {
+      if (pos[k] >= s[k].size()) continue;
+      ++live;
+      nI += s[k][pos[k]].top == 'I';
+      nL += s[k][pos[k]].top == 'L';
+    }
+    if (!live) break;
+    const bool waitL = nL < nI, waitI = !waitL && nI < nL;
+    bool top = false, second = false;
+    for (size_t k = 0; k < s.size(); ++k) {
+      if (pos[k] >= s[k].size()) continue;
+      const Iter &i = s[k][pos[k]];
+      if ((i.top == 'L' && waitL) || (i.top == 'I' && waitI)) continue;
+      top |= i.top != 'P';
+      second |= i.second;
+      ++pos[k];
+    }
+    c.iters += 1;
+    c.second += second;
+    c.exposed += (double)top + (double)second;
+  }
+  return c;
+}
+
+template <class Eye>
+int resume_model(Eye eye, V3 org, int W, int H) {
+  const char *vname[3] = {"V0 every resume reloads", "V1 stored second-child t", "V2 V1 + post-leaf loads hoisted"};
+  RayCounts rc[3];
+  std::vector<TileCost> tiles[3];
+  for (int ty = 0; ty < H / 8; ++ty)
+    for (int tx = 0; tx < W / 8; ++tx) {
+      std::vector<std::vector<Iter>> seqs[3];
+      for (int v = 0; v < 3; ++v) seqs[v].resize(64);
+      bool any = false;
+      for (int l = 0; l < 64; ++l) {
+        const int x = tx * 8 + (l & 7), yo = ty * 8 + (l >> 3), y = H - yo - 1;
+        const V3 d = eye(x, y);
+        const V3 inv{1.0f / d.x, 1.0f / d.y, 1.0f / d.z};
+        for (int v = 0; v < 3; ++v) run_ray(org, d, inv, 0.01f, 100.0f, v, seqs[v][l], rc[v]);
+        any |= !seqs[0][l].empty();
+      }
+      if (!any) continue;
+      for (int v = 0; v < 3; ++v) tiles[v].push_back(replay_resume(seqs[v]));
+    }
+  std::printf("rays %d, wave tiles with a ray past the root %zu\n\n", W * H, tiles[0].size());
+  std::printf("per-ray totals (one frame)%34s%14s%14s\n", "V0", "V1", "V2");
+  auto row = [&](const char *n, double RayCounts::*m) {
+    std::printf("  %-44s%14.0f%14.0f%14.0f\n", n, rc[0].*m, rc[1].*m, rc[2].*m);
+  };
+  row("inner visits below the root (node fetch)", &RayCounts::inner);
+  row("leaf visits (triangle batch fetch)", &RayCounts::leaf);
+  row("frames with >= 2 entered children", &RayCounts::two);
+  row("frames pushed to the LDS stack", &RayCounts::pushed);
+  row("resumes that visit the child", &RayCounts::resume_visit);
+  row("  at the frame's second child", &RayCounts::visit_second);
+  row("  at a third or later child", &RayCounts::visit_later);
+  row("resumes that end in a prune", &RayCounts::resume_prune);
+  row("  at the frame's second child", &RayCounts::prune_second);
+  row("pop-only iterations", &RayCounts::pop_only);
+  row("prunes decided from the stored t (no load)", &RayCounts::prune_stored);
+  row("visits from the stored t (4-byte load)", &RayCounts::visit_stored);
+  row("resume loads issued with a leaf's batch", &RayCounts::hoisted);
+  row("lane iterations (with each ray's first)", &RayCounts::iters);
+  std::printf("  dependent global round trips per lane chain:\n");
+  for (int v = 0; v < 3; ++v) {
+    const double resume = rc[v].resume_visit + rc[v].resume_prune - rc[v].prune_stored;
+    const double exposed = resume - rc[v].hoisted;
+    const double all = rc[v].inner + rc[v].leaf + exposed;
+    std::printf("    %-34s node %.0f + leaf %.0f + resume %.0f (of %.0f loads) = %.0f (resume share %.1f %%)\n", vname[v],
+                rc[v].inner, rc[v].leaf, exposed, resume, all, 100.0 * exposed / all);
+  }
+  // the launch tail: the 1 % of tiles with the most exposed round trips under V0
+  std::vector<size_t> order(tiles[0].size());
+  for (size_t i = 0; i < order.size(); ++i) order[i] = i;
+  std::sort(order.begin(), order.end(), [&](size_t a, size_t b) { return tiles[0][a].exposed > tiles[0][b].exposed; });
+  const size_t ntail = std::max<size_t>(1, order.size() / 100);
+  std::printf("\nwave tiles in lockstep (minority side waits, K = 1)\n");
+  std::printf("  %-34s%12s%16s%16s%16s\n", "", "wave iters", "with 2nd trip", "exposed trips", "longest chain");
+  for (int part = 0; part < 2; ++part) {
+    std::printf("  %s\n", part == 0 ? "whole frame" : "slowest 1 % of tiles (by V0 exposed trips)");
+    double base = 0;
+    for (int v = 0; v < 3; ++v) {
+      TileCost s;
+      const size_t n = part == 0 ? order.size() : ntail;
+      for (size_t i = 0; i < n; ++i) {
+        const TileCost &t = tiles[v][order[i]];
+        s.iters += t.iters; s.second += t.second; s.exposed += t.exposed; s.chain = std::max(s.chain, t.chain);
+      }
+      if (v == 0) base = s.exposed;
+      std::printf("  %-34s%12.0f%16.0f%16.0f%16.0f   (x%.3f exposed vs V0)\n", vname[v], s.iters, s.second, s.exposed,
+                  s.chain, s.exposed / base);
+    }
+  }
+  return 0;
+}
+
 }  // namespace
 
 int main(int argc, char **argv) {
+  const bool resume = argc > 1 && std::strcmp(argv[1], "--resume") == 0;
+  if (resume) { --argc; ++argv; }
   const char *obj = argc > 1 ? argv[1] : "data/_unpacked/stanford-bunny.obj";
   const int W = argc > 2 ? std::atoi(argv[2]) : 1920, H = argc > 3 ? std::atoi(argv[3]) : 1080;
   const double cI = argc > 4 ? std::atof(argv[4]) : 250, cL = argc > 5 ? std::atof(argv[5]) : 360,
@@ -223,6 +498,7 @@ int main(int argc, char **argv) {
     return V3{vi[0] * dd.x + vi[4] * dd.y + vi[8] * dd.z, vi[1] * dd.x + vi[5] * dd.y + vi[9] * dd.z,
               vi[2] * dd.x + vi[6] * dd.y + vi[10] * dd.z};
   };
+  if (resume) return resume_model(eye, V3{pos[0], pos[1], pos[2]}, W, H);
   Cost c[3];
   double both = 0, iters0 = 0, steps = 0;
   long tiles = 0, busy_tiles = 0, root_only = 0;

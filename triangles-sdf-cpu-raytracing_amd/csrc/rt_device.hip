@@ -72,7 +72,8 @@ struct FrameArgs {
 };
 
 // ---------------------------------------------------------- scene adapters --
-// kFields = LDS words per traversal frame (mesh: node, list|count, best t;
+// kFields = LDS words per traversal frame (mesh: node, list|count, best t and,
+// for stacks of up to 7 slots, the second child's entry t, mesh_fields;
 // octree: node, list|count; grid: none).
 // occupancy floors (min_waves below), overridable for A/B builds
 #ifndef RT_GRID_WAVES
@@ -98,8 +99,9 @@ struct FrameArgs {
 #ifndef RT_GENERAL_WAVES
 #define RT_GENERAL_WAVES 4
 #endif
-struct MeshS {
-  static constexpr int kFields = 3;
+template <int F>
+struct MeshSF {
+  static constexpr int kFields = F;
   static constexpr bool kCoop = true;  // primary rays: wave-cooperative tail (mesh_primary_wave)
   static constexpr int kMinWaves = RT_MESH_WAVES;
   static constexpr int kQueueGroup = 2;  // wave tiles per work-queue item (render_persist_kernel)
@@ -117,7 +119,7 @@ struct MeshS {
     float t;
     uint32_t k;
     Hit h = miss_hit();
-    if (mesh_primary_wave<B>(d, o, dir, tn, tf, active, stk, t, k, coop_rays, prio_iters) && active) {
+    if (mesh_primary_wave<B, kFields>(d, o, dir, tn, tf, active, stk, t, k, coop_rays, prio_iters) && active) {
       h.hit = true;
       h.t = t;
       h.n = tri_normal(d.tris, k);
@@ -136,6 +138,9 @@ struct MeshS {
     return mesh_occluded<B>(d, o, dir, tn, tf, st, cnt);
   }
 };
+// the mesh adapter of a kernel with SLOTS stack slots
+template <int SLOTS>
+using MeshS = MeshSF<mesh_fields<SLOTS>()>;
 template <int kMode>
 struct GridS {
   static constexpr int kFields = 1;  // no traversal stack (one unused LDS word per lane)
@@ -1544,12 +1549,12 @@ int launch_render(rt_scene *s, const FrameArgs &fa_in, hipStream_t stream,
     if (rc) return rc;
   }
   if (s->kind == RT_SCENE_MESH) {
-    MeshS sc{mesh_dev(s)};
+    const MeshDev md = mesh_dev(s);
     switch (s->maxd) {
-      case 4: launch_render_t<MeshS, 4>(sc, s->plane, fa, general, stream, counters, diag); break;
-      case 7: launch_render_t<MeshS, 7>(sc, s->plane, fa, general, stream, counters, diag); break;
-      case 15: launch_render_t<MeshS, 15>(sc, s->plane, fa, general, stream, counters, diag); break;
-      default: launch_render_t<MeshS, 31>(sc, s->plane, fa, general, stream, counters, diag); break;
+      case 4: launch_render_t<MeshS<4>, 4>(MeshS<4>{md}, s->plane, fa, general, stream, counters, diag); break;
+      case 7: launch_render_t<MeshS<7>, 7>(MeshS<7>{md}, s->plane, fa, general, stream, counters, diag); break;
+      case 15: launch_render_t<MeshS<15>, 15>(MeshS<15>{md}, s->plane, fa, general, stream, counters, diag); break;
+      default: launch_render_t<MeshS<31>, 31>(MeshS<31>{md}, s->plane, fa, general, stream, counters, diag); break;
     }
   } else if (s->kind == RT_SCENE_GRID) {
     const GridDev gd = grid_dev(s);
@@ -1851,12 +1856,12 @@ int launch_batch(rt_scene *s, FrameBatch &fb, int n, hipStream_t stream) {
   }
   int rc = RT_OK;
   if (s->kind == RT_SCENE_MESH) {
-    MeshS sc{mesh_dev(s)};
+    const MeshDev md = mesh_dev(s);
     switch (s->maxd) {
-      case 4: rc = launch_batch_t<MeshS, 4>(s, sc, s->plane, fb, n, general, stream); break;
-      case 7: rc = launch_batch_t<MeshS, 7>(s, sc, s->plane, fb, n, general, stream); break;
-      case 15: rc = launch_batch_t<MeshS, 15>(s, sc, s->plane, fb, n, general, stream); break;
-      default: rc = launch_batch_t<MeshS, 31>(s, sc, s->plane, fb, n, general, stream); break;
+      case 4: rc = launch_batch_t<MeshS<4>, 4>(s, MeshS<4>{md}, s->plane, fb, n, general, stream); break;
+      case 7: rc = launch_batch_t<MeshS<7>, 7>(s, MeshS<7>{md}, s->plane, fb, n, general, stream); break;
+      case 15: rc = launch_batch_t<MeshS<15>, 15>(s, MeshS<15>{md}, s->plane, fb, n, general, stream); break;
+      default: rc = launch_batch_t<MeshS<31>, 31>(s, MeshS<31>{md}, s->plane, fb, n, general, stream); break;
     }
   } else if (s->kind == RT_SCENE_GRID) {
     const GridDev gd = grid_dev(s);
@@ -2713,12 +2718,12 @@ int rt_intersect_rays(rt_scene *s, const float *o, const float *d, int64_t n, fl
       break;
     if ((e = rtdma::h2d(dO, o, n * 12, nullptr)) || (e = rtdma::h2d(dD, d, n * 12, nullptr))) break;
     if (s->kind == RT_SCENE_MESH) {
-      MeshS sc{mesh_dev(s)};
+      const MeshDev md = mesh_dev(s);
       switch (s->maxd) {
-        case 4: launch_rays_t<MeshS, 4>(sc, s->plane, dO, dD, n, tnear, tfar, dH, dT, dN, dP); break;
-        case 7: launch_rays_t<MeshS, 7>(sc, s->plane, dO, dD, n, tnear, tfar, dH, dT, dN, dP); break;
-        case 15: launch_rays_t<MeshS, 15>(sc, s->plane, dO, dD, n, tnear, tfar, dH, dT, dN, dP); break;
-        default: launch_rays_t<MeshS, 31>(sc, s->plane, dO, dD, n, tnear, tfar, dH, dT, dN, dP); break;
+        case 4: launch_rays_t<MeshS<4>, 4>(MeshS<4>{md}, s->plane, dO, dD, n, tnear, tfar, dH, dT, dN, dP); break;
+        case 7: launch_rays_t<MeshS<7>, 7>(MeshS<7>{md}, s->plane, dO, dD, n, tnear, tfar, dH, dT, dN, dP); break;
+        case 15: launch_rays_t<MeshS<15>, 15>(MeshS<15>{md}, s->plane, dO, dD, n, tnear, tfar, dH, dT, dN, dP); break;
+        default: launch_rays_t<MeshS<31>, 31>(MeshS<31>{md}, s->plane, dO, dD, n, tnear, tfar, dH, dT, dN, dP); break;
       }
     } else if (s->kind == RT_SCENE_GRID) {
       const GridDev gd = grid_dev(s);

@@ -168,16 +168,53 @@ __device__ __forceinline__ void leaf_test(const rtl::GTri *__restrict__ tris, ui
 // Expand an inner node: slab-test its 8 children, sort8, keep t >= 0 entries
 // (a suffix of the sorted order) as a packed list of 3-bit ids + count. Also
 // returns the entry distance and child word of the first child to visit (the
-// child words arrive with the boxes: descending needs no extra load).
+// child words arrive with the boxes: descending needs no extra load), and with
+// RT_MESH_T2 the entry distance of the SECOND child in visit order (has2 =
+// false when fewer than two are entered): the frame keeps it, so resuming at
+// that child needs no box reload (mesh_run).
 // 1: expand_node skips sort8 in waves whose rays all enter <= 2 children with
 // distinct t (A/B switch; 0 always runs the network)
 #ifndef RT_EXPAND_FAST
 #define RT_EXPAND_FAST 1
 #endif
+// 1: a frame keeps the entry distance of its second child (in a register for
+// the top frame, in a fourth LDS word for the stacked ones), and a resume at
+// that child prunes from it without touching memory or loads just the 4-byte
+// child word. 0: every resume reloads the child's box and recomputes the slab
+// test. A/B switch, off: bit-exact, but the extra live register and the loop
+// of pops spill inside the traversal loop at the 5-wave floor and the kernels
+// are slower.
+#ifndef RT_MESH_T2
+#define RT_MESH_T2 0
+#endif
+// 1: the loads a resume needs after a leaf test (the LDS frame below when the
+// top frame ends with the leaf, the next child's word and, without a stored t,
+// its box) are issued above the leaf test, with the triangle batch. 2: only
+// the LDS reads and the 4-byte child word of a child with a stored t. 0: the
+// tail loads them after the leaf test. A/B switch, off: up to 7 more registers
+// live across the leaf test's 48 spill there.
+#ifndef RT_MESH_HOIST
+#define RT_MESH_HOIST 0
+#endif
+// 1: a run of frames that each end by a prune decided from their stored t is
+// popped inside one traversal iteration (a loop of LDS reads). 0: each such
+// end takes the next iteration to pop, as an end decided from a reloaded box
+// does (A/B switch).
+#ifndef RT_MESH_UNWIND
+#define RT_MESH_UNWIND 1
+#endif
+// LDS words per stacked mesh frame: node, list | count << 24 | stored-t flag
+// << 27, local best t and, in the 4-word form, the second child's entry t.
+// Stacks deeper than 7 slots stay at 3 words (their kernels are LDS-limited:
+// a fourth word would cost them a wave per SIMD); their frames carry the
+// stored t only while they are the top frame.
+template <int SLOTS>
+constexpr int mesh_fields() { return RT_MESH_T2 && SLOTS <= 7 ? 4 : 3; }
 template <bool FAST>
 __device__ __forceinline__ void expand_node(const rtl::GNode *__restrict__ node, f3 o, f3 inv,
                                             float tNear, float tFar, uint32_t &list,
-                                            uint32_t &cnt, float &tfirst, uint32_t &cwfirst) {
+                                            uint32_t &cnt, float &tfirst, uint32_t &cwfirst,
+                                            float &tsecond, bool &has2) {
   const float4 *p = reinterpret_cast<const float4 *>(node);
   float bx[48];
 #pragma unroll
@@ -222,6 +259,7 @@ __device__ __forceinline__ void expand_node(const rtl::GNode *__restrict__ node,
       first_id = sw ? ib : ia;
       tfirst = pc == 0 ? 0.0f : (sw ? tb : ta);
       cnt = pc;
+      tsecond = sw ? ta : tb;
       list = pc == 0 ? 0u : pc == 1 ? ia : (sw ? (ib | (ia << 3)) : (ia | (ib << 3)));
     }
   }
@@ -230,11 +268,13 @@ __device__ __forceinline__ void expand_node(const rtl::GNode *__restrict__ node,
     list = 0;
     cnt = 0;
     tfirst = 0.0f;
+    tsecond = 0.0f;
 #pragma unroll
     for (int i = 7; i >= 0; --i) {  // build from the back so the first visit ends in the low bits
       if (!(t[i] < 0.0f)) {
         list = (list << 3) | id[i];
         cnt += 1;
+        tsecond = tfirst;
         tfirst = t[i];
         first_id = id[i];
       }
@@ -244,6 +284,7 @@ __device__ __forceinline__ void expand_node(const rtl::GNode *__restrict__ node,
 #pragma unroll
   for (int c = 1; c < 8; ++c) cf = (first_id == (uint32_t)c) ? cws[c] : cf;
   cwfirst = cf;
+  has2 = RT_MESH_T2 && cnt >= 2;
 }
 
 template <int BLOCK, int F = 3>
@@ -276,10 +317,10 @@ __device__ __forceinline__ bool root_box_miss(const float *b, f3 o, f3 inv, floa
 template <bool FAST = false, class CT>
 __device__ __forceinline__ bool mesh_root(const MeshDev &sc, f3 o, f3 inv, float tNear, float tFar,
                                           uint32_t &l, uint32_t &c, float &tf, uint32_t &cwf,
-                                          CT &cnt) {
+                                          float &ts, bool &has2, CT &cnt) {
   cnt.add(C_BVH_INNER, 1);
   if (root_box_miss(sc.rbox, o, inv, tNear, tFar)) return false;
-  expand_node<FAST>(sc.nodes + sc.root, o, inv, tNear, tFar, l, c, tf, cwf);
+  expand_node<FAST>(sc.nodes + sc.root, o, inv, tNear, tFar, l, c, tf, cwf, ts, has2);
   return c != 0;
 }
 
@@ -298,6 +339,8 @@ struct MState {
   float gbest;      // best t so far
   int32_t depth;    // frames on the stack, incl. the top one
   bool have_t;
+  float t2;         // top frame: entry t of its second child (valid with t2v)
+  bool t2v;         // the next child of the top frame is its second and t2 holds its entry t
 };
 
 // Frame ends by pruning handled per traversal iteration (1: one; the next
@@ -345,16 +388,57 @@ constexpr int kCoopRays = RT_COOP_RAYS;
 // "while-while" split into an inner-node phase and a leaf phase: bunny
 // 0.342 -> 0.523 ms.) TAIL: before each iteration, if kCoopRays or fewer lanes
 // of the wave are still looping, store the state and return true (suspended).
-template <int BLOCK, bool ANY, bool FAST, bool TAIL, uint32_t LB = RT_LEAF_BATCH, bool MAJ = false, class CT>
+//
+// Resuming a frame (RT_MESH_T2): a frame's first child is visited from the
+// expansion's registers; its second child's entry t stays with the frame (t2,
+// LDS word 3 once the frame is stacked, flag bit 27 of word 1). A resume at
+// the second child tests fbest < t2 without touching memory: pruned, the frame
+// ends and the frame below is popped in the same iteration (a loop of LDS
+// reads, at most the stack depth long, up to the first frame that yields a
+// child or has no stored t); not pruned, only the 4-byte child word is
+// loaded. Third and later children reload their box and child word and redo
+// the slab test, and a prune there ends the iteration as before. The stored
+// bits are those the slab test returned at expansion: the same function of
+// the same node and ray, so the same decision (a NaN stays a NaN: visited).
+template <int BLOCK, bool ANY, bool FAST, bool TAIL, uint32_t LB = RT_LEAF_BATCH, bool MAJ = false, int F, class CT>
 __device__ __forceinline__ bool mesh_run(const MeshDev &sc, f3 o, f3 d, f3 inv, float tNear, float tFar,
-                                         LdsStack<BLOCK> st, MState &S, CT &cnt, int coop_rays = kCoopRays,
+                                         LdsStack<BLOCK, F> st, MState &S, CT &cnt, int coop_rays = kCoopRays,
                                          int prio_iters = 0) {
-  uint32_t word = S.word, flist = S.flist, fcnt = S.fcnt, fnode = S.fnode, cwnext = S.cwnext, gk = S.gk;
-  float fbest = S.fbest, tnext = S.tnext, gbest = S.gbest;
+  uint32_t word = S.word, flist = S.flist, fcnt = S.fcnt, fnode = S.fnode, gk = S.gk;
+  float fbest = S.fbest, gbest = S.gbest, t2 = S.t2;
   int depth = S.depth;
-  bool have_t = S.have_t;
+  bool t2v = S.t2v;
   bool suspended = false;
   int it = 0;  // wave-uniform iteration count (prio_iters)
+  // A fresh frame handed in (S.have_t): its first child is chosen here, as the
+  // tail of the iteration that expanded it would, so that inside the loop the
+  // first child's t and word (tnext, cwnext, have_t) live within one iteration
+  // and not across the back-edge.
+  if (S.have_t) {
+    flist >>= 3;
+    fcnt -= 1;
+    if (!(fbest < S.tnext)) word = S.cwnext;
+    else fcnt = 0;
+    S.have_t = false;
+  }
+  // the frame below the top one becomes the top frame (depth >= 2); the ended
+  // frame's best folds into it
+  const auto pop = [&]() {
+    --depth;
+    const float child_best = fbest;
+    fnode = st.at(depth - 1, 0);
+    const uint32_t lc = st.at(depth - 1, 1);
+    flist = lc & 0xFFFFFFu;
+    fcnt = (lc >> 24) & 7u;  // a stacked frame has 1..7 children left
+    fbest = __uint_as_float(st.at(depth - 1, 2));
+    if (child_best < fbest) fbest = child_best;
+    if constexpr (F >= 4) {
+      t2v = ((lc >> 27) & 1u) != 0;
+      t2 = __uint_as_float(st.at(depth - 1, 3));
+    } else {
+      t2v = false;
+    }
+  };
   for (;;) {
     if (TAIL && __popcll(__ballot(1)) <= coop_rays) { suspended = true; break; }
     if (TAIL && prio_iters > 0) {
@@ -375,21 +459,63 @@ __device__ __forceinline__ bool mesh_run(const MeshDev &sc, f3 o, f3 d, f3 inv, 
       if ((isL && waitL) || (isI && waitI)) continue;
     }
 #endif
+    // loads of the child the tail below will look at, issued above a leaf test
+    // (RT_MESH_HOIST): pre = this lane's are in pcw (child word) and pb (box)
+    bool pre = false;
+    uint32_t pcw = 0;
+    float pb[6];
+    // a frame expanded in this iteration: its first child's entry t and word
+    bool have_t = false;
+    float tnext = 0.0f;
+    uint32_t cwnext = rtl::kInvalidChild;
     if (word != rtl::kInvalidChild) {
       if (word & rtl::kLeafBit) {
+        // A leaf test pushes no frame, so the frame the tail resumes after it
+        // is known here: the top frame if it has a child left, else the frame
+        // below, which is popped now (its LDS reads leave with the triangle
+        // batch; the leaf's t then folds through `ended`, the ended frame's
+        // best, as it would on the pop). The next child's word, and its box
+        // where its entry t is not stored, are loaded with the triangles: one
+        // wait covers both, and the tail finds them in registers.
+        float ended = kInf;
+        bool popped = false;
+        if constexpr (RT_MESH_HOIST != 0) {
+          if (fcnt == 0 && depth >= 2) {
+            ended = fbest;
+            fbest = kInf;  // (pop folds the ended frame's best at once: +inf leaves the frame's own)
+            pop();
+            popped = true;
+          }
+          if (fcnt != 0) {
+            const rtl::GNode *nd = mesh_node(sc, fnode);
+            const uint32_t j = flist & 7u;
+            pre = RT_MESH_HOIST == 1 || (RT_MESH_T2 && t2v);
+            if (pre) pcw = nd->child[j];
+            if (RT_MESH_HOIST == 1 && !(RT_MESH_T2 && t2v)) {
+#pragma unroll
+              for (int i = 0; i < 6; ++i) pb[i] = nd->box[j][i];
+            }
+          }
+        }
         float lt = kInf;
         uint32_t lk = rtl::kInvalidChild;
         leaf_test<LB, FAST>(sc.tris, word, o, d, lt, lk, cnt);
         if (lk != rtl::kInvalidChild) {
           if (ANY) { gbest = lt; gk = lk; break; }
-          if (lt < fbest) fbest = lt;
+          if (popped) {
+            if (lt < ended) ended = lt;
+          } else {
+            if (lt < fbest) fbest = lt;
+          }
           if (lt < gbest) { gbest = lt; gk = lk; }
         }
+        if (popped && ended < fbest) fbest = ended;
       } else {
         uint32_t l, c, cwf;
-        float tf;
+        float tf, ts;
+        bool has2;
         cnt.add(C_BVH_INNER, 1);
-        expand_node<FAST>(mesh_node(sc, word), o, inv, tNear, tFar, l, c, tf, cwf);
+        expand_node<FAST>(mesh_node(sc, word), o, inv, tNear, tFar, l, c, tf, cwf, ts, has2);
         if (c != 0) {
           if (depth >= 1 && fcnt == 0) {
             // tail call: the top frame has no child left, so it is replaced,
@@ -403,7 +529,12 @@ __device__ __forceinline__ bool mesh_run(const MeshDev &sc, f3 o, f3 d, f3 inv, 
           } else {
             if (depth >= 1) {
               st.at(depth - 1, 0) = fnode;
-              st.at(depth - 1, 1) = flist | (fcnt << 24);
+              if constexpr (F >= 4) {
+                st.at(depth - 1, 1) = flist | (fcnt << 24) | ((uint32_t)t2v << 27);
+                st.at(depth - 1, 3) = __float_as_uint(t2);
+              } else {
+                st.at(depth - 1, 1) = flist | (fcnt << 24);
+              }
               st.at(depth - 1, 2) = __float_as_uint(fbest);
             }
             ++depth;
@@ -412,56 +543,86 @@ __device__ __forceinline__ bool mesh_run(const MeshDev &sc, f3 o, f3 d, f3 inv, 
           tnext = tf;
           cwnext = cwf;
           have_t = true;
+          t2 = ts;
+          t2v = has2;
         }
       }
       word = rtl::kInvalidChild;
     }
-    // choose the next child; a pruned child ends its frame, and up to
-    // RT_MESH_PRUNE_PASSES - 1 such ends are popped in this same iteration
+    // choose the next child; a pruned child ends its frame. First the part
+    // that needs no global memory: pops, and prunes decided from a stored t
+    // (a loop of LDS reads, at most the stack depth long); then, in one place
+    // for every lane that needs one, the global load: the child word alone
+    // after a stored t that does not prune, else the child's box and word.
+    // After an end decided from a reloaded box, up to RT_MESH_PRUNE_PASSES - 1
+    // more such rounds follow in this iteration.
     bool done = false;
-#pragma unroll
     for (int pass = 0; pass < RT_MESH_PRUNE_PASSES; ++pass) {
-      if (depth == 0) { done = true; break; }
-      if (fcnt == 0) {  // frame done: fold its best into the parent frame
-        --depth;
+      bool load = false, stored = false;
+      uint32_t j = 0;
+      for (;;) {
         if (depth == 0) { done = true; break; }
-        const float child_best = fbest;
-        fnode = st.at(depth - 1, 0);
-        const uint32_t lc = st.at(depth - 1, 1);
-        flist = lc & 0xFFFFFFu;
-        fcnt = lc >> 24;
-        fbest = __uint_as_float(st.at(depth - 1, 2));
-        if (child_best < fbest) fbest = child_best;
-        have_t = false;
-        // stacked frames always have a child left: go on to it
+        if (fcnt == 0) {  // frame done: fold its best into the parent frame
+          if (depth == 1) { depth = 0; done = true; break; }
+          pop();
+          have_t = false;
+          // stacked frames always have a child left: go on to it
+        }
+        j = flist & 7u;
+        flist >>= 3;
+        fcnt -= 1;
+        if (have_t) break;  // fresh frame: its first child, from the expansion's registers
+        load = true;
+        stored = RT_MESH_T2 && t2v;
+        if (!stored) break;  // a third or later child (or no stored t): reload
+        t2v = false;
+        if (!(fbest < t2)) break;  // its second child, entered: only the child word is missing
+        fcnt = 0;  // pruned without a load
+        load = false;
+        pre = false;
+        if (!RT_MESH_UNWIND) { tnext = t2; break; }  // the next iteration pops
       }
-      const uint32_t j = flist & 7u;
-      flist >>= 3;
-      fcnt -= 1;
-      if (!have_t) {  // resumed frame: child box and word, loaded together
-        const rtl::GNode *nd = mesh_node(sc, fnode);
-        const float *b = nd->box[j];
-        cwnext = nd->child[j];
-        tnext = slab<FAST>(b[0], b[2], b[4], b[1], b[3], b[5], o, inv, tNear, tFar);
+      if (done) break;
+      if (load) {
+        float b[6];
+        if (pre) {  // issued above the leaf test
+          cwnext = pcw;
+          if (!stored) {
+#pragma unroll
+            for (int i = 0; i < 6; ++i) b[i] = pb[i];
+          }
+        } else {
+          const rtl::GNode *nd = mesh_node(sc, fnode);
+          cwnext = nd->child[j];
+          if (!stored) {
+#pragma unroll
+            for (int i = 0; i < 6; ++i) b[i] = nd->box[j][i];
+          }
+        }
+        // the stored bits are the ones this slab test would return again
+        if (stored) tnext = t2;
+        else tnext = slab<FAST>(b[0], b[2], b[4], b[1], b[3], b[5], o, inv, tNear, tFar);
       }
       have_t = false;
+      pre = false;
       if (!(fbest < tnext)) { word = cwnext; break; }
       fcnt = 0;  // pruned; later siblings have larger t
     }
     if (done) break;
   }
-  S.word = word; S.flist = flist; S.fcnt = fcnt; S.fnode = fnode; S.cwnext = cwnext; S.gk = gk;
-  S.fbest = fbest; S.tnext = tnext; S.gbest = gbest; S.depth = depth; S.have_t = have_t;
+  S.word = word; S.flist = flist; S.fcnt = fcnt; S.fnode = fnode; S.gk = gk;
+  S.fbest = fbest; S.gbest = gbest; S.depth = depth;
+  S.t2 = t2; S.t2v = t2v;
   return suspended;
 }
 
-template <int BLOCK, bool ANY, bool FAST = false, class CT>
+template <int BLOCK, bool ANY, bool FAST = false, int F, class CT>
 __device__ __forceinline__ bool mesh_continue(const MeshDev &sc, f3 o, f3 d, f3 inv, float tNear,
-                                              float tFar, LdsStack<BLOCK> st, uint32_t word,
+                                              float tFar, LdsStack<BLOCK, F> st, uint32_t word,
                                               uint32_t flist, uint32_t fcnt, float tnext,
-                                              uint32_t cwnext, bool have_t, int depth,
+                                              uint32_t cwnext, bool have_t, float t2, bool t2v, int depth,
                                               float &out_t, uint32_t &out_k, CT &cnt) {
-  MState S{word, flist, fcnt, sc.root, cwnext, rtl::kInvalidChild, kInf, tnext, kInf, depth, have_t};
+  MState S{word, flist, fcnt, sc.root, cwnext, rtl::kInvalidChild, kInf, tnext, kInf, depth, have_t, t2, t2v};
   mesh_run<BLOCK, ANY, FAST, false>(sc, o, d, inv, tNear, tFar, st, S, cnt);
   out_t = S.gbest;
   out_k = S.gk;
@@ -554,13 +715,13 @@ __device__ __forceinline__ uint32_t grp_or(uint32_t v, int k) {
 
 // mesh_run (non-ANY) executed by an 8-lane group on one ray; S is the same in
 // all 8 lanes and stays so. st = the owner lane's LDS stack column.
-template <int BLOCK, bool FAST>
+template <int BLOCK, bool FAST, int F>
 __device__ __forceinline__ void mesh_run_coop(const MeshDev &sc, f3 o, f3 d, f3 inv, float tNear,
-                                              float tFar, LdsStack<BLOCK> st, MState &S, int k) {
+                                              float tFar, LdsStack<BLOCK, F> st, MState &S, int k) {
   uint32_t word = S.word, flist = S.flist, fcnt = S.fcnt, fnode = S.fnode, cwnext = S.cwnext, gk = S.gk;
-  float fbest = S.fbest, tnext = S.tnext, gbest = S.gbest;
+  float fbest = S.fbest, tnext = S.tnext, gbest = S.gbest, t2 = S.t2;
   int depth = S.depth;
-  bool have_t = S.have_t;
+  bool have_t = S.have_t, t2v = S.t2v;
   const int gbase = (threadIdx.x & 63) & ~7;
   for (;;) {
     if (word != rtl::kInvalidChild) {
@@ -594,6 +755,7 @@ __device__ __forceinline__ void mesh_run_coop(const MeshDev &sc, f3 o, f3 d, f3 
         const float tf = __shfl(t, gbase + (int)(i0 & 7u), 64);
         const uint32_t idf = __shfl(id, gbase + (int)(i0 & 7u), 64);
         const uint32_t cwf = __shfl(cwk, gbase + (int)idf, 64);
+        const float ts = __shfl(t, gbase + (int)((i0 + 1u) & 7u), 64);  // the second child's entry t
         if (c != 0) {
           if (depth >= 1 && fcnt == 0) {  // tail call, as in mesh_run
             if (depth >= 2) {
@@ -603,7 +765,12 @@ __device__ __forceinline__ void mesh_run_coop(const MeshDev &sc, f3 o, f3 d, f3 
           } else {
             if (depth >= 1) {
               st.at(depth - 1, 0) = fnode;
-              st.at(depth - 1, 1) = flist | (fcnt << 24);
+              if constexpr (F >= 4) {
+                st.at(depth - 1, 1) = flist | (fcnt << 24) | ((uint32_t)t2v << 27);
+                st.at(depth - 1, 3) = __float_as_uint(t2);
+              } else {
+                st.at(depth - 1, 1) = flist | (fcnt << 24);
+              }
               st.at(depth - 1, 2) = __float_as_uint(fbest);
             }
             ++depth;
@@ -612,6 +779,8 @@ __device__ __forceinline__ void mesh_run_coop(const MeshDev &sc, f3 o, f3 d, f3 
           tnext = tf;
           cwnext = cwf;
           have_t = true;
+          t2 = ts;
+          t2v = RT_MESH_T2 && c >= 2;
         }
       }
       word = rtl::kInvalidChild;
@@ -624,21 +793,33 @@ __device__ __forceinline__ void mesh_run_coop(const MeshDev &sc, f3 o, f3 d, f3 
       fnode = st.at(depth - 1, 0);
       const uint32_t lc = st.at(depth - 1, 1);
       flist = lc & 0xFFFFFFu;
-      fcnt = lc >> 24;
+      fcnt = (lc >> 24) & 7u;
       fbest = __uint_as_float(st.at(depth - 1, 2));
       if (child_best < fbest) fbest = child_best;
       have_t = false;
+      if constexpr (F >= 4) {
+        t2v = ((lc >> 27) & 1u) != 0;
+        t2 = __uint_as_float(st.at(depth - 1, 3));
+      } else {
+        t2v = false;
+      }
     }
     const uint32_t j = flist & 7u;
     flist >>= 3;
     fcnt -= 1;
-    if (!have_t) {
+    if (have_t) {
+      have_t = false;
+    } else if (RT_MESH_T2 && t2v) {  // second child: the stored entry t, as in mesh_run
+      t2v = false;
+      if (fbest < t2) { fcnt = 0; continue; }
+      word = mesh_node(sc, fnode)->child[j];
+      continue;
+    } else {
       const rtl::GNode *nd = mesh_node(sc, fnode);
       const float *b = nd->box[j];
       cwnext = nd->child[j];
       tnext = slab<FAST>(b[0], b[2], b[4], b[1], b[3], b[5], o, inv, tNear, tFar);
     }
-    have_t = false;
     if (fbest < tnext) { fcnt = 0; continue; }
     word = cwnext;
   }
@@ -650,7 +831,7 @@ __device__ __forceinline__ void mesh_run_coop(const MeshDev &sc, f3 o, f3 d, f3 
 // call it, with active = false for lanes without a pixel): each lane traverses
 // its own ray until at most kCoopRays rays remain, then those finish in 8-lane
 // groups. The result is the same as mesh_trace's, bit for bit.
-template <int BLOCK>
+template <int BLOCK, int F>
 __device__ __forceinline__ bool mesh_primary_wave(const MeshDev &sc, f3 o, f3 d, float tNear, float tFar,
                                                   bool active, uint32_t *stk_block, float &out_t,
                                                   uint32_t &out_k, int coop_rays = kCoopRays,
@@ -658,13 +839,13 @@ __device__ __forceinline__ bool mesh_primary_wave(const MeshDev &sc, f3 o, f3 d,
   if (prio_iters > 0) __builtin_amdgcn_s_setprio(0);  // a new tile starts at normal priority
   NoCnt cnt;
   const int lane = threadIdx.x & 63;
-  LdsStack<BLOCK> st{stk_block + threadIdx.x};
+  LdsStack<BLOCK, F> st{stk_block + threadIdx.x};
   const f3 inv{1.0f / d.x, 1.0f / d.y, 1.0f / d.z};  // 1.0f / rayDir (:273)
   // fast: the finite-1/d slab forms and the fast reciprocal (MeshDev::dmax2)
   const bool fast = __builtin_isfinite(inv.x) && __builtin_isfinite(inv.y) && __builtin_isfinite(inv.z) &&
                     dot(d, d) <= sc.dmax2;
   MState S{rtl::kInvalidChild, 0u, 0u, sc.root, rtl::kInvalidChild, rtl::kInvalidChild, kInf, 0.0f, kInf, 0,
-           false};
+           false, 0.0f, false};
   bool pending = false;
   if (active && sc.root != rtl::kInvalidChild) {
     if (sc.root & rtl::kLeafBit) {
@@ -672,11 +853,13 @@ __device__ __forceinline__ bool mesh_primary_wave(const MeshDev &sc, f3 o, f3 d,
       pending = true;
     } else {
       uint32_t l, c, cwf;
-      float tf;
-      const bool entered = fast ? mesh_root<true>(sc, o, inv, tNear, tFar, l, c, tf, cwf, cnt)
-                                : mesh_root<false>(sc, o, inv, tNear, tFar, l, c, tf, cwf, cnt);
+      float tf, ts;
+      bool has2;
+      const bool entered = fast ? mesh_root<true>(sc, o, inv, tNear, tFar, l, c, tf, cwf, ts, has2, cnt)
+                                : mesh_root<false>(sc, o, inv, tNear, tFar, l, c, tf, cwf, ts, has2, cnt);
       if (entered) {
         S.flist = l; S.fcnt = c; S.tnext = tf; S.cwnext = cwf; S.depth = 1; S.have_t = true;
+        S.t2 = ts; S.t2v = has2;
         pending = true;
       }
     }
@@ -725,8 +908,10 @@ __device__ __forceinline__ bool mesh_primary_wave(const MeshDev &sc, f3 o, f3 d,
     G.gbest = __shfl(S.gbest, owner, 64);
     G.depth = __shfl(S.depth, owner, 64);
     G.have_t = __shfl((int)S.have_t, owner, 64) != 0;
+    G.t2 = __shfl(S.t2, owner, 64);
+    G.t2v = __shfl((int)S.t2v, owner, 64) != 0;
     if (g < n) {
-      const LdsStack<BLOCK> gst{stk_block + (threadIdx.x & ~63) + owner};
+      const LdsStack<BLOCK, F> gst{stk_block + (threadIdx.x & ~63) + owner};
       if (gfast)
         mesh_run_coop<BLOCK, true>(sc, go, gd, ginv, tNear, gtf, gst, G, k);
       else
@@ -743,31 +928,32 @@ __device__ __forceinline__ bool mesh_primary_wave(const MeshDev &sc, f3 o, f3 d,
   return S.gk != rtl::kInvalidChild;
 }
 
-template <int BLOCK, bool ANY, class CT>
+template <int BLOCK, bool ANY, int F, class CT>
 __device__ __forceinline__ bool mesh_trace(const MeshDev &sc, f3 o, f3 d, float tNear, float tFar,
-                                           LdsStack<BLOCK> st, float &out_t, uint32_t &out_k,
+                                           LdsStack<BLOCK, F> st, float &out_t, uint32_t &out_k,
                                            CT &cnt) {
   const f3 inv{1.0f / d.x, 1.0f / d.y, 1.0f / d.z};  // 1.0f / rayDir (:273)
   if (sc.root == rtl::kInvalidChild) return false;
   if (sc.root & rtl::kLeafBit)
     return mesh_continue<BLOCK, ANY>(sc, o, d, inv, tNear, tFar, st, sc.root, 0u, 0u, 0.0f,
-                                     rtl::kInvalidChild, false, 0, out_t, out_k, cnt);
+                                     rtl::kInvalidChild, false, 0.0f, false, 0, out_t, out_k, cnt);
   uint32_t l, c, cwf;
-  float tf;
+  float tf, ts;
+  bool has2;
   if (__builtin_isfinite(inv.x) && __builtin_isfinite(inv.y) && __builtin_isfinite(inv.z) &&
       dot(d, d) <= sc.dmax2) {  // (see mesh_primary_wave)
-    if (!mesh_root<true>(sc, o, inv, tNear, tFar, l, c, tf, cwf, cnt)) return false;
+    if (!mesh_root<true>(sc, o, inv, tNear, tFar, l, c, tf, cwf, ts, has2, cnt)) return false;
     return mesh_continue<BLOCK, ANY, true>(sc, o, d, inv, tNear, tFar, st, rtl::kInvalidChild, l, c, tf,
-                                           cwf, true, 1, out_t, out_k, cnt);
+                                           cwf, true, ts, has2, 1, out_t, out_k, cnt);
   }
-  if (!mesh_root<false>(sc, o, inv, tNear, tFar, l, c, tf, cwf, cnt)) return false;
+  if (!mesh_root<false>(sc, o, inv, tNear, tFar, l, c, tf, cwf, ts, has2, cnt)) return false;
   return mesh_continue<BLOCK, ANY, false>(sc, o, d, inv, tNear, tFar, st, rtl::kInvalidChild, l, c, tf,
-                                          cwf, true, 1, out_t, out_k, cnt);
+                                          cwf, true, ts, has2, 1, out_t, out_k, cnt);
 }
 
-template <int BLOCK, class CT>
+template <int BLOCK, int F, class CT>
 __device__ __forceinline__ Hit mesh_intersect(const MeshDev &sc, f3 o, f3 d, float tNear, float tFar,
-                                              LdsStack<BLOCK> st, CT &cnt) {
+                                              LdsStack<BLOCK, F> st, CT &cnt) {
   float t;
   uint32_t k;
   Hit h = miss_hit();
@@ -779,9 +965,9 @@ __device__ __forceinline__ Hit mesh_intersect(const MeshDev &sc, f3 o, f3 d, flo
   }
   return h;
 }
-template <int BLOCK, class CT>
+template <int BLOCK, int F, class CT>
 __device__ __forceinline__ bool mesh_occluded(const MeshDev &sc, f3 o, f3 d, float tNear, float tFar,
-                                              LdsStack<BLOCK> st, CT &cnt) {
+                                              LdsStack<BLOCK, F> st, CT &cnt) {
   float t;
   uint32_t k;
   return mesh_trace<BLOCK, true>(sc, o, d, tNear, tFar, st, t, k, cnt);
