@@ -60,6 +60,12 @@ struct FrameArgs {
   int32_t W, H;
   uint32_t flags;
   int32_t band_rows, rank, nranks, rows_local;
+  // screen rectangle outside which no ray of this frame can store a hit
+  // (cull_rect, mesh primary rays), in 8-pixel tiles of image columns: first
+  // tile | (last tile + 1) << 16. Its image rows travel the same way in
+  // P.reserved (this copy of the parameters is the library's own), so the
+  // batch keeps its size. kCullWhole: no rectangle, every tile is traced
+  uint32_t cull_x;
   const uint32_t *order;  // block -> tile schedule (NULL: blockIdx order)
   uint32_t *cost;         // per-tile cost of this frame (shader cycles, max over waves), or NULL
   // one-frame kernel: bounding box of the pixels a hit was stored to, as
@@ -339,6 +345,8 @@ constexpr uint32_t kFlagFastEye = 1u << 28;
 // frame shared by every slot (the kernels' end-of-dispatch release before the
 // host's stream synchronisation covers their stores, as for rt_render's).
 constexpr uint32_t kFlagNatural = 1u << 27;
+// FrameArgs::cull_x / P.reserved of a frame without a rectangle: tiles [0, 65535)
+constexpr uint32_t kCullWhole = 0xFFFF0000u;
 __device__ __forceinline__ void peer_release(uint32_t flags) {
 #if RT_PEER_RELEASE
   if (flags & kSysStoreFlags) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
@@ -425,6 +433,40 @@ __device__ __forceinline__ bool render_pixels(const S &sc, const PlaneDev &pl, c
   if (DIAG == 0 && !kWaveCoop && !active) return false;
   if (active || kWaveCoop) {  // (the counting variant keeps every lane for its wave reduction)
     LdsStack<B, S::kFields> st{stk + threadIdx.x};
+    if constexpr (kWaveCoop) {
+      const int yo = image_row(active ? yl : 0, fa);
+      // Tile cull (cull_rect): no pixel of this wave lies in the frame's screen
+      // rectangle, so none of its rays can store a hit. The wave does what a
+      // wave of misses does, before any ray arithmetic. Each lane tests its own
+      // pixel (image row: right for bands whose tiles straddle two bands); the
+      // decision is wave-uniform, as mesh_primary_wave needs.
+      const uint32_t cx = fa.cull_x, cy = (uint32_t)fa.P.reserved;
+      const uint32_t px = (uint32_t)xo >> 3, py = (uint32_t)yo >> 3;
+      const bool inside = active && px >= (cx & 0xFFFFu) && px < (cx >> 16) && py >= (cy & 0xFFFFu) && py < (cy >> 16);
+      if (__ballot(inside) == 0) {
+        const bool natural = (fa.flags & (kSysStoreFlags | kFlagNatural)) != 0;
+        const uint32_t idx = (uint32_t)(natural ? yo : yl) * (uint32_t)fa.W + (uint32_t)xo;
+        if (defer) {
+          defer[0] = 0u;
+          defer[kPairWords] = __float_as_uint(kInf);
+        } else if (RT_DIAG_HOST_NOSTORE != 0 && (fa.flags & kFlagHostFrame)) {
+          // diagnostic build only (see below)
+        } else if (active && (fa.flags & RT_FLAG_CLEAR) && !(fa.flags & RT_FLAG_HITS_ONLY)) {
+          const bool sys = (fa.flags & (kSysStoreFlags | kFlagHostFrame)) != 0;
+          fb_store(fa.color + idx, 0u, sys);
+          fb_store(fa.t + idx, kInf, sys);
+        }
+        return false;
+      }
+      // The pixel is made opaque here, so that what follows computes its
+      // values from it afresh (the image row above all) and shares none with
+      // the test. With them shared the register allocation came out worse:
+      // at the 96-VGPR floor 12-16 B more scratch per lane in every 4- and
+      // 7-slot kernel, and a wave per SIMD less in the 15-slot batch kernel
+      // (profiles/r08/README.md). Like this the kernels' registers, scratch
+      // and occupancy are what they were without the test.
+      asm volatile("" : "+v"(xo), "+v"(yl));
+    }
     const int yo = image_row(active ? yl : 0, fa);
     const int y = fa.H - yo - 1;  // loop row y is stored to image row H-y-1 (raytracing.cpp:82)
     const f3 o{fa.P.camera_pos[0], fa.P.camera_pos[1], fa.P.camera_pos[2]};
@@ -1252,6 +1294,9 @@ struct rt_scene {
   rtl::GTri *d_tris = nullptr;
   uint32_t root = rtl::kInvalidChild;
   float root_box[6] = {0, 0, 0, 0, 0, 0};
+  // the root node's eight child boxes (xMin xMax yMin yMax zMin zMax each; an
+  // empty slot is all +inf): the bounds a camera must not sit on (cull_rect)
+  float root_child[48] = {};
   int64_t host_nodes = 0, host_inner = 0;
   uint32_t n_inner = 0;  // inner nodes on the device (MeshDev::n_inner)
   float dmax2 = 0.0f;    // MeshDev::dmax2 (mesh_dmax2; 0: every ray takes the division)
@@ -1923,9 +1968,188 @@ bool fast_eye_ok(const float *m, int32_t W, int32_t H) {
   return lmin >= 0x1p-20;
 }
 
-int fill_frame(FrameArgs &fa, const rt_render_params *p, uint32_t *c, float *t, int32_t W, int32_t H,
-               uint32_t flags, const rt_tile *tile) {
+// Tile cull of the mesh primary path: the screen rectangle of a frame outside
+// which no pixel can store a hit, so that the kernels skip the ray set-up and
+// the traversal of the wave tiles outside it (render_pixels).
+// RTAMD_TILE_CULL=0 renders every tile (A/B switch); rtx_set_tile_cull
+// switches inside one process.
+bool tile_cull_env() {
+  static const bool on = !ab_off("RTAMD_TILE_CULL");
+  return on;
+}
+std::atomic<bool> g_tile_cull{tile_cull_env()};
+
+// cull_rect: the rectangle of pixels whose eye rays can reach `box` (xMin yMin
+// zMin xMax yMax zMax), as out = {first tile column, last + 1, first tile row,
+// last + 1} in 8-pixel tiles of IMAGE columns and rows, padded by 2 pixels and
+// rounded outwards; first == last + 1 == 0 is the empty rectangle (the camera
+// looks away). Returns false for "whole frame". All arithmetic in double.
+// `guard`: n further boxes (xMin xMax yMin yMax zMin zMax each) whose bounds
+// the camera must not sit on (the root node's child boxes; see step 3).
+//
+// The eye ray of pixel (x, loop row y) is d = V3 normalize(q.xyz / q.w) with
+// q = proj_inv (nx, ny, 0, 1), nx = 2 (x + .5) / W - 1, ny likewise: z = 0
+// drops proj_inv's third column, and the divisions by q.w and |p| only scale,
+// so d = s M (nx, ny, 1) with the 3x3 M = V3 [P0 P1 P3] and sign(s) = sign(q.w).
+// A point X = o + t d, t > 0, therefore has c = M^-1 (X - o) = t s (nx, ny, 1):
+// c.z has the sign of q.w and (nx, ny) = (c.x, c.y) / c.z. With all eight
+// corners strictly in front (c.z of that sign) the box is their convex hull
+// and projects into the bounding rectangle of their projections. Loop row y is
+// stored to image row H - 1 - y.
+//
+// Lemma: a pixel outside the rectangle stores no hit on the uncut path, for
+// every ray the kernels generate.
+//  1. A hit lies in the root box. A stored hit needs the root stage
+//     (mesh_root) to enter a child, and every child box lies in the box given
+//     here, MeshDev::rbox, their exact union. A scene whose root is a leaf has
+//     no root stage (its triangles are tested unconditionally and keep
+//     negative t): whole frame.
+//  2. Finite 1/d. Float subtraction and multiplication are correctly rounded,
+//     and b - o is the rounded exact difference of two floats, so each slab
+//     distance carries a relative error of a few 2^-24 and a comparison of
+//     tMin against tMax goes wrong only when the exact values are that close.
+//     Outside the rectangle the ray's line passes the box's projection at 2
+//     pixels or more, i.e. (tMin - tMax) / tMax exceeds 2 pixels' angle; frames
+//     whose pixel subtends less than 2^-17 of the view vector (or with more
+//     than 32768 columns or rows) are "whole frame", which leaves more than an
+//     order of magnitude to the 2^-22 of the error. The float direction itself is within ~2^-21
+//     of the exact one: a hundredth of such a pixel.
+//  3. A zero direction component k: 1/d_k = +-inf, root_box_miss declines and
+//     slab_ispc runs on the root's children. With o_k strictly inside a child's
+//     range on k, (t1, t2) = (-+inf, +-inf): isp_min / isp_max give (-inf,
+//     +inf), the axis drops out as it should. Strictly outside, both are the
+//     same infinity: as tMin's operand +inf survives every isp_max (tMin = +inf
+//     > tMax <= tFar), as tMax's operand -inf survives every isp_min (tMax < 0)
+//     -- a miss, as it should be -- PROVIDED no other operand is NaN, because
+//     isp_max(a, NaN) = NaN and isp_max(NaN, tNear) = tNear turn a NaN tMin
+//     into tNear and a NaN tMax into tFar: the child would be entered whatever
+//     the other axes say. A NaN needs (b - o_k) * inf with b == o_k (an empty
+//     slot's +inf bounds give infinities, never NaN). So a camera with a
+//     coordinate equal to a bound, on that axis, of the box or of a guard box
+//     is "whole frame"; for every other camera the root stage is exact interval
+//     logic on the nonzero axes, and step 2 applies to those.
+//  4. The negative-t leaf quirk (leaf hits are kept without a range test).
+//     Entering a root child needs tMax >= tNear > 0 on the ray's line inside
+//     the box; the camera is outside the box (else "whole frame") and the box
+//     is convex, so the line's whole stretch inside it has t > 0: every
+//     triangle of the scene the line can meet lies ahead of the camera.
+bool cull_rect(const rt_render_params *p, int32_t W, int32_t H, const float box[6], const float *guard,
+               int n_guard, int32_t out[4]) {
+  if (W <= 0 || H <= 0 || W > 32768 || H > 32768) return false;  // (16-bit tile indices; step 2)
+  const float *pi = p->proj_inv, *vi = p->view_inv;
+  double o[3], M[3][3];
+  for (int k = 0; k < 3; ++k) {
+    o[k] = (double)p->camera_pos[k];
+    if (!std::isfinite(o[k]) || !std::isfinite((double)box[k]) || !std::isfinite((double)box[3 + k])) return false;
+    if (!(box[k] <= box[3 + k])) return false;
+  }
+  // the camera inside or on the box, or on a bound of the box or of a guard box
+  bool outside = false;
+  for (int k = 0; k < 3; ++k) {
+    if (o[k] < (double)box[k] || o[k] > (double)box[3 + k]) outside = true;
+    if (o[k] == (double)box[k] || o[k] == (double)box[3 + k]) return false;
+    for (int g = 0; g < n_guard; ++g)
+      if (o[k] == (double)guard[6 * g + 2 * k] || o[k] == (double)guard[6 * g + 2 * k + 1]) return false;
+  }
+  if (!outside) return false;
+  // q.w keeps one sign over the screen (else the rays flip direction across it)
+  const double wc = (double)pi[15], wr = std::fabs((double)pi[3]) + std::fabs((double)pi[7]);
+  if (!std::isfinite(wc) || !std::isfinite(wr) || !(std::fabs(wc) > wr * (1.0 + 0x1p-20))) return false;
+  const double sgn = wc > 0 ? 1.0 : -1.0;
+  const int cols[3] = {0, 1, 3};
+  double scale = 0.0;
+  for (int r = 0; r < 3; ++r)
+    for (int c = 0; c < 3; ++c) {
+      double a = 0.0;
+      for (int j = 0; j < 3; ++j) a += (double)vi[j * 4 + r] * (double)pi[cols[c] * 4 + j];  // V(r,j) P(j,col)
+      if (!std::isfinite(a)) return false;
+      M[r][c] = a;
+      scale = std::max(scale, std::fabs(a));
+    }
+  // inverse by cofactors; near-singular: whole frame
+  double C[3][3];
+  for (int r = 0; r < 3; ++r)
+    for (int c = 0; c < 3; ++c) {
+      const int r1 = (r + 1) % 3, r2 = (r + 2) % 3, c1 = (c + 1) % 3, c2 = (c + 2) % 3;
+      C[r][c] = M[r1][c1] * M[r2][c2] - M[r1][c2] * M[r2][c1];
+    }
+  const double det = M[0][0] * C[0][0] + M[0][1] * C[0][1] + M[0][2] * C[0][2];
+  if (!std::isfinite(det) || !(std::fabs(det) > 1e-9 * scale * scale * scale)) return false;
+  // a pixel's share of the view vector (step 2)
+  const double l0 = std::sqrt(M[0][0] * M[0][0] + M[1][0] * M[1][0] + M[2][0] * M[2][0]) * 2.0 / W;
+  const double l1 = std::sqrt(M[0][1] * M[0][1] + M[1][1] * M[1][1] + M[2][1] * M[2][1]) * 2.0 / H;
+  const double l2 = std::sqrt(M[0][2] * M[0][2] + M[1][2] * M[1][2] + M[2][2] * M[2][2]) +
+                    std::sqrt(M[0][0] * M[0][0] + M[1][0] * M[1][0] + M[2][0] * M[2][0]) +
+                    std::sqrt(M[0][1] * M[0][1] + M[1][1] * M[1][1] + M[2][1] * M[2][1]);
+  if (!(l0 >= 0x1p-17 * l2) || !(l1 >= 0x1p-17 * l2)) return false;
+  double lo[2] = {std::numeric_limits<double>::infinity(), std::numeric_limits<double>::infinity()};
+  double hi[2] = {-lo[0], -lo[1]};
+  int behind = 0;
+  for (int i = 0; i < 8; ++i) {
+    double v[3], c[3];
+    for (int k = 0; k < 3; ++k) v[k] = (double)box[((i >> k) & 1) ? 3 + k : k] - o[k];
+    for (int r = 0; r < 3; ++r) c[r] = (C[0][r] * v[0] + C[1][r] * v[1] + C[2][r] * v[2]) / det;  // M^-1 = C^T / det
+    // strictly in front: c.z of q.w's sign, and not so small that nx, ny
+    // leave double's comfort. Strictly behind (all eight: the camera looks
+    // away, every t on a line through the box is negative): counted
+    const double z = sgn * c[2], zb = 1e-9 * (std::fabs(c[0]) + std::fabs(c[1]));
+    if (!std::isfinite(z) || !std::isfinite(zb)) return false;
+    if (z < -zb && z < 0.0) {
+      ++behind;
+      continue;
+    }
+    if (behind != 0 || !(z > zb) || !(z > 0.0)) return false;
+    for (int a = 0; a < 2; ++a) {
+      const double n = c[a] / c[2];
+      if (!std::isfinite(n)) return false;
+      lo[a] = std::min(lo[a], n);
+      hi[a] = std::max(hi[a], n);
+    }
+  }
+  if (behind == 8) {
+    out[0] = out[1] = out[2] = out[3] = 0;
+    return true;
+  }
+  if (behind != 0) return false;
+  // NDC -> pixel centres (n = 2 (x + .5) / W - 1), padded by 2 pixels; clamped
+  // in double before the conversion
+  const double dim[2] = {(double)W, (double)H};
+  int64_t p0[2], p1[2];  // first and last pixel (column; LOOP row)
+  for (int a = 0; a < 2; ++a) {
+    const double f0 = std::floor((lo[a] + 1.0) * dim[a] * 0.5 - 0.5) - 2.0;
+    const double f1 = std::ceil((hi[a] + 1.0) * dim[a] * 0.5 - 0.5) + 2.0;
+    p0[a] = (int64_t)std::min(std::max(f0, 0.0), dim[a]);
+    p1[a] = (int64_t)std::min(std::max(f1, -1.0), dim[a] - 1.0);
+  }
+  // loop row y -> image row H - 1 - y
+  const int64_t r0 = (int64_t)H - 1 - p1[1], r1 = (int64_t)H - 1 - p0[1];
+  if (p0[0] > p1[0] || r0 > r1) {
+    out[0] = out[1] = out[2] = out[3] = 0;
+    return true;
+  }
+  out[0] = (int32_t)(p0[0] >> 3);
+  out[1] = (int32_t)(p1[0] >> 3) + 1;
+  out[2] = (int32_t)(r0 >> 3);
+  out[3] = (int32_t)(r1 >> 3) + 1;
+  return true;
+}
+
+int fill_frame(FrameArgs &fa, const rt_scene *s, const rt_render_params *p, uint32_t *c, float *t, int32_t W,
+               int32_t H, uint32_t flags, const rt_tile *tile) {
   fa.P = *p;
+  // the rectangle: mesh primary rays only (no plane, Normal shading); the
+  // shading kernels, the counting and stamping variants and the grids and
+  // octrees never read it
+  fa.cull_x = kCullWhole;
+  fa.P.reserved = (int32_t)kCullWhole;
+  if (g_tile_cull.load(std::memory_order_relaxed) && s && s->kind == RT_SCENE_MESH && !s->plane.on &&
+      p->shading_mode == RT_SHADING_NORMAL && s->root != rtl::kInvalidChild && !(s->root & rtl::kLeafBit)) {
+    int32_t r[4];
+    if (cull_rect(p, W, H, s->root_box, s->root_child, 8, r)) {
+      fa.cull_x = (uint32_t)r[0] | ((uint32_t)r[1] << 16);
+      fa.P.reserved = (int32_t)((uint32_t)r[2] | ((uint32_t)r[3] << 16));
+    }
+  }
   fa.color = c;
   fa.t = t;
   fa.W = W;
@@ -2124,6 +2348,8 @@ int rt_scene_create_mesh(const float *vpos4, int64_t nverts, const uint32_t *idx
   s->maxd = maxd;
   s->root = b.root_word;
   std::memcpy(s->root_box, b.root_box, sizeof(s->root_box));
+  if (!(b.root_word & rtl::kLeafBit) && b.root_word < b.nodes.size())
+    std::memcpy(s->root_child, b.nodes[b.root_word].box, sizeof(s->root_child));
   s->host_nodes = b.host_nodes;
   s->host_inner = b.host_inner;
   s->bvh_depth = b.max_depth;
@@ -2223,6 +2449,7 @@ int rt_scene_replicate(const rt_scene *src, int device, rt_scene **out) {
   s->maxd = src->maxd;
   s->root = src->root;
   std::memcpy(s->root_box, src->root_box, sizeof s->root_box);
+  std::memcpy(s->root_child, src->root_child, sizeof s->root_child);
   s->host_nodes = src->host_nodes;
   s->host_inner = src->host_inner;
   s->n_inner = src->n_inner;
@@ -2354,7 +2581,7 @@ int rt_render_device(rt_scene *s, const rt_render_params *p, uint32_t *d_color, 
   if (rc) return rc;
   if (!d_color || !d_t) return set_err(RT_E_INVALID, "NULL framebuffer");
   FrameArgs fa;
-  if ((rc = fill_frame(fa, p, d_color, d_t, W, H, flags, tile))) return rc;
+  if ((rc = fill_frame(fa, s, p, d_color, d_t, W, H, flags, tile))) return rc;
   if (fa.rows_local <= 0) return RT_OK;
   return launch_render(s, fa, (hipStream_t)stream);
 }
@@ -2371,7 +2598,7 @@ int rt_render_device_frames(rt_scene *s, const rt_render_params *params, int32_t
       int rc = check_params(params + f0 + i, W, H);
       if (rc) return rc;
       if (!d_color[f0 + i] || !d_t[f0 + i]) return set_err(RT_E_INVALID, "NULL framebuffer");
-      if ((rc = fill_frame(fb.f[i], params + f0 + i, d_color[f0 + i], d_t[f0 + i], W, H, flags, tile)))
+      if ((rc = fill_frame(fb.f[i], s, params + f0 + i, d_color[f0 + i], d_t[f0 + i], W, H, flags, tile)))
         return rc;
     }
     if (fb.f[0].rows_local <= 0) return RT_OK;
@@ -2583,7 +2810,7 @@ int rt_render(rt_scene *s, const rt_render_params *p, uint32_t *color, float *t,
   if (flags & RT_FLAG_TILE_NATURAL) return set_err(RT_E_INVALID, "rt_render renders whole frames (no tile)");
   // every argument is checked before the first copy is queued
   FrameArgs fa;
-  if ((rc = fill_frame(fa, p, nullptr, nullptr, W, H, flags & ~RT_FLAG_HITS_ONLY, nullptr))) return rc;
+  if ((rc = fill_frame(fa, s, p, nullptr, nullptr, W, H, flags & ~RT_FLAG_HITS_ONLY, nullptr))) return rc;
   const size_t px = (size_t)W * H;
   if (flags == (RT_FLAG_CLEAR | RT_FLAG_HITS_ONLY) && dropin_zero_copy()) {
     if ((rc = ensure_events(s)) || (rc = ensure_copy_streams(s))) return rc;
@@ -2769,7 +2996,7 @@ int rt_count_work(rt_scene *s, const rt_render_params *params, int32_t frames, i
   for (int32_t f = 0; f < frames && e == hipSuccess && rc == RT_OK; ++f) {
     FrameArgs fa;
     if (!(rc = check_params(params + f, W, H)) &&
-        !(rc = fill_frame(fa, params + f, s->d_color, s->d_t, W, H, flags, tile)))
+        !(rc = fill_frame(fa, s, params + f, s->d_color, s->d_t, W, H, flags, tile)))
       rc = launch_render(s, fa, 0, d, 1);
   }
   unsigned long long h[C_NUM] = {};
@@ -2796,7 +3023,7 @@ int rtx_wave_stamps(rt_scene *s, const rt_render_params *params, int32_t W, int3
   unsigned long long *d = nullptr;
   HIP_TRY(hipMalloc(&d, nw * 4 * sizeof(unsigned long long)));
   FrameArgs fa;
-  if (!(rc = fill_frame(fa, params, s->d_color, s->d_t, W, H, flags, nullptr)))
+  if (!(rc = fill_frame(fa, s, params, s->d_color, s->d_t, W, H, flags, nullptr)))
     rc = launch_render(s, fa, 0, d, 2);
   hipError_t e = rc ? hipSuccess : hipMemcpy(out, d, nw * 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost);
   HIP_NOTE(hipFree(d));
@@ -2817,6 +3044,23 @@ int rtx_set_band_queue_px(int64_t px) {
 // projection takes eye_ray_fast. Not part of include/rtamd.h.
 int rtx_fast_eye_ok(const float *proj_inv, int32_t W, int32_t H) {
   return proj_inv && fast_eye_ok(proj_inv, W, H) ? 1 : 0;
+}
+
+// cull_rect for tests (host only): the tile rectangle of a W x H frame for a
+// scene box (xMin yMin zMin xMax yMax zMax) into out[4] = first tile column,
+// last + 1, first tile row, last + 1 (image rows, 8-pixel tiles; all zero:
+// empty). Returns 1 with a rectangle, 0 for "whole frame" (out untouched).
+// Not part of include/rtamd.h.
+int rtx_cull_rect(const rt_render_params *p, int32_t W, int32_t H, const float box[6], int32_t out[4]) {
+  return p && box && out && cull_rect(p, W, H, box, nullptr, 0, out) ? 1 : 0;
+}
+
+// Tile cull of the mesh primary path on (1) / off (0) for the frames filled
+// from now on; < 0 restores the RTAMD_TILE_CULL setting. Not part of
+// include/rtamd.h.
+int rtx_set_tile_cull(int on) {
+  g_tile_cull.store(on < 0 ? tile_cull_env() : (on != 0));
+  return RT_OK;
 }
 
 // Heavy-first band order on (1) / off (0) from now on; < 0 restores the
@@ -2890,7 +3134,7 @@ int rt_bench_frames(rt_scene *s, const rt_render_params *params, int32_t frames,
   for (int32_t f = 0; f < frames; ++f) {
     FrameArgs fa;
     if ((rc = check_params(params + f, W, H)) ||
-        (rc = fill_frame(fa, params + f, s->d_color, s->d_t, W, H, flags, nullptr)) ||
+        (rc = fill_frame(fa, s, params + f, s->d_color, s->d_t, W, H, flags, nullptr)) ||
         (rc = launch_render(s, fa, 0)))
       return rc;
   }
@@ -2920,7 +3164,7 @@ int render_band_host(rt_scene *s, const rt_render_params *p, uint32_t *dc, float
   if (!s) return set_err(RT_E_INVALID, "scene is NULL");
   if (int rc = check_params(p, W, H)) return rc;
   FrameArgs fa;
-  if (int rc = fill_frame(fa, p, dc, dt, W, H, RT_FLAG_CLEAR | RT_FLAG_HITS_ONLY, tile)) return rc;
+  if (int rc = fill_frame(fa, s, p, dc, dt, W, H, RT_FLAG_CLEAR | RT_FLAG_HITS_ONLY, tile)) return rc;
   if (fa.rows_local <= 0) return RT_OK;
   fa.flags |= kFlagHostFrame | kFlagNatural | (d_span ? kFlagRowSpan : 0u);
   fa.hit_box = d_span;

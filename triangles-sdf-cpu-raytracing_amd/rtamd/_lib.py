@@ -138,6 +138,13 @@ _SIGS = {
 
 EXPORTED = tuple(_SIGS)
 
+# test hooks outside include/rtamd.h (a library injected through RTAMD_LIB may
+# predate them): the tile cull's switch and its host-only screen rectangle
+_XSIGS = {
+    "rtx_set_tile_cull": (C.c_int, [C.c_int]),
+    "rtx_cull_rect": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+}
+
 
 def source_build_id() -> str:
     """rt_build_id() of a library built from this tree (the Makefile's ID_SRCS
@@ -193,6 +200,11 @@ def lib():
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args
+        for name, (res, args) in _XSIGS.items():
+            fn = getattr(L, name, None)
+            if fn is not None:
+                fn.restype = res
+                fn.argtypes = args
         _lib = L
     return _lib
 
