@@ -11,7 +11,13 @@ stamps. The all-culled launch gives the wave time of a culled item; times the
 orbit launch's items outside the rectangle, over that launch's wave time, it
 is the share those items take.
   bash tools/build_variant.sh stamps -DRT_PERSIST_STAMPS
-  RTAMD_LIB=.../lib/var_stamps.so python tools/cull_stamps.py [group] [--host-only]
+  RTAMD_LIB=.../lib/var_stamps.so python tools/cull_stamps.py [group] [--host-only] [--flags clear|hits_only]
+
+--flags hits_only renders RT_FLAG_CLEAR | RT_FLAG_HITS_ONLY into frames cleared
+beforehand, so a culled tile and a missed pixel store nothing: the all-culled
+launch is then the pure claim cost of its items, and the difference to
+--flags clear (the default) is what the background's stores cost
+(profiles/r09/README.md).
 """
 import ctypes as C
 import os
@@ -45,7 +51,15 @@ def tile_shares(L, mesh):
 
 
 def main():
-    args = [a for a in sys.argv[1:] if not a.startswith("--")]
+    argv = sys.argv[1:]
+    mode = "clear"
+    if "--flags" in argv:
+        i = argv.index("--flags")
+        mode = argv[i + 1]
+        del argv[i:i + 2]
+        if mode not in ("clear", "hits_only"):
+            sys.exit("--flags clear|hits_only")
+    args = [a for a in argv if not a.startswith("--")]
     group = int(args[0]) if args else 10
     L = rtamd.lib()
     mesh = rtamd.load_mesh_from_obj(data.path("stanford-bunny.obj"), scale=True)
@@ -69,12 +83,19 @@ def main():
     fb = [(torch.empty((H, W), dtype=torch.int32, device=dev), torch.empty((H, W), dtype=torch.float32, device=dev))
           for _ in range(group)]
     st = torch.cuda.current_stream().cuda_stream
+    flags = rtamd.RT_FLAG_CLEAR | (rtamd._lib.RT_FLAG_HITS_ONLY if mode == "hits_only" else 0)
+    print(f"flags: {mode}")
 
     def launch(prm, stamps):
+        if mode == "hits_only":  # the cleared frame the flag asks for
+            for c, t in fb:
+                c.zero_()
+                t.fill_(float("inf"))
+            torch.cuda.synchronize()
         rtamd._lib.check(L.rtx_set_persist_stamps(C.c_void_p(stamps.data_ptr()) if stamps is not None else None,
                                                    CAP if stamps is not None else 0))
         sc.render_device_frames(prm, [c.data_ptr() for c, _ in fb], [t.data_ptr() for _, t in fb], W, H,
-                                rtamd.RT_FLAG_CLEAR, stream=st)
+                                flags, stream=st)
         torch.cuda.synchronize()
 
     for prm in (near, away, near, away):  # warm
@@ -91,7 +112,7 @@ def main():
             span = (s[:, 1].max() - s[:, 0].min()) / 100.0
             res[name] = (wave_us, items, span, len(s))
             print(f"rep {rep} {name}: {len(s)} waves, {items} items, span {span:.1f} us, wave time {wave_us:.0f} us"
-                  f" ({wave_us / items * 1e3:.1f} ns per item)")
+                  f" ({wave_us / items * 1e3:.1f} ns per item; {items / span:.1f} claims per us)")
         (wo, io, so, _), (wa, ia, sa, _) = res["orbit"], res["away"]
         out_items = io * (1.0 - sh[:group].mean())
         print(f"rep {rep}: items outside the rectangle ~{out_items:.0f} of {io}: {out_items * wa / ia:.0f} us of the orbit"

@@ -32,6 +32,7 @@
 #include "rt_host.h"
 #include "rt_layout.h"
 #include "rt_math.h"
+#include "rt_queue.h"
 #include "rt_scenes.h"
 
 using namespace rtd;
@@ -795,23 +796,28 @@ void render_batch_kernel(S sc, PlaneDev pl, FrameBatch fb) {
 // is drained, so a wave whose tile finishes early takes the next one at once
 // instead of waiting for the in-order workgroup dispatcher (which stalls
 // behind a full SE while other SEs have free slots). The queue is sharded per
-// XCD: item i belongs to head i % 8 (HW_REG_XCC_ID picks a wave's own head),
-// a wave whose head is drained moves on to the other seven, so the batch
-// completes whatever XCDs the grid lands on. The next item is claimed before
-// the current one is traced (its atomic's latency hides under the traversal).
-// The last wave out resets the heads for the next launch on the stream.
+// XCD, with `nheads` / 8 sub-heads each (rt_queue.h holds the item order): item
+// i belongs to head i % nheads; a wave starts on a head of its own XCD
+// (HW_REG_XCC_ID) and, once that is drained, moves on to the others, so the
+// batch completes whatever XCDs the grid lands on. The next item is claimed
+// before the current one is traced (its atomic's latency hides under the
+// traversal). The last wave out resets the heads for the next launch on the
+// stream.
 struct PersistQ {
-  uint32_t *heads;   // 8 heads kHeadStride words apart; heads[8 * kHeadStride] = waves done
+  uint32_t *heads;   // nheads heads `stride` words apart; heads[nheads * stride] = waves done
   uint32_t items;    // frames * per_frame
   uint32_t tiles_x, per_frame;  // items (groups of gx x gy wave tiles) per row / per frame
   uint32_t waves;    // waves in the grid
   uint32_t gx, gy;   // wave tiles (8x8 pixels) per item: 1x1, 2x1 or 2x2
   uint32_t stride;   // words between heads
-  // item order of a head (render_persist_kernel): cpf == 0 interleaved (item
-  // i on head i % 8); cpf > 0 banded: head h takes tile rows [h cpf, (h+1) cpf)
-  // of the row-major items of every frame, frame after frame (nper = frames x
-  // cpf slots, slots past per_frame are empty), so an XCD's L2 holds the part
-  // of the scene its band of the image sees; a drained head steals as before
+  uint32_t nheads;   // 8, 16, 32 or 64 (rtq::heads_ok)
+  // item order of a head: cpf == 0 interleaved (rt_queue.h: item i on head
+  // i % nheads); cpf > 0 banded: head h takes tile rows [h cpf, (h+1) cpf) of
+  // the row-major items of every frame, frame after frame (nper = frames x
+  // cpf slots, slots past per_frame are empty). The banded order was measured
+  // and rejected and no launch sets it; the branch
+  // stays because the 4- and 7-slot mesh kernels come out with 28 B more
+  // scratch per lane without it (profiles/r09/README.md)
   uint32_t cpf, nper;
   // diagnostic builds (-DRT_PERSIST_STAMPS, tools/build_variant.sh; see
   // rtx_set_persist_stamps): per wave w = blockIdx.x * (kPBlock / 64) + wave, 8 x u64 =
@@ -829,6 +835,40 @@ __device__ __forceinline__ uint32_t q_claim(uint32_t *head) {
   uint32_t k = 0;
   if ((threadIdx.x & 63) == 0) k = __hip_atomic_fetch_add(head, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   return __builtin_amdgcn_readfirstlane(k);
+}
+// RT_QUEUE_HEADS: 0 = PersistQ::nheads (a run-time setting), 8..64 = compiled in
+#ifndef RT_QUEUE_HEADS
+#define RT_QUEUE_HEADS 0
+#endif
+__device__ __forceinline__ uint32_t q_nheads(const PersistQ &q) { return RT_QUEUE_HEADS ? (uint32_t)RT_QUEUE_HEADS : q.nheads; }
+// a wave's first head: its XCD's, the sub-head dealt over the XCD's waves
+// (workgroups go to the XCDs round-robin, so blockIdx.x >> 3 counts an XCD's
+// workgroups; nothing depends on that: any wave may start on any head)
+__device__ __forceinline__ uint32_t q_home(uint32_t xcc, uint32_t nheads) {
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  return rtq::home(xcc, (blockIdx.x >> 3) + wave, nheads);
+}
+// head `own` is drained: every head read at once (one lane each, one round
+// trip) -> the first head after `own` that still has items, rtq::kNone if none
+__device__ __forceinline__ uint32_t q_scan(const PersistQ &q, uint32_t nh, uint32_t own, int lane) {
+  uint32_t v = 0xFFFFFFFFu;
+  const bool mine = (uint32_t)lane < nh;
+  if (mine) v = __hip_atomic_load(q.heads + (uint32_t)lane * q.stride, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  const uint32_t cap = q.cpf ? q.nper : rtq::cap(q.items, nh, (uint32_t)lane);
+  const uint64_t left = __ballot(mine && v < cap);
+  return left ? rtq::next(left, own, nh) : rtq::kNone;
+}
+// a wave is done: the last one out resets the heads for the stream's next launch
+__device__ __forceinline__ void q_leave(const PersistQ &q, uint32_t nh, int lane) {
+  uint32_t *done = q.heads + nh * q.stride;
+  uint32_t last = 0;
+  if (lane == 0) last = __hip_atomic_fetch_add(done, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == q.waves - 1;
+  if (__builtin_amdgcn_readfirstlane(last)) {
+    // every wave has left its claim loop: no claim is in flight any more
+    if ((uint32_t)lane < nh)
+      __hip_atomic_store(q.heads + (uint32_t)lane * q.stride, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (lane == 0) __hip_atomic_store(done, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
 }
 
 template <class S, int SLOTS, bool GENERAL>
@@ -856,7 +896,7 @@ void render_persist_kernel(S sc_arg, PlaneDev pl, FrameBatch fb, PersistQ q) {
   unsigned long long t_item = t_start, t_last = t_start, d_max = 0;
   uint32_t n_items = 0, last_item = 0, max_item = 0;
 #endif
-  uint32_t h = xcc;
+  uint32_t h = q_home(xcc, q_nheads(q));
   uint32_t k = q_claim(q.heads + h * q.stride);
   NoCnt cnt{};
   for (;;) {
@@ -864,7 +904,8 @@ void render_persist_kernel(S sc_arg, PlaneDev pl, FrameBatch fb, PersistQ q) {
     uint32_t item, f, r;
     bool drained, empty = false;
     if (q.cpf == 0) {
-      item = k * 8 + h;
+      // rtq::item(q.items, nheads, h, k), spelled out beside the banded form
+      item = k * q_nheads(q) + h;
       drained = item >= q.items;
       f = item / q.per_frame;
       r = item - f * q.per_frame;
@@ -876,17 +917,11 @@ void render_persist_kernel(S sc_arg, PlaneDev pl, FrameBatch fb, PersistQ q) {
       item = f * q.per_frame + r;
     }
     if (drained) {
-      // head h drained: read all eight heads at once (lanes 0-7, one round
-      // trip) and claim from a head that still has items, the first one after
-      // this XCD's own; none left: done. A claim that loses the race to the
-      // last item just comes back here.
-      uint32_t v = 0xFFFFFFFFu;
-      if (lane < 8) v = __hip_atomic_load(q.heads + lane * q.stride, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      const uint32_t cap = q.cpf ? q.nper : (q.items + 7u - (uint32_t)lane) / 8u;
-      const uint64_t m = __ballot(lane < 8 && v < cap) & 0xFFull;
-      if (m == 0) break;
-      const uint32_t rot = (uint32_t)(((m >> (xcc + 1)) | (m << (7 - xcc))) & 0xFFull);  // bit i: head xcc+1+i
-      h = (xcc + 1 + (uint32_t)__builtin_ctz(rot)) & 7u;
+      // head h drained: claim from the first head after it that still has
+      // items; none left: done. A claim that loses the race to the last item
+      // just comes back here.
+      h = q_scan(q, q_nheads(q), h, lane);
+      if (h == rtq::kNone) break;
       k = q_claim(q.heads + h * q.stride);
       continue;
     }
@@ -937,15 +972,7 @@ void render_persist_kernel(S sc_arg, PlaneDev pl, FrameBatch fb, PersistQ q) {
   }
 #endif
   peer_release(fb.f[0].flags);
-  if (lane == 0) {
-    uint32_t *done = q.heads + 8 * q.stride;
-    if (__hip_atomic_fetch_add(done, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == q.waves - 1) {
-      // every wave has left its claim loop: no claim is in flight any more
-      for (int i = 0; i < 8; ++i)
-        __hip_atomic_store(q.heads + i * q.stride, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(done, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
+  q_leave(q, q_nheads(q), lane);
 }
 
 // ---------------------------------------------------------------- ray pump --
@@ -974,16 +1001,25 @@ struct PumpFrame {  // the per-frame arguments a lane needs, copied to LDS
 
 // wave-uniform work-item stream over the sharded queue (render_persist_kernel's
 // protocol): the ticket of the next item on head h is claimed one ahead
+// The pump keeps one head per XCD (kPumpHeads): its refill loop has no
+// registers to spare for a run-time head count (profiles/r09/README.md), and a
+// stream's head set is all zero between launches, so each kernel may deal its
+// items over a head count of its own.
+constexpr uint32_t kPumpHeads = rtq::kXcds;
 struct ItemStream {
   uint32_t h, k;
 };
 __device__ __forceinline__ uint32_t take_item(const PersistQ &q, ItemStream &s, uint32_t xcc, int lane) {
   for (;;) {
-    const uint32_t item = s.k * 8 + s.h;
-    if (item < q.items) {
+    const uint32_t item = rtq::item(q.items, kPumpHeads, s.h, s.k);
+    if (item != rtq::kNone) {
       s.k = q_claim(q.heads + s.h * q.stride);
       return item;
     }
+    // head s.h drained: render_persist_kernel's q_scan for the 8 heads, from
+    // this XCD's own, spelled out (rtq::cap and rtq::next with the count folded
+    // in; the shared form costs the octree pump 4-12 B of scratch per lane)
+    static_assert(kPumpHeads == 8 && rtq::cap(45, 8, 3) == (45 + 7 - 3) / 8 && rtq::next(0x21, 5, 8) == 0, "take_item's scan");
     uint32_t v = 0xFFFFFFFFu;
     if (lane < 8) v = __hip_atomic_load(q.heads + lane * q.stride, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     const uint64_t m = __ballot(lane < 8 && v < (q.items + 7u - (uint32_t)lane) / 8u) & 0xFFull;
@@ -1072,7 +1108,8 @@ void render_pump_kernel(P sc, FrameBatch fb, PersistQ q, int32_t nframes, int32_
   const bool clear = (F.flags & RT_FLAG_CLEAR) != 0, hits_only = (F.flags & RT_FLAG_HITS_ONLY) != 0;
   const bool peer = (F.flags & kSysStoreFlags) != 0;
   const uint32_t isz = 64u * q.gx * q.gy;  // pixels per item
-  ItemStream is{xcc, q_claim(q.heads + xcc * q.stride)};
+  ItemStream is{xcc, 0u};
+  is.k = q_claim(q.heads + is.h * q.stride);
   uint32_t cur = take_item(q, is, xcc, lane), off = 0;
   LdsStack<kBlock, P::kFields> st{stk + threadIdx.x};
   typename P::Ray R;
@@ -1166,14 +1203,7 @@ void render_pump_kernel(P sc, FrameBatch fb, PersistQ q, int32_t nframes, int32_
     }
   }
   peer_release(F.flags);
-  if (lane == 0) {
-    uint32_t *done = q.heads + 8 * q.stride;
-    if (__hip_atomic_fetch_add(done, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == q.waves - 1) {
-      for (int i = 0; i < 8; ++i)
-        __hip_atomic_store(q.heads + i * q.stride, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(done, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
+  q_leave(q, kPumpHeads, lane);
 }
 
 template <class S, int SLOTS>
@@ -1634,7 +1664,11 @@ int launch_render(rt_scene *s, const FrameArgs &fa_in, hipStream_t stream,
 // first launch on a new stream neither stalls the other streams nor breaks a
 // graph capture. rt_stream_prepare() does it ahead of time (outside a timed
 // region); rt_stream_release() frees the set, again in stream order.
-constexpr size_t kQueueBytes = (8 * kHeadStrideMax + 16) * sizeof(uint32_t);
+// (the most heads at the default stride, then the waves-done counter; the
+// widest RTAMD_QSTRIDE fits with 8 heads, make_queue checks every other pair)
+constexpr size_t kQueueWords = (size_t)rtq::kMaxHeads * kHeadStride + 16;
+constexpr size_t kQueueBytes = kQueueWords * sizeof(uint32_t);
+static_assert((size_t)rtq::kXcds * kHeadStrideMax + 1 <= kQueueWords, "8 heads at the widest stride must fit");
 std::mutex g_queue_mu;
 std::map<std::pair<int, hipStream_t>, uint32_t *> g_queues;
 
@@ -1761,6 +1795,24 @@ int resident_blocks(K kernel, int &blocks, int &dev_cached, int block = kBlock) 
   return RT_OK;
 }
 
+// Heads of the work queue: 8 (one per XCD) x RT_QUEUE_SUBHEADS sub-heads.
+// RTAMD_QHEADS=8|16|32|64 overrides it (A/B switch); rtx_set_queue_heads
+// switches inside one process. A stream's head set is all zero between
+// launches whatever count the last one ran with, so the count may change from
+// launch to launch.
+#ifndef RT_QUEUE_SUBHEADS
+#define RT_QUEUE_SUBHEADS 2
+#endif
+static_assert(rtq::heads_ok(rtq::kXcds * RT_QUEUE_SUBHEADS), "RT_QUEUE_SUBHEADS: 1, 2, 4 or 8");
+int queue_heads_env() {
+  static const int h = [] {
+    const long long v = ab_int("RTAMD_QHEADS", rtq::kXcds * RT_QUEUE_SUBHEADS, rtq::kXcds, rtq::kMaxHeads);
+    return rtq::heads_ok((uint32_t)v) ? (int)v : (int)(rtq::kXcds * RT_QUEUE_SUBHEADS);
+  }();
+  return h;
+}
+std::atomic<int> g_queue_heads{queue_heads_env()};
+
 // Work queue of one multi-frame launch: items of `group` 8x8 wave tiles
 // (1: 1x1, 2: 2x1, 4: 2x2) of n frames, the stream's head set; *grid = the
 // launch's workgroups (the resident ones, fewer for a small batch).
@@ -1771,18 +1823,15 @@ int make_queue(const FrameBatch &fb, int n, int group, int blocks, hipStream_t s
   q.heads = heads;
   static const uint32_t stride = (uint32_t)ab_int("RTAMD_QSTRIDE", kHeadStride, 1, kHeadStrideMax);
   q.stride = stride;
+  q.nheads = (uint32_t)g_queue_heads.load(std::memory_order_relaxed);
+  if ((size_t)q.stride * q.nheads + 1 > kQueueWords)
+    return set_err(RT_E_INVALID, "work queue: RTAMD_QSTRIDE x the head count does not fit the stream's head set");
   q.gx = group >= 2 ? 2 : 1;
   q.gy = group >= 4 ? 2 : 1;
   q.tiles_x = (uint32_t)((fb.f[0].W + 8 * q.gx - 1) / (8 * q.gx));
   q.per_frame = q.tiles_x * (uint32_t)((fb.f[0].rows_local + 8 * q.gy - 1) / (8 * q.gy));
   q.items = q.per_frame * (uint32_t)n;
-  // RTAMD_QMAP=band: banded item order per head (PersistQ::cpf)
-  static const bool banded = [] {
-    const char *e = ab_env("RTAMD_QMAP");
-    return e && std::strcmp(e, "band") == 0;
-  }();
-  q.cpf = banded ? (q.per_frame + 7) / 8 : 0;
-  q.nper = q.cpf * (uint32_t)n;
+  q.cpf = q.nper = 0;  // interleaved order (PersistQ::cpf)
   const uint32_t wpb = (uint32_t)block / 64;  // waves per workgroup
   grid = std::min<uint32_t>((uint32_t)blocks, (q.items + wpb - 1) / wpb);
   q.waves = grid * wpb;
@@ -3061,6 +3110,28 @@ int rtx_cull_rect(const rt_render_params *p, int32_t W, int32_t H, const float b
 int rtx_set_tile_cull(int on) {
   g_tile_cull.store(on < 0 ? tile_cull_env() : (on != 0));
   return RT_OK;
+}
+
+// Heads of the work queue (8, 16, 32 or 64) for the launches from now on;
+// < 0 restores the RTAMD_QHEADS setting. Not part of include/rtamd.h.
+int rtx_set_queue_heads(int heads) {
+  if (heads >= 0 && !rtq::heads_ok((uint32_t)heads)) return set_err(RT_E_INVALID, "queue heads: 8, 16, 32 or 64");
+  g_queue_heads.store(heads < 0 ? queue_heads_env() : heads);
+  return RT_OK;
+}
+
+// The work queue's item order for tests (host only, rt_queue.h): slot k of
+// `head` -> *item (0xFFFFFFFF past the head's last item), and the number of
+// slots of `head` that hold an item. rtx_queue_cap returns -1 for a head count
+// the queue does not take. Not part of include/rtamd.h.
+int rtx_queue_item(uint32_t items, uint32_t heads, uint32_t head, uint32_t k, uint32_t *item) {
+  if (!item || !rtq::heads_ok(heads) || head >= heads) return set_err(RT_E_INVALID, "bad queue head");
+  *item = rtq::item(items, heads, head, k);
+  return RT_OK;
+}
+int64_t rtx_queue_cap(uint32_t items, uint32_t heads, uint32_t head) {
+  if (!rtq::heads_ok(heads) || head >= heads) return -1;
+  return (int64_t)rtq::cap(items, heads, head);
 }
 
 // Heavy-first band order on (1) / off (0) from now on; < 0 restores the
