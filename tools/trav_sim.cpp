@@ -203,6 +203,11 @@ void replay(const std::vector<std::string> &s, int policy, double cI, double cL,
 //       a visit loads only the 4-byte child word;
 //   V2  V1 + the loads of the frame looked at after a leaf are issued with the
 //       leaf's triangle batch (one wait covers both): not exposed.
+//   V3  the frame's record in LDS holds its second child's entry t and child
+//       word (RT_MESH_T2 = 2): a resume there needs no global load at all; a
+//       prune ends the iteration and the next one pops (no unwinding), a
+//       visit takes the word from the record
+//       (profiles/r10/trav_sim_resume.txt).
 // Per ray: round trips by class. Per wave tile (lockstep, the minority side of
 // a leaf / inner split waits, RT_MESH_MAJ = 1): wave iterations, iterations in
 // which any advancing lane needs the second round trip, exposed round trips
@@ -214,7 +219,8 @@ struct Iter {
 };
 struct RayCounts {
   double inner = 0, leaf = 0, two = 0, pushed = 0, resume_visit = 0, resume_prune = 0, prune_second = 0,
-         visit_second = 0, visit_later = 0, pop_only = 0, prune_stored = 0, visit_stored = 0, hoisted = 0, iters = 0;
+         visit_second = 0, visit_later = 0, pop_only = 0, prune_stored = 0, visit_stored = 0, visit_record = 0, hoisted = 0,
+         iters = 0;
 };
 struct Frame {
   uint32_t node;
@@ -248,7 +254,7 @@ Frame expand(uint32_t ni, V3 o, V3 inv, float tn, float tf) {
   return f;
 }
 
-// one ray through mesh_run's loop; variant 0, 1, 2 as above
+// one ray through mesh_run's loop; variant 0 .. 3 as above
 void run_ray(V3 o, V3 d, V3 inv, float tn, float tf, int variant, std::vector<Iter> &seq, RayCounts &rc) {
   seq.clear();
   if (nodes[0].leaf) return;
@@ -310,7 +316,7 @@ void run_ray(V3 o, V3 d, V3 inv, float tn, float tf, int variant, std::vector<It
         word = child;
         break;
       }
-      const bool covered = variant >= 2 && it.top == 'L' && first;  // issued with the leaf's batch
+      const bool covered = variant == 2 && it.top == 'L' && first;  // issued with the leaf's batch
       first = false;
       if (variant >= 1 && k == 1) {  // the stored entry t
         if (f.best < t) {
@@ -318,12 +324,15 @@ void run_ray(V3 o, V3 d, V3 inv, float tn, float tf, int variant, std::vector<It
           rc.resume_prune += 1;
           rc.prune_second += 1;
           f.next = f.n;
+          if (variant == 3) break;  // the next iteration pops
           continue;  // unwound in this iteration
         }
         rc.visit_stored += 1;
         rc.resume_visit += 1;
         rc.visit_second += 1;
-        if (covered) rc.hoisted += 1; else it.second = true;
+        if (variant == 3) rc.visit_record += 1;  // the word too is in the record: no load
+        else if (covered) rc.hoisted += 1;
+        else it.second = true;
         word = child;
         break;
       }
@@ -386,28 +395,30 @@ TileCost replay_resume(const std::vector<std::vector<Iter>> &s) {
 
 template <class Eye>
 int resume_model(Eye eye, V3 org, int W, int H) {
-  const char *vname[3] = {"V0 every resume reloads", "V1 stored second-child t", "V2 V1 + post-leaf loads hoisted"};
-  RayCounts rc[3];
-  std::vector<TileCost> tiles[3];
+  constexpr int kV = 4;
+  const char *vname[kV] = {"V0 every resume reloads", "V1 stored second-child t", "V2 V1 + post-leaf loads hoisted",
+                           "V3 second child's t + word in LDS"};
+  RayCounts rc[kV];
+  std::vector<TileCost> tiles[kV];
   for (int ty = 0; ty < H / 8; ++ty)
     for (int tx = 0; tx < W / 8; ++tx) {
-      std::vector<std::vector<Iter>> seqs[3];
-      for (int v = 0; v < 3; ++v) seqs[v].resize(64);
+      std::vector<std::vector<Iter>> seqs[kV];
+      for (int v = 0; v < kV; ++v) seqs[v].resize(64);
       bool any = false;
       for (int l = 0; l < 64; ++l) {
         const int x = tx * 8 + (l & 7), yo = ty * 8 + (l >> 3), y = H - yo - 1;
         const V3 d = eye(x, y);
         const V3 inv{1.0f / d.x, 1.0f / d.y, 1.0f / d.z};
-        for (int v = 0; v < 3; ++v) run_ray(org, d, inv, 0.01f, 100.0f, v, seqs[v][l], rc[v]);
+        for (int v = 0; v < kV; ++v) run_ray(org, d, inv, 0.01f, 100.0f, v, seqs[v][l], rc[v]);
         any |= !seqs[0][l].empty();
       }
       if (!any) continue;
-      for (int v = 0; v < 3; ++v) tiles[v].push_back(replay_resume(seqs[v]));
+      for (int v = 0; v < kV; ++v) tiles[v].push_back(replay_resume(seqs[v]));
     }
   std::printf("rays %d, wave tiles with a ray past the root %zu\n\n", W * H, tiles[0].size());
-  std::printf("per-ray totals (one frame)%34s%14s%14s\n", "V0", "V1", "V2");
+  std::printf("per-ray totals (one frame)%34s%14s%14s%14s\n", "V0", "V1", "V2", "V3");
   auto row = [&](const char *n, double RayCounts::*m) {
-    std::printf("  %-44s%14.0f%14.0f%14.0f\n", n, rc[0].*m, rc[1].*m, rc[2].*m);
+    std::printf("  %-44s%14.0f%14.0f%14.0f%14.0f\n", n, rc[0].*m, rc[1].*m, rc[2].*m, rc[3].*m);
   };
   row("inner visits below the root (node fetch)", &RayCounts::inner);
   row("leaf visits (triangle batch fetch)", &RayCounts::leaf);
@@ -420,12 +431,13 @@ int resume_model(Eye eye, V3 org, int W, int H) {
   row("  at the frame's second child", &RayCounts::prune_second);
   row("pop-only iterations", &RayCounts::pop_only);
   row("prunes decided from the stored t (no load)", &RayCounts::prune_stored);
-  row("visits from the stored t (4-byte load)", &RayCounts::visit_stored);
+  row("visits from the stored t", &RayCounts::visit_stored);
+  row("  with the word from the record (no load)", &RayCounts::visit_record);
   row("resume loads issued with a leaf's batch", &RayCounts::hoisted);
   row("lane iterations (with each ray's first)", &RayCounts::iters);
   std::printf("  dependent global round trips per lane chain:\n");
-  for (int v = 0; v < 3; ++v) {
-    const double resume = rc[v].resume_visit + rc[v].resume_prune - rc[v].prune_stored;
+  for (int v = 0; v < kV; ++v) {
+    const double resume = rc[v].resume_visit + rc[v].resume_prune - rc[v].prune_stored - rc[v].visit_record;
     const double exposed = resume - rc[v].hoisted;
     const double all = rc[v].inner + rc[v].leaf + exposed;
     std::printf("    %-34s node %.0f + leaf %.0f + resume %.0f (of %.0f loads) = %.0f (resume share %.1f %%)\n", vname[v],
@@ -441,7 +453,7 @@ int resume_model(Eye eye, V3 org, int W, int H) {
   for (int part = 0; part < 2; ++part) {
     std::printf("  %s\n", part == 0 ? "whole frame" : "slowest 1 % of tiles (by V0 exposed trips)");
     double base = 0;
-    for (int v = 0; v < 3; ++v) {
+    for (int v = 0; v < kV; ++v) {
       TileCost s;
       const size_t n = part == 0 ? order.size() : ntail;
       for (size_t i = 0; i < n; ++i) {

@@ -79,9 +79,11 @@ struct FrameArgs {
 };
 
 // ---------------------------------------------------------- scene adapters --
-// kFields = LDS words per traversal frame (mesh: node, list|count, best t and,
-// for stacks of up to 7 slots, the second child's entry t, mesh_fields;
-// octree: node, list|count; grid: none).
+// kFields = LDS words per traversal frame (mesh: node, list|count|record flag,
+// best t, mesh_fields; octree: node, list|count; grid: none). kRec = words of
+// a stack level's second-child record (mesh_rec: the mesh kernels of up to 7
+// slots; else 0). StackOf: the adapter's per-lane stack; stack_words: its LDS
+// words per lane at SLOTS slots.
 // occupancy floors (min_waves below), overridable for A/B builds
 #ifndef RT_GRID_WAVES
 #define RT_GRID_WAVES 1
@@ -106,9 +108,14 @@ struct FrameArgs {
 #ifndef RT_GENERAL_WAVES
 #define RT_GENERAL_WAVES 4
 #endif
-template <int F>
+template <class S, int B>
+using StackOf = LdsStack<B, S::kFields, S::kRec>;
+template <class S, int SLOTS>
+constexpr int stack_words() { return lds_stack_words<SLOTS, S::kFields, S::kRec>(); }
+template <int F, int R>
 struct MeshSF {
   static constexpr int kFields = F;
+  static constexpr int kRec = R;
   static constexpr bool kCoop = true;  // primary rays: wave-cooperative tail (mesh_primary_wave)
   static constexpr int kMinWaves = RT_MESH_WAVES;
   static constexpr int kQueueGroup = 2;  // wave tiles per work-queue item (render_persist_kernel)
@@ -126,7 +133,7 @@ struct MeshSF {
     float t;
     uint32_t k;
     Hit h = miss_hit();
-    if (mesh_primary_wave<B, kFields>(d, o, dir, tn, tf, active, stk, t, k, coop_rays, prio_iters) && active) {
+    if (mesh_primary_wave<B, kFields, kRec>(d, o, dir, tn, tf, active, stk, t, k, coop_rays, prio_iters) && active) {
       h.hit = true;
       h.t = t;
       h.n = tri_normal(d.tris, k);
@@ -136,21 +143,22 @@ struct MeshSF {
   }
   template <int B, class CT>
   __device__ __forceinline__ Hit intersect(f3 o, f3 dir, float tn, float tf,
-                                           LdsStack<B, kFields> st, CT &cnt) const {
+                                           LdsStack<B, kFields, kRec> st, CT &cnt) const {
     return mesh_intersect<B>(d, o, dir, tn, tf, st, cnt);
   }
   template <int B, class CT>
   __device__ __forceinline__ bool occluded(f3 o, f3 dir, float tn, float tf,
-                                           LdsStack<B, kFields> st, CT &cnt) const {
+                                           LdsStack<B, kFields, kRec> st, CT &cnt) const {
     return mesh_occluded<B>(d, o, dir, tn, tf, st, cnt);
   }
 };
 // the mesh adapter of a kernel with SLOTS stack slots
 template <int SLOTS>
-using MeshS = MeshSF<mesh_fields<SLOTS>()>;
+using MeshS = MeshSF<mesh_fields<SLOTS>(), mesh_rec<SLOTS>()>;
 template <int kMode>
 struct GridS {
   static constexpr int kFields = 1;  // no traversal stack (one unused LDS word per lane)
+  static constexpr int kRec = 0;
   static constexpr bool kCoop = false;
   static constexpr int kMinWaves = RT_GRID_WAVES;
   // block dispatch: a grid tile is too short for the queue's claims to pay
@@ -174,6 +182,7 @@ struct GridS {
 template <bool PACK>
 struct OctS {
   static constexpr int kFields = kOctFields;
+  static constexpr int kRec = 0;
   static constexpr bool kCoop = false;
   static constexpr int kMinWaves = RT_OCT_WAVES;
   static constexpr int kQueueGroup = 2;
@@ -200,7 +209,7 @@ struct SurfHit {
 };
 template <class S, int B, class CT>
 __device__ __forceinline__ SurfHit union_intersect(const S &sc, const PlaneDev &pl, f3 o, f3 d,
-                                                   float tn, float tf, LdsStack<B, S::kFields> st, CT &cnt) {
+                                                   float tn, float tf, StackOf<S, B> st, CT &cnt) {
   cnt.add(C_RAYS, 1);
   SurfHit r{sc.template intersect<B>(o, d, tn, tf, st, cnt), 1.0f, 0.0f};
   if (pl.on) {
@@ -223,7 +232,7 @@ __device__ __forceinline__ SurfHit union_intersect(const S &sc, const PlaneDev &
 // Shadow query: HitInfo::hitten of the union is the OR of both hitten flags.
 template <class S, int B, class CT>
 __device__ __forceinline__ bool union_occluded(const S &sc, const PlaneDev &pl, f3 o, f3 d, float tn,
-                                               float tf, LdsStack<B, S::kFields> st, CT &cnt) {
+                                               float tf, StackOf<S, B> st, CT &cnt) {
   cnt.add(C_RAYS, 1);
   if (sc.template occluded<B>(o, d, tn, tf, st, cnt)) return true;
   if (pl.on) {
@@ -238,7 +247,7 @@ __device__ __forceinline__ bool union_occluded(const S &sc, const PlaneDev &pl, 
 template <class S, int B, class CT>
 __device__ __forceinline__ f4 lambert_color(const S &sc, const PlaneDev &pl,
                                             const rt_render_params &P, f3 o, f3 d,
-                                            const SurfHit &sh, f3 n, LdsStack<B, S::kFields> st, CT &cnt) {
+                                            const SurfHit &sh, f3 n, StackOf<S, B> st, CT &cnt) {
   bool visible = true;
   const f3 point = o + sh.h.t * d;
   const f3 L{P.light_pos[0], P.light_pos[1], P.light_pos[2]};
@@ -257,7 +266,7 @@ __device__ __forceinline__ f4 lambert_color(const S &sc, const PlaneDev &pl,
 template <class S, int B, class CT>
 __device__ __forceinline__ f4 shade_one(const S &sc, const PlaneDev &pl, const rt_render_params &P,
                                         f3 o, f3 d, float tFarEff, bool allow_refl, bool &hit,
-                                        float &t_out, LdsStack<B, S::kFields> st, int64_t *prim, CT &cnt) {
+                                        float &t_out, StackOf<S, B> st, int64_t *prim, CT &cnt) {
   const SurfHit sh = union_intersect<S, B>(sc, pl, o, d, 0.01f, tFarEff, st, cnt);
   if (prim) *prim = sh.h.hit ? sh.h.prim : -1;
   if (!sh.h.hit) {
@@ -433,7 +442,7 @@ __device__ __forceinline__ bool render_pixels(const S &sc, const PlaneDev &pl, c
   constexpr bool kWaveCoop = DIAG == 0 && !GENERAL && S::kCoop;
   if (DIAG == 0 && !kWaveCoop && !active) return false;
   if (active || kWaveCoop) {  // (the counting variant keeps every lane for its wave reduction)
-    LdsStack<B, S::kFields> st{stk + threadIdx.x};
+    StackOf<S, B> st{stk + threadIdx.x};
     if constexpr (kWaveCoop) {
       const int yo = image_row(active ? yl : 0, fa);
       // Tile cull (cull_rect): no pixel of this wave lies in the frame's screen
@@ -705,7 +714,7 @@ template <class S, int SLOTS, bool GENERAL, int DIAG>
 __global__ __launch_bounds__(frame_block<DIAG>()) __attribute__((amdgpu_waves_per_eu(min_waves<S, SLOTS, GENERAL, DIAG>())))
 void render_kernel(S sc_arg, PlaneDev pl, FrameArgs fa,
                                                         unsigned long long *counters) {
-  __shared__ uint32_t stk[SLOTS * S::kFields * frame_block<DIAG>()];
+  __shared__ uint32_t stk[stack_words<S, SLOTS>() * frame_block<DIAG>()];
   constexpr bool kPair = RT_PAIR_FLUSH && DIAG == 0 && frame_block<DIAG>() == kBlock;
   __shared__ __attribute__((aligned(16))) uint32_t hf[kPair ? 2 * kPairWords + 4 : 4];
   S sc = sc_arg;
@@ -765,7 +774,7 @@ static_assert(kBBlock == 64 || kBBlock == kBlock, "batch workgroup: one wave or 
 template <class S, int SLOTS, bool GENERAL>
 __global__ __launch_bounds__(kBBlock) __attribute__((amdgpu_waves_per_eu(min_waves<S, SLOTS, GENERAL, 0>())))
 void render_batch_kernel(S sc, PlaneDev pl, FrameBatch fb) {
-  __shared__ uint32_t stk[SLOTS * S::kFields * kBBlock];
+  __shared__ uint32_t stk[stack_words<S, SLOTS>() * kBBlock];
   if constexpr (kBBlock == kBlock) {
     render_body<S, SLOTS, GENERAL, 0>(sc, pl, fb.f[blockIdx.z], nullptr, stk);
   } else {
@@ -874,7 +883,7 @@ __device__ __forceinline__ void q_leave(const PersistQ &q, uint32_t nh, int lane
 template <class S, int SLOTS, bool GENERAL>
 __global__ __launch_bounds__(kPBlock) __attribute__((amdgpu_waves_per_eu(min_waves<S, SLOTS, GENERAL, 0>())))
 void render_persist_kernel(S sc_arg, PlaneDev pl, FrameBatch fb, PersistQ q) {
-  __shared__ uint32_t stk[SLOTS * S::kFields * kPBlock];
+  __shared__ uint32_t stk[stack_words<S, SLOTS>() * kPBlock];
   S sc = sc_arg;
   if constexpr (S::kCoop && !GENERAL) sc.prio_iters = RT_HEAVY_PRIO;
   if constexpr (S::kLdsNodes > 0 && !GENERAL) {
@@ -1211,10 +1220,10 @@ __global__ __launch_bounds__(kBlock) void rays_kernel(S sc, PlaneDev pl, const f
                                                        const float *d3, int64_t n, float tn,
                                                        float tf, int32_t *hit, float *t,
                                                        float *nrm, int64_t *prim) {
-  __shared__ uint32_t stk[SLOTS * S::kFields * kBlock];
+  __shared__ uint32_t stk[stack_words<S, SLOTS>() * kBlock];
   const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   if (i >= n) return;
-  LdsStack<kBlock, S::kFields> st{stk + threadIdx.x};
+  StackOf<S, kBlock> st{stk + threadIdx.x};
   const f3 o{o3[3 * i], o3[3 * i + 1], o3[3 * i + 2]};
   const f3 d{d3[3 * i], d3[3 * i + 1], d3[3 * i + 2]};
   NoCnt cnt;

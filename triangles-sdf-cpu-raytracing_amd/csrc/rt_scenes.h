@@ -168,53 +168,77 @@ __device__ __forceinline__ void leaf_test(const rtl::GTri *__restrict__ tris, ui
 // Expand an inner node: slab-test its 8 children, sort8, keep t >= 0 entries
 // (a suffix of the sorted order) as a packed list of 3-bit ids + count. Also
 // returns the entry distance and child word of the first child to visit (the
-// child words arrive with the boxes: descending needs no extra load), and with
-// RT_MESH_T2 the entry distance of the SECOND child in visit order (has2 =
-// false when fewer than two are entered): the frame keeps it, so resuming at
-// that child needs no box reload (mesh_run).
+// child words arrive with the boxes: descending needs no extra load), and the
+// entry distance of the SECOND child in visit order and, with W2, its child
+// word (has2 = false when fewer than two are entered): the frame's record
+// keeps them, so resuming at that child needs no box reload (mesh_run).
 // 1: expand_node skips sort8 in waves whose rays all enter <= 2 children with
 // distinct t (A/B switch; 0 always runs the network)
 #ifndef RT_EXPAND_FAST
 #define RT_EXPAND_FAST 1
 #endif
-// 1: a frame keeps the entry distance of its second child (in a register for
-// the top frame, in a fourth LDS word for the stacked ones), and a resume at
-// that child prunes from it without touching memory or loads just the 4-byte
-// child word. 0: every resume reloads the child's box and recomputes the slab
-// test. A/B switch, off: bit-exact, but the extra live register and the loop
-// of pops spill inside the traversal loop at the 5-wave floor and the kernels
-// are slower.
+// The second-child record: per lane and per stack level (one level more than
+// the stack has slots: the top frame has one too) the entry distance of the
+// frame's second child in visit order and, in the two-word form, that child's
+// word, in LDS beside the frame stack (LdsStack::rec). The record of the frame
+// at stack depth d sits at level d - 1: the frame holds that level while it is
+// the top frame and keeps it once pushed, so the record is written once, where
+// the frame is created, and never moves; only a one-bit flag travels with the
+// frame. A resume at the second child then prunes without touching global
+// memory, or visits the child from the recorded word (two-word form) or after
+// loading just the 4-byte word (one-word form).
+// 2: both words for stacks of up to 4 slots, t alone for 7 slots (both would
+// not fit the CU's LDS at the kernel's waves). 1: t alone for up to 7 slots.
+// 0: no record, every resume reloads the child's box and recomputes the slab
+// test. Stacks deeper than 7 slots never take a record: their kernels are
+// LDS-limited. A/B switch, off: bit-exact and no kernel loses a wave, but on
+// the same tree the no-record build is 1.5 % (two words) and 1 % (one word)
+// faster on the bunny: the second select chain, the record's LDS traffic and
+// 16 B more scratch cost more than the saved round trips return (DESIGN.md
+// section 8, profiles/r10).
 #ifndef RT_MESH_T2
 #define RT_MESH_T2 0
 #endif
-// 1: the loads a resume needs after a leaf test (the LDS frame below when the
-// top frame ends with the leaf, the next child's word and, without a stored t,
-// its box) are issued above the leaf test, with the triangle batch. 2: only
-// the LDS reads and the 4-byte child word of a child with a stored t. 0: the
-// tail loads them after the leaf test. A/B switch, off: up to 7 more registers
-// live across the leaf test's 48 spill there.
-#ifndef RT_MESH_HOIST
-#define RT_MESH_HOIST 0
-#endif
-// 1: a run of frames that each end by a prune decided from their stored t is
-// popped inside one traversal iteration (a loop of LDS reads). 0: each such
-// end takes the next iteration to pop, as an end decided from a reloaded box
-// does (A/B switch).
-#ifndef RT_MESH_UNWIND
-#define RT_MESH_UNWIND 1
-#endif
-// LDS words per stacked mesh frame: node, list | count << 24 | stored-t flag
-// << 27, local best t and, in the 4-word form, the second child's entry t.
-// Stacks deeper than 7 slots stay at 3 words (their kernels are LDS-limited:
-// a fourth word would cost them a wave per SIMD); their frames carry the
-// stored t only while they are the top frame.
+// LDS words per stacked mesh frame: node, list | count << 24 | record flag
+// << 27, local best t
 template <int SLOTS>
-constexpr int mesh_fields() { return RT_MESH_T2 && SLOTS <= 7 ? 4 : 3; }
-template <bool FAST>
+constexpr int mesh_fields() { return 3; }
+// words of a stack level's second-child record
+template <int SLOTS>
+constexpr int mesh_rec() { return (RT_MESH_T2 == 0 || SLOTS > 7) ? 0 : (RT_MESH_T2 >= 2 && SLOTS <= 4) ? 2 : 1; }
+// 1: where expand_node runs the sort8 network it reads the child words of the
+// first two children from the node again afterwards (two 4-byte loads of a
+// line just read) instead of keeping all 8 words in registers across the
+// network, where they spill at the mesh kernels' 5-wave floor. The reload
+// waits where the spilled words' scratch reloads waited, with fewer vector
+// memory instructions: the persistent 4-slot kernel goes from 52 to 24 B of
+// scratch per lane, the batch and one-frame kernels to none, and the bunny at
+// 10 frames x 2 streams from 0.0644 to 0.0625 ms/frame (DESIGN.md section 4,
+// round 10). Waves that skip the network select from the registers, as
+// before. 0: the words are selected from the registers everywhere (A/B
+// switch).
+#ifndef RT_EXPAND_RELOAD
+#define RT_EXPAND_RELOAD 1
+#endif
+// the child words of the first and (W2) second child in visit order
+template <bool W2>
+__device__ __forceinline__ void select_words(const uint32_t (&cws)[8], uint32_t first_id, uint32_t second_id,
+                                             uint32_t &cwfirst, uint32_t &cwsecond) {
+  uint32_t cf = cws[0], cs = cws[0];
+#pragma unroll
+  for (int c = 1; c < 8; ++c) cf = (first_id == (uint32_t)c) ? cws[c] : cf;
+  if constexpr (W2) {
+#pragma unroll
+    for (int c = 1; c < 8; ++c) cs = (second_id == (uint32_t)c) ? cws[c] : cs;
+  }
+  cwfirst = cf;
+  cwsecond = cs;
+}
+template <bool FAST, bool W2 = false>
 __device__ __forceinline__ void expand_node(const rtl::GNode *__restrict__ node, f3 o, f3 inv,
                                             float tNear, float tFar, uint32_t &list,
                                             uint32_t &cnt, float &tfirst, uint32_t &cwfirst,
-                                            float &tsecond, bool &has2) {
+                                            float &tsecond, uint32_t &cwsecond, bool &has2) {
   const float4 *p = reinterpret_cast<const float4 *>(node);
   float bx[48];
 #pragma unroll
@@ -233,7 +257,7 @@ __device__ __forceinline__ void expand_node(const rtl::GNode *__restrict__ node,
                       bx[6 * c + 5], o, inv, tNear, tFar);  // box: xMin xMax yMin yMax zMin zMax
     id[c] = (uint32_t)c;
   }
-  uint32_t first_id = 0;
+  uint32_t first_id = 0, second_id = 0;
   bool sorted = false;
   if constexpr (FAST && RT_EXPAND_FAST) {
     // At most two children entered with distinct t: the network's output order
@@ -257,10 +281,12 @@ __device__ __forceinline__ void expand_node(const rtl::GNode *__restrict__ node,
       sorted = true;
       const bool sw = pc == 2 && tb < ta;
       first_id = sw ? ib : ia;
+      second_id = sw ? ia : ib;
       tfirst = pc == 0 ? 0.0f : (sw ? tb : ta);
       cnt = pc;
       tsecond = sw ? ta : tb;
       list = pc == 0 ? 0u : pc == 1 ? ia : (sw ? (ib | (ia << 3)) : (ia | (ib << 3)));
+      if constexpr (RT_EXPAND_RELOAD != 0) select_words<W2>(cws, first_id, second_id, cwfirst, cwsecond);
     }
   }
   if (!sorted) {
@@ -276,26 +302,41 @@ __device__ __forceinline__ void expand_node(const rtl::GNode *__restrict__ node,
         cnt += 1;
         tsecond = tfirst;
         tfirst = t[i];
+        second_id = first_id;
         first_id = id[i];
       }
     }
+    if constexpr (RT_EXPAND_RELOAD != 0) {
+      // the words of the two children, read again now that the order is known
+      // (the node's line is in the L1): the 8 words need not stay in
+      // registers across the network
+      cwfirst = node->child[first_id];
+      cwsecond = W2 ? node->child[second_id] : 0u;
+    }
   }
-  uint32_t cf = cws[0];
-#pragma unroll
-  for (int c = 1; c < 8; ++c) cf = (first_id == (uint32_t)c) ? cws[c] : cf;
-  cwfirst = cf;
-  has2 = RT_MESH_T2 && cnt >= 2;
+  if constexpr (RT_EXPAND_RELOAD == 0) select_words<W2>(cws, first_id, second_id, cwfirst, cwsecond);
+  has2 = cnt >= 2;
 }
 
-template <int BLOCK, int F = 3>
+// A stack level is R record words (the mesh's second-child record, mesh_rec)
+// followed by the F words of the frame slot. The deepest top frame has a
+// record and no slot, so a stack of SLOTS slots takes lds_stack_words words
+// per lane: SLOTS whole levels and the records of level SLOTS.
+template <int BLOCK, int F = 3, int R = 0>
 struct LdsStack {
-  uint32_t *base;  // lane-interleaved words, F words per frame slot
+  uint32_t *base;  // lane-interleaved words, R + F words per level
   __device__ __forceinline__ uint32_t &at(int slot, int field) {
-    // slot * F * BLOCK as a full-rate 24-bit multiply (slots are small): the
-    // plain form compiles to the quarter-rate v_mul_lo_u32
-    return base[__umul24((uint32_t)slot, (uint32_t)(F * BLOCK)) + (uint32_t)(field * BLOCK)];
+    // slot * (R + F) * BLOCK as a full-rate 24-bit multiply (slots are small):
+    // the plain form compiles to the quarter-rate v_mul_lo_u32
+    return base[__umul24((uint32_t)slot, (uint32_t)((R + F) * BLOCK)) + (uint32_t)((R + field) * BLOCK)];
+  }
+  // record word i of `level` (0 .. SLOTS)
+  __device__ __forceinline__ uint32_t &rec(int level, int i) {
+    return base[__umul24((uint32_t)level, (uint32_t)((R + F) * BLOCK)) + (uint32_t)(i * BLOCK)];
   }
 };
+template <int SLOTS, int F, int R = 0>
+constexpr int lds_stack_words() { return SLOTS * (R + F) + R; }
 
 // ANY = true: shadow-ray query, stop at the first leaf hit (only hitten is used).
 // Slab test of the root union box: true iff the ray certainly misses it.
@@ -314,13 +355,13 @@ __device__ __forceinline__ bool root_box_miss(const float *b, f3 o, f3 inv, floa
 // Root stage of BVHBuilder::traverseNode(0): the union-box pretest and the
 // root's 8-child expansion (wave-uniform node: scalar loads). Returns false if
 // the traversal ends here (no child entered); otherwise the root frame.
-template <bool FAST = false, class CT>
+template <bool FAST = false, bool W2 = false, class CT>
 __device__ __forceinline__ bool mesh_root(const MeshDev &sc, f3 o, f3 inv, float tNear, float tFar,
                                           uint32_t &l, uint32_t &c, float &tf, uint32_t &cwf,
-                                          float &ts, bool &has2, CT &cnt) {
+                                          float &ts, uint32_t &cws, bool &has2, CT &cnt) {
   cnt.add(C_BVH_INNER, 1);
   if (root_box_miss(sc.rbox, o, inv, tNear, tFar)) return false;
-  expand_node<FAST>(sc.nodes + sc.root, o, inv, tNear, tFar, l, c, tf, cwf, ts, has2);
+  expand_node<FAST, W2>(sc.nodes + sc.root, o, inv, tNear, tFar, l, c, tf, cwf, ts, cws, has2);
   return c != 0;
 }
 
@@ -339,8 +380,7 @@ struct MState {
   float gbest;      // best t so far
   int32_t depth;    // frames on the stack, incl. the top one
   bool have_t;
-  float t2;         // top frame: entry t of its second child (valid with t2v)
-  bool t2v;         // the next child of the top frame is its second and t2 holds its entry t
+  bool t2v;         // the next child of the top frame is its second and the frame's record holds it
 };
 
 // Frame ends by pruning handled per traversal iteration (1: one; the next
@@ -389,23 +429,23 @@ constexpr int kCoopRays = RT_COOP_RAYS;
 // 0.342 -> 0.523 ms.) TAIL: before each iteration, if kCoopRays or fewer lanes
 // of the wave are still looping, store the state and return true (suspended).
 //
-// Resuming a frame (RT_MESH_T2): a frame's first child is visited from the
-// expansion's registers; its second child's entry t stays with the frame (t2,
-// LDS word 3 once the frame is stacked, flag bit 27 of word 1). A resume at
-// the second child tests fbest < t2 without touching memory: pruned, the frame
-// ends and the frame below is popped in the same iteration (a loop of LDS
-// reads, at most the stack depth long, up to the first frame that yields a
-// child or has no stored t); not pruned, only the 4-byte child word is
-// loaded. Third and later children reload their box and child word and redo
-// the slab test, and a prune there ends the iteration as before. The stored
-// bits are those the slab test returned at expansion: the same function of
-// the same node and ray, so the same decision (a NaN stays a NaN: visited).
-template <int BLOCK, bool ANY, bool FAST, bool TAIL, uint32_t LB = RT_LEAF_BATCH, bool MAJ = false, int F, class CT>
+// Resuming a frame (R > 0 record words, mesh_rec): a frame's first child is
+// visited from the expansion's registers; its second child's entry t and, with
+// R = 2, child word are in the frame's record (LDS level depth - 1, written
+// where the frame is created; the flag t2v, bit 27 of word 1 once the frame is
+// stacked, says the next child is that one). A resume at the second child
+// reads t from the record: pruned, the frame ends without a global load and
+// the next iteration pops it; entered, the child word comes from the record
+// (R = 2) or from a 4-byte load (R = 1). Third and later children reload their
+// box and child word and redo the slab test. The recorded bits are those the
+// slab test returned at expansion: the same function of the same node and
+// ray, so the same decision (a NaN stays a NaN: visited).
+template <int BLOCK, bool ANY, bool FAST, bool TAIL, uint32_t LB = RT_LEAF_BATCH, bool MAJ = false, int F, int R, class CT>
 __device__ __forceinline__ bool mesh_run(const MeshDev &sc, f3 o, f3 d, f3 inv, float tNear, float tFar,
-                                         LdsStack<BLOCK, F> st, MState &S, CT &cnt, int coop_rays = kCoopRays,
+                                         LdsStack<BLOCK, F, R> st, MState &S, CT &cnt, int coop_rays = kCoopRays,
                                          int prio_iters = 0) {
   uint32_t word = S.word, flist = S.flist, fcnt = S.fcnt, fnode = S.fnode, gk = S.gk;
-  float fbest = S.fbest, gbest = S.gbest, t2 = S.t2;
+  float fbest = S.fbest, gbest = S.gbest;
   int depth = S.depth;
   bool t2v = S.t2v;
   bool suspended = false;
@@ -432,12 +472,7 @@ __device__ __forceinline__ bool mesh_run(const MeshDev &sc, f3 o, f3 d, f3 inv, 
     fcnt = (lc >> 24) & 7u;  // a stacked frame has 1..7 children left
     fbest = __uint_as_float(st.at(depth - 1, 2));
     if (child_best < fbest) fbest = child_best;
-    if constexpr (F >= 4) {
-      t2v = ((lc >> 27) & 1u) != 0;
-      t2 = __uint_as_float(st.at(depth - 1, 3));
-    } else {
-      t2v = false;
-    }
+    t2v = R > 0 && ((lc >> 27) & 1u) != 0;
   };
   for (;;) {
     if (TAIL && __popcll(__ballot(1)) <= coop_rays) { suspended = true; break; }
@@ -459,63 +494,26 @@ __device__ __forceinline__ bool mesh_run(const MeshDev &sc, f3 o, f3 d, f3 inv, 
       if ((isL && waitL) || (isI && waitI)) continue;
     }
 #endif
-    // loads of the child the tail below will look at, issued above a leaf test
-    // (RT_MESH_HOIST): pre = this lane's are in pcw (child word) and pb (box)
-    bool pre = false;
-    uint32_t pcw = 0;
-    float pb[6];
     // a frame expanded in this iteration: its first child's entry t and word
     bool have_t = false;
     float tnext = 0.0f;
     uint32_t cwnext = rtl::kInvalidChild;
     if (word != rtl::kInvalidChild) {
       if (word & rtl::kLeafBit) {
-        // A leaf test pushes no frame, so the frame the tail resumes after it
-        // is known here: the top frame if it has a child left, else the frame
-        // below, which is popped now (its LDS reads leave with the triangle
-        // batch; the leaf's t then folds through `ended`, the ended frame's
-        // best, as it would on the pop). The next child's word, and its box
-        // where its entry t is not stored, are loaded with the triangles: one
-        // wait covers both, and the tail finds them in registers.
-        float ended = kInf;
-        bool popped = false;
-        if constexpr (RT_MESH_HOIST != 0) {
-          if (fcnt == 0 && depth >= 2) {
-            ended = fbest;
-            fbest = kInf;  // (pop folds the ended frame's best at once: +inf leaves the frame's own)
-            pop();
-            popped = true;
-          }
-          if (fcnt != 0) {
-            const rtl::GNode *nd = mesh_node(sc, fnode);
-            const uint32_t j = flist & 7u;
-            pre = RT_MESH_HOIST == 1 || (RT_MESH_T2 && t2v);
-            if (pre) pcw = nd->child[j];
-            if (RT_MESH_HOIST == 1 && !(RT_MESH_T2 && t2v)) {
-#pragma unroll
-              for (int i = 0; i < 6; ++i) pb[i] = nd->box[j][i];
-            }
-          }
-        }
         float lt = kInf;
         uint32_t lk = rtl::kInvalidChild;
         leaf_test<LB, FAST>(sc.tris, word, o, d, lt, lk, cnt);
         if (lk != rtl::kInvalidChild) {
           if (ANY) { gbest = lt; gk = lk; break; }
-          if (popped) {
-            if (lt < ended) ended = lt;
-          } else {
-            if (lt < fbest) fbest = lt;
-          }
+          if (lt < fbest) fbest = lt;
           if (lt < gbest) { gbest = lt; gk = lk; }
         }
-        if (popped && ended < fbest) fbest = ended;
       } else {
-        uint32_t l, c, cwf;
+        uint32_t l, c, cwf, cws;
         float tf, ts;
         bool has2;
         cnt.add(C_BVH_INNER, 1);
-        expand_node<FAST>(mesh_node(sc, word), o, inv, tNear, tFar, l, c, tf, cwf, ts, has2);
+        expand_node<FAST, R >= 2>(mesh_node(sc, word), o, inv, tNear, tFar, l, c, tf, cwf, ts, cws, has2);
         if (c != 0) {
           if (depth >= 1 && fcnt == 0) {
             // tail call: the top frame has no child left, so it is replaced,
@@ -529,12 +527,7 @@ __device__ __forceinline__ bool mesh_run(const MeshDev &sc, f3 o, f3 d, f3 inv, 
           } else {
             if (depth >= 1) {
               st.at(depth - 1, 0) = fnode;
-              if constexpr (F >= 4) {
-                st.at(depth - 1, 1) = flist | (fcnt << 24) | ((uint32_t)t2v << 27);
-                st.at(depth - 1, 3) = __float_as_uint(t2);
-              } else {
-                st.at(depth - 1, 1) = flist | (fcnt << 24);
-              }
+              st.at(depth - 1, 1) = flist | (fcnt << 24) | (R > 0 ? (uint32_t)t2v << 27 : 0u);
               st.at(depth - 1, 2) = __float_as_uint(fbest);
             }
             ++depth;
@@ -543,68 +536,49 @@ __device__ __forceinline__ bool mesh_run(const MeshDev &sc, f3 o, f3 d, f3 inv, 
           tnext = tf;
           cwnext = cwf;
           have_t = true;
-          t2 = ts;
-          t2v = has2;
+          // the new frame's record, at the level it keeps for its lifetime
+          if constexpr (R >= 1) st.rec(depth - 1, 0) = __float_as_uint(ts);
+          if constexpr (R >= 2) st.rec(depth - 1, 1) = cws;
+          t2v = R > 0 && has2;
         }
       }
       word = rtl::kInvalidChild;
     }
-    // choose the next child; a pruned child ends its frame. First the part
-    // that needs no global memory: pops, and prunes decided from a stored t
-    // (a loop of LDS reads, at most the stack depth long); then, in one place
-    // for every lane that needs one, the global load: the child word alone
-    // after a stored t that does not prune, else the child's box and word.
-    // After an end decided from a reloaded box, up to RT_MESH_PRUNE_PASSES - 1
-    // more such rounds follow in this iteration.
+    // choose the next child; a pruned child ends its frame. A pop first, where
+    // the top frame has ended; then the child's entry t and word: from the
+    // expansion's registers (a fresh frame's first child), from the frame's
+    // record (its second child: LDS reads, and with a one-word record the
+    // 4-byte child word of a child that is entered), or from the child's box
+    // and word, reloaded. After an end decided from a reloaded box, up to
+    // RT_MESH_PRUNE_PASSES - 1 more such rounds follow in this iteration.
     bool done = false;
     for (int pass = 0; pass < RT_MESH_PRUNE_PASSES; ++pass) {
-      bool load = false, stored = false;
-      uint32_t j = 0;
-      for (;;) {
-        if (depth == 0) { done = true; break; }
-        if (fcnt == 0) {  // frame done: fold its best into the parent frame
-          if (depth == 1) { depth = 0; done = true; break; }
-          pop();
-          have_t = false;
-          // stacked frames always have a child left: go on to it
-        }
-        j = flist & 7u;
-        flist >>= 3;
-        fcnt -= 1;
-        if (have_t) break;  // fresh frame: its first child, from the expansion's registers
-        load = true;
-        stored = RT_MESH_T2 && t2v;
-        if (!stored) break;  // a third or later child (or no stored t): reload
-        t2v = false;
-        if (!(fbest < t2)) break;  // its second child, entered: only the child word is missing
-        fcnt = 0;  // pruned without a load
-        load = false;
-        pre = false;
-        if (!RT_MESH_UNWIND) { tnext = t2; break; }  // the next iteration pops
+      if (depth == 0) { done = true; break; }
+      if (fcnt == 0) {  // frame done: fold its best into the parent frame
+        if (depth == 1) { depth = 0; done = true; break; }
+        pop();
+        have_t = false;
+        // stacked frames always have a child left: go on to it
       }
-      if (done) break;
-      if (load) {
-        float b[6];
-        if (pre) {  // issued above the leaf test
-          cwnext = pcw;
-          if (!stored) {
-#pragma unroll
-            for (int i = 0; i < 6; ++i) b[i] = pb[i];
-          }
+      const uint32_t j = flist & 7u;
+      flist >>= 3;
+      fcnt -= 1;
+      if (!have_t) {  // (a fresh frame's first child is in tnext, cwnext)
+        if (R > 0 && t2v) {  // the recorded bits are the ones this slab test would return again
+          t2v = false;
+          tnext = __uint_as_float(st.rec(depth - 1, 0));
+          if constexpr (R >= 2) cwnext = st.rec(depth - 1, 1);
+          else if (!(fbest < tnext)) cwnext = mesh_node(sc, fnode)->child[j];
         } else {
           const rtl::GNode *nd = mesh_node(sc, fnode);
+          float b[6];
           cwnext = nd->child[j];
-          if (!stored) {
 #pragma unroll
-            for (int i = 0; i < 6; ++i) b[i] = nd->box[j][i];
-          }
+          for (int i = 0; i < 6; ++i) b[i] = nd->box[j][i];
+          tnext = slab<FAST>(b[0], b[2], b[4], b[1], b[3], b[5], o, inv, tNear, tFar);
         }
-        // the stored bits are the ones this slab test would return again
-        if (stored) tnext = t2;
-        else tnext = slab<FAST>(b[0], b[2], b[4], b[1], b[3], b[5], o, inv, tNear, tFar);
       }
       have_t = false;
-      pre = false;
       if (!(fbest < tnext)) { word = cwnext; break; }
       fcnt = 0;  // pruned; later siblings have larger t
     }
@@ -612,17 +586,18 @@ __device__ __forceinline__ bool mesh_run(const MeshDev &sc, f3 o, f3 d, f3 inv, 
   }
   S.word = word; S.flist = flist; S.fcnt = fcnt; S.fnode = fnode; S.gk = gk;
   S.fbest = fbest; S.gbest = gbest; S.depth = depth;
-  S.t2 = t2; S.t2v = t2v;
+  S.t2v = t2v;
   return suspended;
 }
 
-template <int BLOCK, bool ANY, bool FAST = false, int F, class CT>
+// (t2v: the root frame's record, level 0 of st, holds its second child)
+template <int BLOCK, bool ANY, bool FAST = false, int F, int R, class CT>
 __device__ __forceinline__ bool mesh_continue(const MeshDev &sc, f3 o, f3 d, f3 inv, float tNear,
-                                              float tFar, LdsStack<BLOCK, F> st, uint32_t word,
+                                              float tFar, LdsStack<BLOCK, F, R> st, uint32_t word,
                                               uint32_t flist, uint32_t fcnt, float tnext,
-                                              uint32_t cwnext, bool have_t, float t2, bool t2v, int depth,
+                                              uint32_t cwnext, bool have_t, bool t2v, int depth,
                                               float &out_t, uint32_t &out_k, CT &cnt) {
-  MState S{word, flist, fcnt, sc.root, cwnext, rtl::kInvalidChild, kInf, tnext, kInf, depth, have_t, t2, t2v};
+  MState S{word, flist, fcnt, sc.root, cwnext, rtl::kInvalidChild, kInf, tnext, kInf, depth, have_t, t2v};
   mesh_run<BLOCK, ANY, FAST, false>(sc, o, d, inv, tNear, tFar, st, S, cnt);
   out_t = S.gbest;
   out_k = S.gk;
@@ -715,11 +690,13 @@ __device__ __forceinline__ uint32_t grp_or(uint32_t v, int k) {
 
 // mesh_run (non-ANY) executed by an 8-lane group on one ray; S is the same in
 // all 8 lanes and stays so. st = the owner lane's LDS stack column.
-template <int BLOCK, bool FAST, int F>
+// The group reads the records the per-lane loop wrote into that column and
+// writes its own frames' there (all 8 lanes store the same words).
+template <int BLOCK, bool FAST, int F, int R>
 __device__ __forceinline__ void mesh_run_coop(const MeshDev &sc, f3 o, f3 d, f3 inv, float tNear,
-                                              float tFar, LdsStack<BLOCK, F> st, MState &S, int k) {
+                                              float tFar, LdsStack<BLOCK, F, R> st, MState &S, int k) {
   uint32_t word = S.word, flist = S.flist, fcnt = S.fcnt, fnode = S.fnode, cwnext = S.cwnext, gk = S.gk;
-  float fbest = S.fbest, tnext = S.tnext, gbest = S.gbest, t2 = S.t2;
+  float fbest = S.fbest, tnext = S.tnext, gbest = S.gbest;
   int depth = S.depth;
   bool have_t = S.have_t, t2v = S.t2v;
   const int gbase = (threadIdx.x & 63) & ~7;
@@ -755,7 +732,14 @@ __device__ __forceinline__ void mesh_run_coop(const MeshDev &sc, f3 o, f3 d, f3 
         const float tf = __shfl(t, gbase + (int)(i0 & 7u), 64);
         const uint32_t idf = __shfl(id, gbase + (int)(i0 & 7u), 64);
         const uint32_t cwf = __shfl(cwk, gbase + (int)idf, 64);
-        const float ts = __shfl(t, gbase + (int)((i0 + 1u) & 7u), 64);  // the second child's entry t
+        // the second child's entry t and word (the next entry of the sorted order)
+        float ts = 0.0f;
+        uint32_t cws = 0;
+        if constexpr (R >= 1) ts = __shfl(t, gbase + (int)((i0 + 1u) & 7u), 64);
+        if constexpr (R >= 2) {
+          const uint32_t ids = __shfl(id, gbase + (int)((i0 + 1u) & 7u), 64);
+          cws = __shfl(cwk, gbase + (int)ids, 64);
+        }
         if (c != 0) {
           if (depth >= 1 && fcnt == 0) {  // tail call, as in mesh_run
             if (depth >= 2) {
@@ -765,12 +749,7 @@ __device__ __forceinline__ void mesh_run_coop(const MeshDev &sc, f3 o, f3 d, f3 
           } else {
             if (depth >= 1) {
               st.at(depth - 1, 0) = fnode;
-              if constexpr (F >= 4) {
-                st.at(depth - 1, 1) = flist | (fcnt << 24) | ((uint32_t)t2v << 27);
-                st.at(depth - 1, 3) = __float_as_uint(t2);
-              } else {
-                st.at(depth - 1, 1) = flist | (fcnt << 24);
-              }
+              st.at(depth - 1, 1) = flist | (fcnt << 24) | (R > 0 ? (uint32_t)t2v << 27 : 0u);
               st.at(depth - 1, 2) = __float_as_uint(fbest);
             }
             ++depth;
@@ -779,8 +758,9 @@ __device__ __forceinline__ void mesh_run_coop(const MeshDev &sc, f3 o, f3 d, f3 
           tnext = tf;
           cwnext = cwf;
           have_t = true;
-          t2 = ts;
-          t2v = RT_MESH_T2 && c >= 2;
+          if constexpr (R >= 1) st.rec(depth - 1, 0) = __float_as_uint(ts);
+          if constexpr (R >= 2) st.rec(depth - 1, 1) = cws;
+          t2v = R > 0 && c >= 2;
         }
       }
       word = rtl::kInvalidChild;
@@ -797,22 +777,19 @@ __device__ __forceinline__ void mesh_run_coop(const MeshDev &sc, f3 o, f3 d, f3 
       fbest = __uint_as_float(st.at(depth - 1, 2));
       if (child_best < fbest) fbest = child_best;
       have_t = false;
-      if constexpr (F >= 4) {
-        t2v = ((lc >> 27) & 1u) != 0;
-        t2 = __uint_as_float(st.at(depth - 1, 3));
-      } else {
-        t2v = false;
-      }
+      t2v = R > 0 && ((lc >> 27) & 1u) != 0;
     }
     const uint32_t j = flist & 7u;
     flist >>= 3;
     fcnt -= 1;
     if (have_t) {
       have_t = false;
-    } else if (RT_MESH_T2 && t2v) {  // second child: the stored entry t, as in mesh_run
+    } else if (R > 0 && t2v) {  // second child: the frame's record, as in mesh_run
       t2v = false;
-      if (fbest < t2) { fcnt = 0; continue; }
-      word = mesh_node(sc, fnode)->child[j];
+      tnext = __uint_as_float(st.rec(depth - 1, 0));
+      if (fbest < tnext) { fcnt = 0; continue; }
+      if constexpr (R >= 2) word = st.rec(depth - 1, 1);
+      else word = mesh_node(sc, fnode)->child[j];
       continue;
     } else {
       const rtl::GNode *nd = mesh_node(sc, fnode);
@@ -831,7 +808,8 @@ __device__ __forceinline__ void mesh_run_coop(const MeshDev &sc, f3 o, f3 d, f3 
 // call it, with active = false for lanes without a pixel): each lane traverses
 // its own ray until at most kCoopRays rays remain, then those finish in 8-lane
 // groups. The result is the same as mesh_trace's, bit for bit.
-template <int BLOCK, int F>
+// (RW: the record words of a stack level, R elsewhere)
+template <int BLOCK, int F, int RW>
 __device__ __forceinline__ bool mesh_primary_wave(const MeshDev &sc, f3 o, f3 d, float tNear, float tFar,
                                                   bool active, uint32_t *stk_block, float &out_t,
                                                   uint32_t &out_k, int coop_rays = kCoopRays,
@@ -839,27 +817,30 @@ __device__ __forceinline__ bool mesh_primary_wave(const MeshDev &sc, f3 o, f3 d,
   if (prio_iters > 0) __builtin_amdgcn_s_setprio(0);  // a new tile starts at normal priority
   NoCnt cnt;
   const int lane = threadIdx.x & 63;
-  LdsStack<BLOCK, F> st{stk_block + threadIdx.x};
+  LdsStack<BLOCK, F, RW> st{stk_block + threadIdx.x};
   const f3 inv{1.0f / d.x, 1.0f / d.y, 1.0f / d.z};  // 1.0f / rayDir (:273)
   // fast: the finite-1/d slab forms and the fast reciprocal (MeshDev::dmax2)
   const bool fast = __builtin_isfinite(inv.x) && __builtin_isfinite(inv.y) && __builtin_isfinite(inv.z) &&
                     dot(d, d) <= sc.dmax2;
   MState S{rtl::kInvalidChild, 0u, 0u, sc.root, rtl::kInvalidChild, rtl::kInvalidChild, kInf, 0.0f, kInf, 0,
-           false, 0.0f, false};
+           false, false};
   bool pending = false;
   if (active && sc.root != rtl::kInvalidChild) {
     if (sc.root & rtl::kLeafBit) {
       S.word = sc.root;
       pending = true;
     } else {
-      uint32_t l, c, cwf;
+      uint32_t l, c, cwf, cws;
       float tf, ts;
       bool has2;
-      const bool entered = fast ? mesh_root<true>(sc, o, inv, tNear, tFar, l, c, tf, cwf, ts, has2, cnt)
-                                : mesh_root<false>(sc, o, inv, tNear, tFar, l, c, tf, cwf, ts, has2, cnt);
+      const bool entered = fast ? mesh_root<true, RW >= 2>(sc, o, inv, tNear, tFar, l, c, tf, cwf, ts, cws, has2, cnt)
+                                : mesh_root<false, RW >= 2>(sc, o, inv, tNear, tFar, l, c, tf, cwf, ts, cws, has2, cnt);
       if (entered) {
         S.flist = l; S.fcnt = c; S.tnext = tf; S.cwnext = cwf; S.depth = 1; S.have_t = true;
-        S.t2 = ts; S.t2v = has2;
+        // the root frame's record
+        if constexpr (RW >= 1) st.rec(0, 0) = __float_as_uint(ts);
+        if constexpr (RW >= 2) st.rec(0, 1) = cws;
+        S.t2v = RW > 0 && has2;
         pending = true;
       }
     }
@@ -908,10 +889,9 @@ __device__ __forceinline__ bool mesh_primary_wave(const MeshDev &sc, f3 o, f3 d,
     G.gbest = __shfl(S.gbest, owner, 64);
     G.depth = __shfl(S.depth, owner, 64);
     G.have_t = __shfl((int)S.have_t, owner, 64) != 0;
-    G.t2 = __shfl(S.t2, owner, 64);
     G.t2v = __shfl((int)S.t2v, owner, 64) != 0;
     if (g < n) {
-      const LdsStack<BLOCK, F> gst{stk_block + (threadIdx.x & ~63) + owner};
+      const LdsStack<BLOCK, F, RW> gst{stk_block + (threadIdx.x & ~63) + owner};
       if (gfast)
         mesh_run_coop<BLOCK, true>(sc, go, gd, ginv, tNear, gtf, gst, G, k);
       else
@@ -928,32 +908,38 @@ __device__ __forceinline__ bool mesh_primary_wave(const MeshDev &sc, f3 o, f3 d,
   return S.gk != rtl::kInvalidChild;
 }
 
-template <int BLOCK, bool ANY, int F, class CT>
+template <int BLOCK, bool ANY, int F, int R, class CT>
 __device__ __forceinline__ bool mesh_trace(const MeshDev &sc, f3 o, f3 d, float tNear, float tFar,
-                                           LdsStack<BLOCK, F> st, float &out_t, uint32_t &out_k,
+                                           LdsStack<BLOCK, F, R> st, float &out_t, uint32_t &out_k,
                                            CT &cnt) {
   const f3 inv{1.0f / d.x, 1.0f / d.y, 1.0f / d.z};  // 1.0f / rayDir (:273)
   if (sc.root == rtl::kInvalidChild) return false;
   if (sc.root & rtl::kLeafBit)
     return mesh_continue<BLOCK, ANY>(sc, o, d, inv, tNear, tFar, st, sc.root, 0u, 0u, 0.0f,
-                                     rtl::kInvalidChild, false, 0.0f, false, 0, out_t, out_k, cnt);
-  uint32_t l, c, cwf;
+                                     rtl::kInvalidChild, false, false, 0, out_t, out_k, cnt);
+  uint32_t l, c, cwf, cws;
   float tf, ts;
   bool has2;
+  // the root frame's record (level 0)
+  const auto record = [&]() {
+    if constexpr (R >= 1) st.rec(0, 0) = __float_as_uint(ts);
+    if constexpr (R >= 2) st.rec(0, 1) = cws;
+    return R > 0 && has2;
+  };
   if (__builtin_isfinite(inv.x) && __builtin_isfinite(inv.y) && __builtin_isfinite(inv.z) &&
       dot(d, d) <= sc.dmax2) {  // (see mesh_primary_wave)
-    if (!mesh_root<true>(sc, o, inv, tNear, tFar, l, c, tf, cwf, ts, has2, cnt)) return false;
+    if (!mesh_root<true, R >= 2>(sc, o, inv, tNear, tFar, l, c, tf, cwf, ts, cws, has2, cnt)) return false;
     return mesh_continue<BLOCK, ANY, true>(sc, o, d, inv, tNear, tFar, st, rtl::kInvalidChild, l, c, tf,
-                                           cwf, true, ts, has2, 1, out_t, out_k, cnt);
+                                           cwf, true, record(), 1, out_t, out_k, cnt);
   }
-  if (!mesh_root<false>(sc, o, inv, tNear, tFar, l, c, tf, cwf, ts, has2, cnt)) return false;
+  if (!mesh_root<false, R >= 2>(sc, o, inv, tNear, tFar, l, c, tf, cwf, ts, cws, has2, cnt)) return false;
   return mesh_continue<BLOCK, ANY, false>(sc, o, d, inv, tNear, tFar, st, rtl::kInvalidChild, l, c, tf,
-                                          cwf, true, ts, has2, 1, out_t, out_k, cnt);
+                                          cwf, true, record(), 1, out_t, out_k, cnt);
 }
 
-template <int BLOCK, int F, class CT>
+template <int BLOCK, int F, int R, class CT>
 __device__ __forceinline__ Hit mesh_intersect(const MeshDev &sc, f3 o, f3 d, float tNear, float tFar,
-                                              LdsStack<BLOCK, F> st, CT &cnt) {
+                                              LdsStack<BLOCK, F, R> st, CT &cnt) {
   float t;
   uint32_t k;
   Hit h = miss_hit();
@@ -965,9 +951,9 @@ __device__ __forceinline__ Hit mesh_intersect(const MeshDev &sc, f3 o, f3 d, flo
   }
   return h;
 }
-template <int BLOCK, int F, class CT>
+template <int BLOCK, int F, int R, class CT>
 __device__ __forceinline__ bool mesh_occluded(const MeshDev &sc, f3 o, f3 d, float tNear, float tFar,
-                                              LdsStack<BLOCK, F> st, CT &cnt) {
+                                              LdsStack<BLOCK, F, R> st, CT &cnt) {
   float t;
   uint32_t k;
   return mesh_trace<BLOCK, true>(sc, o, d, tNear, tFar, st, t, k, cnt);
