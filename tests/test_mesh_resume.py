@@ -1,8 +1,9 @@
-"""Resuming and unwinding mesh traversal frames (mesh_run's choose-next tail
-and, when built in, the frame's stored second-child distance and the loads
-hoisted above the leaf test: csrc/rt_scenes.h, RT_MESH_T2 / RT_MESH_HOIST),
-against the oracle, bit for bit: colour, coverage and t bits of frames, hit /
-t / normal / id of rays.
+"""Resuming and unwinding mesh traversal frames (the choose-next tail of
+mesh_run and mesh_run_coop, csrc/rt_scenes.h: a resumed frame reloads its next
+child's box and word; builds that kept the second child's entry distance with
+the frame, or hoisted the resume's loads above the leaf test, were measured
+and deleted), against the oracle, bit for bit: colour,
+coverage and t bits of frames, hit / t / normal / id of rays.
 
 The meshes are the overlapping, tie-heavy ones of test_gpu_edge.py at sizes
 whose trees take the 4-, 7- and 15-slot kernels: `rand` prunes at second and

@@ -1,12 +1,13 @@
-"""A mesh frame's second child: the resume that the second-child record
-(csrc/rt_scenes.h, RT_MESH_T2, LdsStack::rec) serves from LDS and that a build
-without the record serves by reloading the child's box. Everything is compared
-with the oracle bit for bit, so the file holds on either build.
+"""A mesh frame's second child: the resume that reloads the child's box and
+word (csrc/rt_scenes.h, mesh_run and mesh_run_coop). A second-child record in
+LDS beside the frame stack once served it without the reload; it was measured
+slower and deleted. Everything is compared with the
+oracle bit for bit, so the file holds on any build.
 
 What it adds to test_mesh_resume.py:
   * trees of an exact depth (asserted on the host through rt_bvh_export before
     anything is rendered): 5 levels, where the deepest top frame of the 4-slot
-    kernels sits one level beyond the stack's slots (record level SLOTS), and 8
+    kernels sits one level beyond the stack's slots, and 8
     levels, the same for the 7-slot kernels. The `same` meshes (every triangle
     identical: all siblings tie, none is pruned) walk every root-to-leaf path,
     so the deepest level is reached;

@@ -2,8 +2,8 @@
 kernel trace (the check that bench.py's event-timed kernel_ms agrees with the
 profiler).
 
-bench.py issues, on the headline kernel (render_persist_kernel<MeshSF<3>, 4,
-false> for the bunny): the warm-up launches over the stream pool (max(--warmup,
+bench.py issues, on the headline kernel (render_persist_kernel<MeshS, 4, false>
+for the bunny): the warm-up launches over the stream pool (max(--warmup,
 2 x 8) frames: 2 launches at the defaults), the timed two-stream launches, then
 for roofline.one_stream the same warm-up frames on one stream (2 launches) and
 the timed one-stream launches. Dispatches are taken in Dispatch_Id order.
@@ -19,7 +19,7 @@ import sys
 
 def main():
     f, n = sys.argv[1], int(sys.argv[2])
-    key = sys.argv[3] if len(sys.argv) > 3 else "render_persist_kernel<(anonymous namespace)::MeshSF<3>, 4, false>"
+    key = sys.argv[3] if len(sys.argv) > 3 else "render_persist_kernel<(anonymous namespace)::MeshS, 4, false>"
     rows = [r for r in csv.DictReader(open(f)) if key in r["Kernel_Name"]]
     rows.sort(key=lambda r: int(r["Dispatch_Id"]))
     d = [(int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e6 for r in rows]

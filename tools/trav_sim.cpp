@@ -196,8 +196,9 @@ void replay(const std::vector<std::string> &s, int policy, double cI, double cL,
 // child" tail. The top part's node or triangle fetch is one dependent global
 // round trip; a tail that resumes a frame at a child whose entry t is not at
 // hand reloads the child's box and word: a second one, exposed after the first.
-// Variants:
-//   V0  the loop as it was: every resume reloads and recomputes the slab test;
+// Variants (V0 is the loop that ships; V1 to V3 were built, measured slower
+// and are no longer in the tree):
+//   V0  every resume reloads and recomputes the slab test;
 //   V1  the frame keeps its second child's entry t (RT_MESH_T2): a prune there
 //       costs no load and the frames below are unwound in the same iteration,
 //       a visit loads only the 4-byte child word;
@@ -209,7 +210,7 @@ void replay(const std::vector<std::string> &s, int policy, double cI, double cL,
 //       visit takes the word from the record
 //       (profiles/r10/trav_sim_resume.txt).
 // Per ray: round trips by class. Per wave tile (lockstep, the minority side of
-// a leaf / inner split waits, RT_MESH_MAJ = 1): wave iterations, iterations in
+// a leaf / inner split waits, as mesh_run does for primary rays): wave iterations, iterations in
 // which any advancing lane needs the second round trip, exposed round trips
 // (first + second). The cooperative tail is not modelled: its 8-lane groups
 // walk the same per-ray sequence.

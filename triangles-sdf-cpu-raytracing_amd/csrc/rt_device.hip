@@ -79,11 +79,10 @@ struct FrameArgs {
 };
 
 // ---------------------------------------------------------- scene adapters --
-// kFields = LDS words per traversal frame (mesh: node, list|count|record flag,
-// best t, mesh_fields; octree: node, list|count; grid: none). kRec = words of
-// a stack level's second-child record (mesh_rec: the mesh kernels of up to 7
-// slots; else 0). StackOf: the adapter's per-lane stack; stack_words: its LDS
-// words per lane at SLOTS slots.
+// kFields = LDS words per traversal frame (mesh: node, list|count, best t;
+// octree: children block, list|count, leaf mask|depth; grid: none). StackOf:
+// the adapter's per-lane stack; stack_words: its LDS words per lane at SLOTS
+// slots.
 // occupancy floors (min_waves below), overridable for A/B builds
 #ifndef RT_GRID_WAVES
 #define RT_GRID_WAVES 1
@@ -109,17 +108,14 @@ struct FrameArgs {
 #define RT_GENERAL_WAVES 4
 #endif
 template <class S, int B>
-using StackOf = LdsStack<B, S::kFields, S::kRec>;
+using StackOf = LdsStack<B, S::kFields>;
 template <class S, int SLOTS>
-constexpr int stack_words() { return lds_stack_words<SLOTS, S::kFields, S::kRec>(); }
-template <int F, int R>
-struct MeshSF {
-  static constexpr int kFields = F;
-  static constexpr int kRec = R;
+constexpr int stack_words() { return SLOTS * S::kFields; }
+struct MeshS {
+  static constexpr int kFields = 3;
   static constexpr bool kCoop = true;  // primary rays: wave-cooperative tail (mesh_primary_wave)
   static constexpr int kMinWaves = RT_MESH_WAVES;
   static constexpr int kQueueGroup = 2;  // wave tiles per work-queue item (render_persist_kernel)
-  static constexpr int kLdsNodes = RT_LDS_NODES;  // top-of-tree nodes per persistent block in LDS
   MeshDev d;
   // rays at or below which the wave hands its remaining rays to 8-lane groups
   // (wave-uniform; the persistent kernel raises it for a wave's last item)
@@ -133,7 +129,7 @@ struct MeshSF {
     float t;
     uint32_t k;
     Hit h = miss_hit();
-    if (mesh_primary_wave<B, kFields, kRec>(d, o, dir, tn, tf, active, stk, t, k, coop_rays, prio_iters) && active) {
+    if (mesh_primary_wave<B, kFields>(d, o, dir, tn, tf, active, stk, t, k, coop_rays, prio_iters) && active) {
       h.hit = true;
       h.t = t;
       h.n = tri_normal(d.tris, k);
@@ -143,28 +139,23 @@ struct MeshSF {
   }
   template <int B, class CT>
   __device__ __forceinline__ Hit intersect(f3 o, f3 dir, float tn, float tf,
-                                           LdsStack<B, kFields, kRec> st, CT &cnt) const {
+                                           LdsStack<B, kFields> st, CT &cnt) const {
     return mesh_intersect<B>(d, o, dir, tn, tf, st, cnt);
   }
   template <int B, class CT>
   __device__ __forceinline__ bool occluded(f3 o, f3 dir, float tn, float tf,
-                                           LdsStack<B, kFields, kRec> st, CT &cnt) const {
+                                           LdsStack<B, kFields> st, CT &cnt) const {
     return mesh_occluded<B>(d, o, dir, tn, tf, st, cnt);
   }
 };
-// the mesh adapter of a kernel with SLOTS stack slots
-template <int SLOTS>
-using MeshS = MeshSF<mesh_fields<SLOTS>(), mesh_rec<SLOTS>()>;
 template <int kMode>
 struct GridS {
   static constexpr int kFields = 1;  // no traversal stack (one unused LDS word per lane)
-  static constexpr int kRec = 0;
   static constexpr bool kCoop = false;
   static constexpr int kMinWaves = RT_GRID_WAVES;
   // block dispatch: a grid tile is too short for the queue's claims to pay
   // (256^3, 8 frames x 2 streams: 0.0506 ms/frame vs 0.0541 at 4 tiles per claim)
   static constexpr int kQueueGroup = 0;
-  static constexpr int kLdsNodes = 0;
   GridDev d;
   template <int B, class CT>
   __device__ __forceinline__ Hit intersect(f3 o, f3 dir, float tn, float tf,
@@ -182,11 +173,9 @@ struct GridS {
 template <bool PACK>
 struct OctS {
   static constexpr int kFields = kOctFields;
-  static constexpr int kRec = 0;
   static constexpr bool kCoop = false;
   static constexpr int kMinWaves = RT_OCT_WAVES;
   static constexpr int kQueueGroup = 2;
-  static constexpr int kLdsNodes = 0;
   OctDev d;
   template <int B, class CT>
   __device__ __forceinline__ Hit intersect(f3 o, f3 dir, float tn, float tf,
@@ -886,18 +875,6 @@ void render_persist_kernel(S sc_arg, PlaneDev pl, FrameBatch fb, PersistQ q) {
   __shared__ uint32_t stk[stack_words<S, SLOTS>() * kPBlock];
   S sc = sc_arg;
   if constexpr (S::kCoop && !GENERAL) sc.prio_iters = RT_HEAVY_PRIO;
-  if constexpr (S::kLdsNodes > 0 && !GENERAL) {
-    // the top BVH levels (the first inner nodes, BFS order) copied into this
-    // block's LDS once per launch; every item's traversal reads them there
-    constexpr int kQ = (int)(sizeof(rtl::GNode) / 16);
-    __shared__ float4 lnodes[S::kLdsNodes * kQ];
-    const uint32_t n = sc.d.n_inner < (uint32_t)S::kLdsNodes ? sc.d.n_inner : (uint32_t)S::kLdsNodes;
-    const float4 *src = reinterpret_cast<const float4 *>(sc.d.nodes);
-    for (uint32_t i = threadIdx.x; i < n * kQ; i += kPBlock) lnodes[i] = src[i];
-    __syncthreads();
-    sc.d.lnodes = reinterpret_cast<const rtl::GNode *>(lnodes);
-    sc.d.n_lds = n;
-  }
   const int lane = threadIdx.x & 63;
   const uint32_t xcc = __builtin_amdgcn_s_getreg(0x1814) & 7;  // HW_REG_XCC_ID: this wave's XCD
 #ifdef RT_PERSIST_STAMPS
@@ -1445,7 +1422,7 @@ __global__ __launch_bounds__(256) void brick_kernel(const float *__restrict__ sr
 }
 
 MeshDev mesh_dev(const rt_scene *s) {
-  MeshDev m{s->d_nodes, s->d_tris, s->root, {}, s->coop, s->n_inner, nullptr, 0, s->dmax2};
+  MeshDev m{s->d_nodes, s->d_tris, s->root, {}, s->coop, s->n_inner, s->dmax2};
   for (int k = 0; k < 6; ++k) m.rbox[k] = s->root_box[k];
   return m;
 }
@@ -1635,10 +1612,10 @@ int launch_render(rt_scene *s, const FrameArgs &fa_in, hipStream_t stream,
   if (s->kind == RT_SCENE_MESH) {
     const MeshDev md = mesh_dev(s);
     switch (s->maxd) {
-      case 4: launch_render_t<MeshS<4>, 4>(MeshS<4>{md}, s->plane, fa, general, stream, counters, diag); break;
-      case 7: launch_render_t<MeshS<7>, 7>(MeshS<7>{md}, s->plane, fa, general, stream, counters, diag); break;
-      case 15: launch_render_t<MeshS<15>, 15>(MeshS<15>{md}, s->plane, fa, general, stream, counters, diag); break;
-      default: launch_render_t<MeshS<31>, 31>(MeshS<31>{md}, s->plane, fa, general, stream, counters, diag); break;
+      case 4: launch_render_t<MeshS, 4>(MeshS{md}, s->plane, fa, general, stream, counters, diag); break;
+      case 7: launch_render_t<MeshS, 7>(MeshS{md}, s->plane, fa, general, stream, counters, diag); break;
+      case 15: launch_render_t<MeshS, 15>(MeshS{md}, s->plane, fa, general, stream, counters, diag); break;
+      default: launch_render_t<MeshS, 31>(MeshS{md}, s->plane, fa, general, stream, counters, diag); break;
     }
   } else if (s->kind == RT_SCENE_GRID) {
     const GridDev gd = grid_dev(s);
@@ -1961,10 +1938,10 @@ int launch_batch(rt_scene *s, FrameBatch &fb, int n, hipStream_t stream) {
   if (s->kind == RT_SCENE_MESH) {
     const MeshDev md = mesh_dev(s);
     switch (s->maxd) {
-      case 4: rc = launch_batch_t<MeshS<4>, 4>(s, MeshS<4>{md}, s->plane, fb, n, general, stream); break;
-      case 7: rc = launch_batch_t<MeshS<7>, 7>(s, MeshS<7>{md}, s->plane, fb, n, general, stream); break;
-      case 15: rc = launch_batch_t<MeshS<15>, 15>(s, MeshS<15>{md}, s->plane, fb, n, general, stream); break;
-      default: rc = launch_batch_t<MeshS<31>, 31>(s, MeshS<31>{md}, s->plane, fb, n, general, stream); break;
+      case 4: rc = launch_batch_t<MeshS, 4>(s, MeshS{md}, s->plane, fb, n, general, stream); break;
+      case 7: rc = launch_batch_t<MeshS, 7>(s, MeshS{md}, s->plane, fb, n, general, stream); break;
+      case 15: rc = launch_batch_t<MeshS, 15>(s, MeshS{md}, s->plane, fb, n, general, stream); break;
+      default: rc = launch_batch_t<MeshS, 31>(s, MeshS{md}, s->plane, fb, n, general, stream); break;
     }
   } else if (s->kind == RT_SCENE_GRID) {
     const GridDev gd = grid_dev(s);
@@ -3005,10 +2982,10 @@ int rt_intersect_rays(rt_scene *s, const float *o, const float *d, int64_t n, fl
     if (s->kind == RT_SCENE_MESH) {
       const MeshDev md = mesh_dev(s);
       switch (s->maxd) {
-        case 4: launch_rays_t<MeshS<4>, 4>(MeshS<4>{md}, s->plane, dO, dD, n, tnear, tfar, dH, dT, dN, dP); break;
-        case 7: launch_rays_t<MeshS<7>, 7>(MeshS<7>{md}, s->plane, dO, dD, n, tnear, tfar, dH, dT, dN, dP); break;
-        case 15: launch_rays_t<MeshS<15>, 15>(MeshS<15>{md}, s->plane, dO, dD, n, tnear, tfar, dH, dT, dN, dP); break;
-        default: launch_rays_t<MeshS<31>, 31>(MeshS<31>{md}, s->plane, dO, dD, n, tnear, tfar, dH, dT, dN, dP); break;
+        case 4: launch_rays_t<MeshS, 4>(MeshS{md}, s->plane, dO, dD, n, tnear, tfar, dH, dT, dN, dP); break;
+        case 7: launch_rays_t<MeshS, 7>(MeshS{md}, s->plane, dO, dD, n, tnear, tfar, dH, dT, dN, dP); break;
+        case 15: launch_rays_t<MeshS, 15>(MeshS{md}, s->plane, dO, dD, n, tnear, tfar, dH, dT, dN, dP); break;
+        default: launch_rays_t<MeshS, 31>(MeshS{md}, s->plane, dO, dD, n, tnear, tfar, dH, dT, dN, dP); break;
       }
     } else if (s->kind == RT_SCENE_GRID) {
       const GridDev gd = grid_dev(s);

@@ -60,11 +60,11 @@ struct MeshDev {
   // be fetched. Used only when all three 1/d components are finite.
   float rbox[6];
   bool coop;  // primary rays: cooperative tail enabled (diagnostic switch rtx_set_coop)
-  uint32_t n_inner;  // inner nodes (BFS order: the first ones are the top levels)
-  // top-of-tree copy in LDS (render_persist_kernel, RT_LDS_NODES): inner nodes
-  // [0, n_lds) are read from lnodes (a block's LDS), the rest from nodes
-  const rtl::GNode *lnodes;
-  uint32_t n_lds;
+  // inner nodes (BFS order: the first ones are the top levels). No kernel reads
+  // it at present; it keeps its place because without it the argument loads of
+  // coop and dmax2 merge and every mesh kernel's SGPR allocation shifts
+  // (profiles/r11/README.md): drop it in a pass that may move registers.
+  uint32_t n_inner;
   // rays with dot(d, d) <= dmax2 cannot make any triangle's |det| reach 2^125
   // (|det| <= 1.5 |e1| |e2| |d| in float arithmetic, max |e1| |e2| of the
   // scene measured at creation, mesh_dmax2): they take the triangle test with
@@ -72,40 +72,20 @@ struct MeshDev {
   float dmax2;
 };
 
-// Inner nodes of the top BVH levels kept in each persistent block's LDS (0:
-// off; A/B switch, e.g. 73 = the top three levels, 16 KiB per block). Node
-// reads then go through a per-lane choice of the LDS or the global copy (flat
-// loads). Bit-exact, and measured level to 1 % slower:
-// the vector L1 already serves 96-99 % of the node lines, so off.
-#ifndef RT_LDS_NODES
-#define RT_LDS_NODES 0
-#endif
-__device__ __forceinline__ const rtl::GNode *mesh_node(const MeshDev &sc, uint32_t i) {
-#if RT_LDS_NODES
-  return i < sc.n_lds ? sc.lnodes + i : sc.nodes + i;
-#else
-  return sc.nodes + i;
-#endif
-}
-
 // triangle_intersection (ray_pack.ispc:132-165) on one triangle already in
 // registers (v0, e1 = v1-v0, e2 = v2-v0; the subtractions are exact host-side
 // float ops, identical to the reference's). Returns t, or +inf on a miss.
 // FR (fast reciprocal): 1 / det as rtm::rcp_rn (rt_rcp.h), the same bits as
 // the division for every 1e-8 <= |det| < 2^126; taken by rays whose direction
 // keeps every |det| of the scene below 2^125 (MeshDev::dmax2; |det| < 1e-8 is
-// a miss below whatever inv_det is). RT_FAST_RCP=0: the division always (A/B
-// switch).
-#ifndef RT_FAST_RCP
-#define RT_FAST_RCP 1
-#endif
+// a miss below whatever inv_det is).
 template <bool FR>
 __device__ __forceinline__ float tri_t(float4 a, float4 b, float4 c, f3 o, f3 d) {
   const f3 v0{a.x, a.y, a.z}, e1{b.x, b.y, b.z}, e2{c.x, c.y, c.z};
   const f3 pvec = cross(d, e2);
   const float det = dot(e1, pvec);
   float inv_det;
-  if constexpr (FR && RT_FAST_RCP) {
+  if constexpr (FR) {
     inv_det = rtm::rcp_rn(det);
   } else {
     inv_det = 1 / det;
@@ -168,77 +148,32 @@ __device__ __forceinline__ void leaf_test(const rtl::GTri *__restrict__ tris, ui
 // Expand an inner node: slab-test its 8 children, sort8, keep t >= 0 entries
 // (a suffix of the sorted order) as a packed list of 3-bit ids + count. Also
 // returns the entry distance and child word of the first child to visit (the
-// child words arrive with the boxes: descending needs no extra load), and the
-// entry distance of the SECOND child in visit order and, with W2, its child
-// word (has2 = false when fewer than two are entered): the frame's record
-// keeps them, so resuming at that child needs no box reload (mesh_run).
-// 1: expand_node skips sort8 in waves whose rays all enter <= 2 children with
-// distinct t (A/B switch; 0 always runs the network)
-#ifndef RT_EXPAND_FAST
-#define RT_EXPAND_FAST 1
-#endif
-// The second-child record: per lane and per stack level (one level more than
-// the stack has slots: the top frame has one too) the entry distance of the
-// frame's second child in visit order and, in the two-word form, that child's
-// word, in LDS beside the frame stack (LdsStack::rec). The record of the frame
-// at stack depth d sits at level d - 1: the frame holds that level while it is
-// the top frame and keeps it once pushed, so the record is written once, where
-// the frame is created, and never moves; only a one-bit flag travels with the
-// frame. A resume at the second child then prunes without touching global
-// memory, or visits the child from the recorded word (two-word form) or after
-// loading just the 4-byte word (one-word form).
-// 2: both words for stacks of up to 4 slots, t alone for 7 slots (both would
-// not fit the CU's LDS at the kernel's waves). 1: t alone for up to 7 slots.
-// 0: no record, every resume reloads the child's box and recomputes the slab
-// test. Stacks deeper than 7 slots never take a record: their kernels are
-// LDS-limited. A/B switch, off: bit-exact and no kernel loses a wave, but on
-// the same tree the no-record build is 1.5 % (two words) and 1 % (one word)
-// faster on the bunny: the second select chain, the record's LDS traffic and
-// 16 B more scratch cost more than the saved round trips return (DESIGN.md
-// section 8, profiles/r10).
-#ifndef RT_MESH_T2
-#define RT_MESH_T2 0
-#endif
-// LDS words per stacked mesh frame: node, list | count << 24 | record flag
-// << 27, local best t
-template <int SLOTS>
-constexpr int mesh_fields() { return 3; }
-// words of a stack level's second-child record
-template <int SLOTS>
-constexpr int mesh_rec() { return (RT_MESH_T2 == 0 || SLOTS > 7) ? 0 : (RT_MESH_T2 >= 2 && SLOTS <= 4) ? 2 : 1; }
-// 1: where expand_node runs the sort8 network it reads the child words of the
-// first two children from the node again afterwards (two 4-byte loads of a
+// child words arrive with the boxes: descending needs no extra load).
+// FAST: waves whose rays all enter <= 2 children with distinct t skip sort8
+// and select the first child's word from the registers. Where the network
+// runs, the word is read from the node again afterwards (a 4-byte load of a
 // line just read) instead of keeping all 8 words in registers across the
 // network, where they spill at the mesh kernels' 5-wave floor. The reload
 // waits where the spilled words' scratch reloads waited, with fewer vector
 // memory instructions: the persistent 4-slot kernel goes from 52 to 24 B of
 // scratch per lane, the batch and one-frame kernels to none, and the bunny at
 // 10 frames x 2 streams from 0.0644 to 0.0625 ms/frame (DESIGN.md section 4,
-// round 10). Waves that skip the network select from the registers, as
-// before. 0: the words are selected from the registers everywhere (A/B
-// switch).
-#ifndef RT_EXPAND_RELOAD
-#define RT_EXPAND_RELOAD 1
-#endif
-// the child words of the first and (W2) second child in visit order
-template <bool W2>
-__device__ __forceinline__ void select_words(const uint32_t (&cws)[8], uint32_t first_id, uint32_t second_id,
-                                             uint32_t &cwfirst, uint32_t &cwsecond) {
-  uint32_t cf = cws[0], cs = cws[0];
+// round 10).
+// The child word of the first child in visit order: a select chain over the
+// 8 words. (They come in as the two loaded vectors: handed over as a
+// reference to an array, the compiler turned the chain into a load at a
+// selected address, and the array went to LDS and scratch.)
+__device__ __forceinline__ uint32_t select_word(uint4 cw0, uint4 cw1, uint32_t first_id) {
+  const uint32_t cws[8] = {cw0.x, cw0.y, cw0.z, cw0.w, cw1.x, cw1.y, cw1.z, cw1.w};
+  uint32_t cf = cws[0];
 #pragma unroll
   for (int c = 1; c < 8; ++c) cf = (first_id == (uint32_t)c) ? cws[c] : cf;
-  if constexpr (W2) {
-#pragma unroll
-    for (int c = 1; c < 8; ++c) cs = (second_id == (uint32_t)c) ? cws[c] : cs;
-  }
-  cwfirst = cf;
-  cwsecond = cs;
+  return cf;
 }
-template <bool FAST, bool W2 = false>
+template <bool FAST>
 __device__ __forceinline__ void expand_node(const rtl::GNode *__restrict__ node, f3 o, f3 inv,
                                             float tNear, float tFar, uint32_t &list,
-                                            uint32_t &cnt, float &tfirst, uint32_t &cwfirst,
-                                            float &tsecond, uint32_t &cwsecond, bool &has2) {
+                                            uint32_t &cnt, float &tfirst, uint32_t &cwfirst) {
   const float4 *p = reinterpret_cast<const float4 *>(node);
   float bx[48];
 #pragma unroll
@@ -248,7 +183,6 @@ __device__ __forceinline__ void expand_node(const rtl::GNode *__restrict__ node,
   }
   const uint4 cw0 = reinterpret_cast<const uint4 *>(node->child)[0];
   const uint4 cw1 = reinterpret_cast<const uint4 *>(node->child)[1];
-  const uint32_t cws[8] = {cw0.x, cw0.y, cw0.z, cw0.w, cw1.x, cw1.y, cw1.z, cw1.w};
   float t[8];
   uint32_t id[8];
 #pragma unroll
@@ -257,9 +191,8 @@ __device__ __forceinline__ void expand_node(const rtl::GNode *__restrict__ node,
                       bx[6 * c + 5], o, inv, tNear, tFar);  // box: xMin xMax yMin yMax zMin zMax
     id[c] = (uint32_t)c;
   }
-  uint32_t first_id = 0, second_id = 0;
   bool sorted = false;
-  if constexpr (FAST && RT_EXPAND_FAST) {
+  if constexpr (FAST) {
     // At most two children entered with distinct t: the network's output order
     // of the entered children is plain ascending t (any correct sort gives
     // it), so the wave skips sort8 when every lane is in that case. Ties (or
@@ -280,63 +213,45 @@ __device__ __forceinline__ void expand_node(const rtl::GNode *__restrict__ node,
     if (__ballot(slow) == 0) {
       sorted = true;
       const bool sw = pc == 2 && tb < ta;
-      first_id = sw ? ib : ia;
-      second_id = sw ? ia : ib;
       tfirst = pc == 0 ? 0.0f : (sw ? tb : ta);
       cnt = pc;
-      tsecond = sw ? ta : tb;
       list = pc == 0 ? 0u : pc == 1 ? ia : (sw ? (ib | (ia << 3)) : (ia | (ib << 3)));
-      if constexpr (RT_EXPAND_RELOAD != 0) select_words<W2>(cws, first_id, second_id, cwfirst, cwsecond);
+      cwfirst = select_word(cw0, cw1, sw ? ib : ia);
     }
   }
   if (!sorted) {
     sort8(t, id);
+    uint32_t first_id = 0;
     list = 0;
     cnt = 0;
     tfirst = 0.0f;
-    tsecond = 0.0f;
 #pragma unroll
     for (int i = 7; i >= 0; --i) {  // build from the back so the first visit ends in the low bits
       if (!(t[i] < 0.0f)) {
         list = (list << 3) | id[i];
         cnt += 1;
-        tsecond = tfirst;
         tfirst = t[i];
-        second_id = first_id;
         first_id = id[i];
       }
     }
-    if constexpr (RT_EXPAND_RELOAD != 0) {
-      // the words of the two children, read again now that the order is known
-      // (the node's line is in the L1): the 8 words need not stay in
-      // registers across the network
-      cwfirst = node->child[first_id];
-      cwsecond = W2 ? node->child[second_id] : 0u;
-    }
+    // the first child's word, read again now that the order is known (the
+    // node's line is in the L1): the 8 words need not stay in registers
+    // across the network
+    cwfirst = node->child[first_id];
   }
-  if constexpr (RT_EXPAND_RELOAD == 0) select_words<W2>(cws, first_id, second_id, cwfirst, cwsecond);
-  has2 = cnt >= 2;
 }
 
-// A stack level is R record words (the mesh's second-child record, mesh_rec)
-// followed by the F words of the frame slot. The deepest top frame has a
-// record and no slot, so a stack of SLOTS slots takes lds_stack_words words
-// per lane: SLOTS whole levels and the records of level SLOTS.
-template <int BLOCK, int F = 3, int R = 0>
+// A lane's stack: slots of F words each (a stack of SLOTS slots takes
+// SLOTS * F words per lane).
+template <int BLOCK, int F = 3>
 struct LdsStack {
-  uint32_t *base;  // lane-interleaved words, R + F words per level
+  uint32_t *base;  // lane-interleaved words, F words per slot
   __device__ __forceinline__ uint32_t &at(int slot, int field) {
-    // slot * (R + F) * BLOCK as a full-rate 24-bit multiply (slots are small):
-    // the plain form compiles to the quarter-rate v_mul_lo_u32
-    return base[__umul24((uint32_t)slot, (uint32_t)((R + F) * BLOCK)) + (uint32_t)((R + field) * BLOCK)];
-  }
-  // record word i of `level` (0 .. SLOTS)
-  __device__ __forceinline__ uint32_t &rec(int level, int i) {
-    return base[__umul24((uint32_t)level, (uint32_t)((R + F) * BLOCK)) + (uint32_t)(i * BLOCK)];
+    // slot * F * BLOCK as a full-rate 24-bit multiply (slots are small): the
+    // plain form compiles to the quarter-rate v_mul_lo_u32
+    return base[__umul24((uint32_t)slot, (uint32_t)(F * BLOCK)) + (uint32_t)(field * BLOCK)];
   }
 };
-template <int SLOTS, int F, int R = 0>
-constexpr int lds_stack_words() { return SLOTS * (R + F) + R; }
 
 // ANY = true: shadow-ray query, stop at the first leaf hit (only hitten is used).
 // Slab test of the root union box: true iff the ray certainly misses it.
@@ -355,13 +270,12 @@ __device__ __forceinline__ bool root_box_miss(const float *b, f3 o, f3 inv, floa
 // Root stage of BVHBuilder::traverseNode(0): the union-box pretest and the
 // root's 8-child expansion (wave-uniform node: scalar loads). Returns false if
 // the traversal ends here (no child entered); otherwise the root frame.
-template <bool FAST = false, bool W2 = false, class CT>
+template <bool FAST = false, class CT>
 __device__ __forceinline__ bool mesh_root(const MeshDev &sc, f3 o, f3 inv, float tNear, float tFar,
-                                          uint32_t &l, uint32_t &c, float &tf, uint32_t &cwf,
-                                          float &ts, uint32_t &cws, bool &has2, CT &cnt) {
+                                          uint32_t &l, uint32_t &c, float &tf, uint32_t &cwf, CT &cnt) {
   cnt.add(C_BVH_INNER, 1);
   if (root_box_miss(sc.rbox, o, inv, tNear, tFar)) return false;
-  expand_node<FAST, W2>(sc.nodes + sc.root, o, inv, tNear, tFar, l, c, tf, cwf, ts, cws, has2);
+  expand_node<FAST>(sc.nodes + sc.root, o, inv, tNear, tFar, l, c, tf, cwf);
   return c != 0;
 }
 
@@ -380,14 +294,7 @@ struct MState {
   float gbest;      // best t so far
   int32_t depth;    // frames on the stack, incl. the top one
   bool have_t;
-  bool t2v;         // the next child of the top frame is its second and the frame's record holds it
 };
-
-// Frame ends by pruning handled per traversal iteration (1: one; the next
-// iteration pops the ended frame; A/B switch)
-#ifndef RT_MESH_PRUNE_PASSES
-#define RT_MESH_PRUNE_PASSES 1
-#endif
 
 // Rays still looping in a wave at or below which the primary mesh path hands
 // its remaining rays to 8-lane groups (mesh_run_coop).
@@ -407,21 +314,15 @@ constexpr int kCoopRays = RT_COOP_RAYS;
 
 // Primary mesh traversal (MAJ, mesh_primary_wave): an iteration whose lanes
 // split between leaf tests and inner expansions runs only the side with more
-// lanes -- the lanes of the side with fewer than 1/K as many wait one
-// iteration, their visit order unchanged -- so the wave mostly runs one of the
-// two branches per iteration instead of both. Modelled first on the CPU
+// lanes -- the lanes of the side with fewer wait one iteration, their visit
+// order unchanged -- so the wave mostly runs one of the two branches per
+// iteration instead of both. Modelled first on the CPU
 // (tools/trav_sim.cpp, bunny 1080p: 38 % of the kernel's iterations ran both
-// branches; waiting at K = 1 takes 14 % of the wave instructions for 15 % more
+// branches; waiting takes 14 % of the wave instructions for 15 % more
 // iterations), then measured (section 4, round 6): bunny 10 x 2 0.0808 /
-// 0.0800 -> 0.0777 / 0.0776, one frame 0.1806 -> 0.1594 / 0.1588 ms/frame. K =
-// 2 was level; the shading kernels (MAJ off) were ~2 % slower with it.
-// RT_MESH_MAJ = K (0: off everywhere; A/B switch).
-#ifndef RT_MESH_MAJ
-#define RT_MESH_MAJ 1
-#endif
-#ifndef RT_MESH_MAJ_DEN  // K = RT_MESH_MAJ / RT_MESH_MAJ_DEN
-#define RT_MESH_MAJ_DEN 1
-#endif
+// 0.0800 -> 0.0777 / 0.0776, one frame 0.1806 -> 0.1594 / 0.1588 ms/frame.
+// Waiting only below a 2 : 1 split was level; the shading kernels (MAJ off)
+// were ~2 % slower with it.
 
 // The traversal loop. One iteration = one unit of this lane's work (expand a
 // node, test a leaf, or resume/pop a frame). (Measured and rejected: the
@@ -429,25 +330,15 @@ constexpr int kCoopRays = RT_COOP_RAYS;
 // 0.342 -> 0.523 ms.) TAIL: before each iteration, if kCoopRays or fewer lanes
 // of the wave are still looping, store the state and return true (suspended).
 //
-// Resuming a frame (R > 0 record words, mesh_rec): a frame's first child is
-// visited from the expansion's registers; its second child's entry t and, with
-// R = 2, child word are in the frame's record (LDS level depth - 1, written
-// where the frame is created; the flag t2v, bit 27 of word 1 once the frame is
-// stacked, says the next child is that one). A resume at the second child
-// reads t from the record: pruned, the frame ends without a global load and
-// the next iteration pops it; entered, the child word comes from the record
-// (R = 2) or from a 4-byte load (R = 1). Third and later children reload their
-// box and child word and redo the slab test. The recorded bits are those the
-// slab test returned at expansion: the same function of the same node and
-// ray, so the same decision (a NaN stays a NaN: visited).
-template <int BLOCK, bool ANY, bool FAST, bool TAIL, uint32_t LB = RT_LEAF_BATCH, bool MAJ = false, int F, int R, class CT>
+// Resuming a frame: its first child is visited from the expansion's registers;
+// every later child reloads its box and child word and redoes the slab test.
+template <int BLOCK, bool ANY, bool FAST, bool TAIL, uint32_t LB = RT_LEAF_BATCH, bool MAJ = false, int F, class CT>
 __device__ __forceinline__ bool mesh_run(const MeshDev &sc, f3 o, f3 d, f3 inv, float tNear, float tFar,
-                                         LdsStack<BLOCK, F, R> st, MState &S, CT &cnt, int coop_rays = kCoopRays,
+                                         LdsStack<BLOCK, F> st, MState &S, CT &cnt, int coop_rays = kCoopRays,
                                          int prio_iters = 0) {
   uint32_t word = S.word, flist = S.flist, fcnt = S.fcnt, fnode = S.fnode, gk = S.gk;
   float fbest = S.fbest, gbest = S.gbest;
   int depth = S.depth;
-  bool t2v = S.t2v;
   bool suspended = false;
   int it = 0;  // wave-uniform iteration count (prio_iters)
   // A fresh frame handed in (S.have_t): its first child is chosen here, as the
@@ -472,7 +363,6 @@ __device__ __forceinline__ bool mesh_run(const MeshDev &sc, f3 o, f3 d, f3 inv, 
     fcnt = (lc >> 24) & 7u;  // a stacked frame has 1..7 children left
     fbest = __uint_as_float(st.at(depth - 1, 2));
     if (child_best < fbest) fbest = child_best;
-    t2v = R > 0 && ((lc >> 27) & 1u) != 0;
   };
   for (;;) {
     if (TAIL && __popcll(__ballot(1)) <= coop_rays) { suspended = true; break; }
@@ -480,20 +370,18 @@ __device__ __forceinline__ bool mesh_run(const MeshDev &sc, f3 o, f3 d, f3 inv, 
       it = __builtin_amdgcn_readfirstlane(it + 1);
       if (it == prio_iters) __builtin_amdgcn_s_setprio(RT_HEAVY_PRIO_LEVEL);
     }
-#if RT_MESH_MAJ
     if constexpr (MAJ && !ANY) {
-      // one branch per iteration where the lanes disagree by more than K to 1:
-      // the minority side's lanes wait (their visit order is unchanged, only
-      // later), so the wave runs the leaf test or the expansion, not both
+      // one branch per iteration where the lanes disagree: the minority side's
+      // lanes wait (their visit order is unchanged, only later), so the wave
+      // runs the leaf test or the expansion, not both
       const bool isL = word != rtl::kInvalidChild && (word & rtl::kLeafBit);
       const bool isI = word != rtl::kInvalidChild && !(word & rtl::kLeafBit);
       const uint32_t nL = (uint32_t)__popcll(__ballot(isL)), nI = (uint32_t)__popcll(__ballot(isI));
       // wave-uniform: at most one side waits, so every iteration advances
-      const bool waitL = nL * RT_MESH_MAJ < nI * RT_MESH_MAJ_DEN;
-      const bool waitI = !waitL && nI * RT_MESH_MAJ < nL * RT_MESH_MAJ_DEN;
+      const bool waitL = nL < nI;
+      const bool waitI = !waitL && nI < nL;
       if ((isL && waitL) || (isI && waitI)) continue;
     }
-#endif
     // a frame expanded in this iteration: its first child's entry t and word
     bool have_t = false;
     float tnext = 0.0f;
@@ -509,11 +397,10 @@ __device__ __forceinline__ bool mesh_run(const MeshDev &sc, f3 o, f3 d, f3 inv, 
           if (lt < gbest) { gbest = lt; gk = lk; }
         }
       } else {
-        uint32_t l, c, cwf, cws;
-        float tf, ts;
-        bool has2;
+        uint32_t l, c, cwf;
+        float tf;
         cnt.add(C_BVH_INNER, 1);
-        expand_node<FAST, R >= 2>(mesh_node(sc, word), o, inv, tNear, tFar, l, c, tf, cwf, ts, cws, has2);
+        expand_node<FAST>(sc.nodes + word, o, inv, tNear, tFar, l, c, tf, cwf);
         if (c != 0) {
           if (depth >= 1 && fcnt == 0) {
             // tail call: the top frame has no child left, so it is replaced,
@@ -527,7 +414,7 @@ __device__ __forceinline__ bool mesh_run(const MeshDev &sc, f3 o, f3 d, f3 inv, 
           } else {
             if (depth >= 1) {
               st.at(depth - 1, 0) = fnode;
-              st.at(depth - 1, 1) = flist | (fcnt << 24) | (R > 0 ? (uint32_t)t2v << 27 : 0u);
+              st.at(depth - 1, 1) = flist | (fcnt << 24);
               st.at(depth - 1, 2) = __float_as_uint(fbest);
             }
             ++depth;
@@ -536,68 +423,47 @@ __device__ __forceinline__ bool mesh_run(const MeshDev &sc, f3 o, f3 d, f3 inv, 
           tnext = tf;
           cwnext = cwf;
           have_t = true;
-          // the new frame's record, at the level it keeps for its lifetime
-          if constexpr (R >= 1) st.rec(depth - 1, 0) = __float_as_uint(ts);
-          if constexpr (R >= 2) st.rec(depth - 1, 1) = cws;
-          t2v = R > 0 && has2;
         }
       }
       word = rtl::kInvalidChild;
     }
-    // choose the next child; a pruned child ends its frame. A pop first, where
-    // the top frame has ended; then the child's entry t and word: from the
-    // expansion's registers (a fresh frame's first child), from the frame's
-    // record (its second child: LDS reads, and with a one-word record the
-    // 4-byte child word of a child that is entered), or from the child's box
-    // and word, reloaded. After an end decided from a reloaded box, up to
-    // RT_MESH_PRUNE_PASSES - 1 more such rounds follow in this iteration.
-    bool done = false;
-    for (int pass = 0; pass < RT_MESH_PRUNE_PASSES; ++pass) {
-      if (depth == 0) { done = true; break; }
-      if (fcnt == 0) {  // frame done: fold its best into the parent frame
-        if (depth == 1) { depth = 0; done = true; break; }
-        pop();
-        have_t = false;
-        // stacked frames always have a child left: go on to it
-      }
-      const uint32_t j = flist & 7u;
-      flist >>= 3;
-      fcnt -= 1;
-      if (!have_t) {  // (a fresh frame's first child is in tnext, cwnext)
-        if (R > 0 && t2v) {  // the recorded bits are the ones this slab test would return again
-          t2v = false;
-          tnext = __uint_as_float(st.rec(depth - 1, 0));
-          if constexpr (R >= 2) cwnext = st.rec(depth - 1, 1);
-          else if (!(fbest < tnext)) cwnext = mesh_node(sc, fnode)->child[j];
-        } else {
-          const rtl::GNode *nd = mesh_node(sc, fnode);
-          float b[6];
-          cwnext = nd->child[j];
-#pragma unroll
-          for (int i = 0; i < 6; ++i) b[i] = nd->box[j][i];
-          tnext = slab<FAST>(b[0], b[2], b[4], b[1], b[3], b[5], o, inv, tNear, tFar);
-        }
-      }
+    // choose the next child; a pruned child ends its frame (the next
+    // iteration pops it). A pop first, where the top frame has ended; then the
+    // child's entry t and word: from the expansion's registers (a fresh
+    // frame's first child) or from the child's box and word, reloaded.
+    if (depth == 0) break;
+    if (fcnt == 0) {  // frame done: fold its best into the parent frame
+      if (depth == 1) { depth = 0; break; }
+      pop();
       have_t = false;
-      if (!(fbest < tnext)) { word = cwnext; break; }
-      fcnt = 0;  // pruned; later siblings have larger t
+      // stacked frames always have a child left: go on to it
     }
-    if (done) break;
+    const uint32_t j = flist & 7u;
+    flist >>= 3;
+    fcnt -= 1;
+    if (!have_t) {  // (a fresh frame's first child is in tnext, cwnext)
+      const rtl::GNode *nd = sc.nodes + fnode;
+      float b[6];
+      cwnext = nd->child[j];
+#pragma unroll
+      for (int i = 0; i < 6; ++i) b[i] = nd->box[j][i];
+      tnext = slab<FAST>(b[0], b[2], b[4], b[1], b[3], b[5], o, inv, tNear, tFar);
+    }
+    if (!(fbest < tnext)) { word = cwnext; continue; }
+    fcnt = 0;  // pruned; later siblings have larger t
   }
   S.word = word; S.flist = flist; S.fcnt = fcnt; S.fnode = fnode; S.gk = gk;
   S.fbest = fbest; S.gbest = gbest; S.depth = depth;
-  S.t2v = t2v;
   return suspended;
 }
 
-// (t2v: the root frame's record, level 0 of st, holds its second child)
-template <int BLOCK, bool ANY, bool FAST = false, int F, int R, class CT>
+template <int BLOCK, bool ANY, bool FAST = false, int F, class CT>
 __device__ __forceinline__ bool mesh_continue(const MeshDev &sc, f3 o, f3 d, f3 inv, float tNear,
-                                              float tFar, LdsStack<BLOCK, F, R> st, uint32_t word,
+                                              float tFar, LdsStack<BLOCK, F> st, uint32_t word,
                                               uint32_t flist, uint32_t fcnt, float tnext,
-                                              uint32_t cwnext, bool have_t, bool t2v, int depth,
+                                              uint32_t cwnext, bool have_t, int depth,
                                               float &out_t, uint32_t &out_k, CT &cnt) {
-  MState S{word, flist, fcnt, sc.root, cwnext, rtl::kInvalidChild, kInf, tnext, kInf, depth, have_t, t2v};
+  MState S{word, flist, fcnt, sc.root, cwnext, rtl::kInvalidChild, kInf, tnext, kInf, depth, have_t};
   mesh_run<BLOCK, ANY, FAST, false>(sc, o, d, inv, tNear, tFar, st, S, cnt);
   out_t = S.gbest;
   out_k = S.gk;
@@ -689,16 +555,16 @@ __device__ __forceinline__ uint32_t grp_or(uint32_t v, int k) {
 }
 
 // mesh_run (non-ANY) executed by an 8-lane group on one ray; S is the same in
-// all 8 lanes and stays so. st = the owner lane's LDS stack column.
-// The group reads the records the per-lane loop wrote into that column and
-// writes its own frames' there (all 8 lanes store the same words).
-template <int BLOCK, bool FAST, int F, int R>
+// all 8 lanes and stays so. st = the owner lane's LDS stack column: the group
+// reads the frames the per-lane loop stacked there and stacks its own (all 8
+// lanes store the same words).
+template <int BLOCK, bool FAST, int F>
 __device__ __forceinline__ void mesh_run_coop(const MeshDev &sc, f3 o, f3 d, f3 inv, float tNear,
-                                              float tFar, LdsStack<BLOCK, F, R> st, MState &S, int k) {
+                                              float tFar, LdsStack<BLOCK, F> st, MState &S, int k) {
   uint32_t word = S.word, flist = S.flist, fcnt = S.fcnt, fnode = S.fnode, cwnext = S.cwnext, gk = S.gk;
   float fbest = S.fbest, tnext = S.tnext, gbest = S.gbest;
   int depth = S.depth;
-  bool have_t = S.have_t, t2v = S.t2v;
+  bool have_t = S.have_t;
   const int gbase = (threadIdx.x & 63) & ~7;
   for (;;) {
     if (word != rtl::kInvalidChild) {
@@ -718,7 +584,7 @@ __device__ __forceinline__ void mesh_run_coop(const MeshDev &sc, f3 o, f3 d, f3 
           if (tk < gbest) { gbest = tk; gk = first + kk; }
         }
       } else {
-        const rtl::GNode *nd = mesh_node(sc, word);
+        const rtl::GNode *nd = sc.nodes + word;
         const float2 *bp = reinterpret_cast<const float2 *>(nd->box[k]);
         const float2 bxx = bp[0], byy = bp[1], bzz = bp[2];  // (min, max) per axis
         const uint32_t cwk = nd->child[k];
@@ -732,14 +598,6 @@ __device__ __forceinline__ void mesh_run_coop(const MeshDev &sc, f3 o, f3 d, f3 
         const float tf = __shfl(t, gbase + (int)(i0 & 7u), 64);
         const uint32_t idf = __shfl(id, gbase + (int)(i0 & 7u), 64);
         const uint32_t cwf = __shfl(cwk, gbase + (int)idf, 64);
-        // the second child's entry t and word (the next entry of the sorted order)
-        float ts = 0.0f;
-        uint32_t cws = 0;
-        if constexpr (R >= 1) ts = __shfl(t, gbase + (int)((i0 + 1u) & 7u), 64);
-        if constexpr (R >= 2) {
-          const uint32_t ids = __shfl(id, gbase + (int)((i0 + 1u) & 7u), 64);
-          cws = __shfl(cwk, gbase + (int)ids, 64);
-        }
         if (c != 0) {
           if (depth >= 1 && fcnt == 0) {  // tail call, as in mesh_run
             if (depth >= 2) {
@@ -749,7 +607,7 @@ __device__ __forceinline__ void mesh_run_coop(const MeshDev &sc, f3 o, f3 d, f3 
           } else {
             if (depth >= 1) {
               st.at(depth - 1, 0) = fnode;
-              st.at(depth - 1, 1) = flist | (fcnt << 24) | (R > 0 ? (uint32_t)t2v << 27 : 0u);
+              st.at(depth - 1, 1) = flist | (fcnt << 24);
               st.at(depth - 1, 2) = __float_as_uint(fbest);
             }
             ++depth;
@@ -758,9 +616,6 @@ __device__ __forceinline__ void mesh_run_coop(const MeshDev &sc, f3 o, f3 d, f3 
           tnext = tf;
           cwnext = cwf;
           have_t = true;
-          if constexpr (R >= 1) st.rec(depth - 1, 0) = __float_as_uint(ts);
-          if constexpr (R >= 2) st.rec(depth - 1, 1) = cws;
-          t2v = R > 0 && c >= 2;
         }
       }
       word = rtl::kInvalidChild;
@@ -777,22 +632,14 @@ __device__ __forceinline__ void mesh_run_coop(const MeshDev &sc, f3 o, f3 d, f3 
       fbest = __uint_as_float(st.at(depth - 1, 2));
       if (child_best < fbest) fbest = child_best;
       have_t = false;
-      t2v = R > 0 && ((lc >> 27) & 1u) != 0;
     }
     const uint32_t j = flist & 7u;
     flist >>= 3;
     fcnt -= 1;
     if (have_t) {
       have_t = false;
-    } else if (R > 0 && t2v) {  // second child: the frame's record, as in mesh_run
-      t2v = false;
-      tnext = __uint_as_float(st.rec(depth - 1, 0));
-      if (fbest < tnext) { fcnt = 0; continue; }
-      if constexpr (R >= 2) word = st.rec(depth - 1, 1);
-      else word = mesh_node(sc, fnode)->child[j];
-      continue;
     } else {
-      const rtl::GNode *nd = mesh_node(sc, fnode);
+      const rtl::GNode *nd = sc.nodes + fnode;
       const float *b = nd->box[j];
       cwnext = nd->child[j];
       tnext = slab<FAST>(b[0], b[2], b[4], b[1], b[3], b[5], o, inv, tNear, tFar);
@@ -808,8 +655,7 @@ __device__ __forceinline__ void mesh_run_coop(const MeshDev &sc, f3 o, f3 d, f3 
 // call it, with active = false for lanes without a pixel): each lane traverses
 // its own ray until at most kCoopRays rays remain, then those finish in 8-lane
 // groups. The result is the same as mesh_trace's, bit for bit.
-// (RW: the record words of a stack level, R elsewhere)
-template <int BLOCK, int F, int RW>
+template <int BLOCK, int F>
 __device__ __forceinline__ bool mesh_primary_wave(const MeshDev &sc, f3 o, f3 d, float tNear, float tFar,
                                                   bool active, uint32_t *stk_block, float &out_t,
                                                   uint32_t &out_k, int coop_rays = kCoopRays,
@@ -817,30 +663,25 @@ __device__ __forceinline__ bool mesh_primary_wave(const MeshDev &sc, f3 o, f3 d,
   if (prio_iters > 0) __builtin_amdgcn_s_setprio(0);  // a new tile starts at normal priority
   NoCnt cnt;
   const int lane = threadIdx.x & 63;
-  LdsStack<BLOCK, F, RW> st{stk_block + threadIdx.x};
+  LdsStack<BLOCK, F> st{stk_block + threadIdx.x};
   const f3 inv{1.0f / d.x, 1.0f / d.y, 1.0f / d.z};  // 1.0f / rayDir (:273)
   // fast: the finite-1/d slab forms and the fast reciprocal (MeshDev::dmax2)
   const bool fast = __builtin_isfinite(inv.x) && __builtin_isfinite(inv.y) && __builtin_isfinite(inv.z) &&
                     dot(d, d) <= sc.dmax2;
   MState S{rtl::kInvalidChild, 0u, 0u, sc.root, rtl::kInvalidChild, rtl::kInvalidChild, kInf, 0.0f, kInf, 0,
-           false, false};
+           false};
   bool pending = false;
   if (active && sc.root != rtl::kInvalidChild) {
     if (sc.root & rtl::kLeafBit) {
       S.word = sc.root;
       pending = true;
     } else {
-      uint32_t l, c, cwf, cws;
-      float tf, ts;
-      bool has2;
-      const bool entered = fast ? mesh_root<true, RW >= 2>(sc, o, inv, tNear, tFar, l, c, tf, cwf, ts, cws, has2, cnt)
-                                : mesh_root<false, RW >= 2>(sc, o, inv, tNear, tFar, l, c, tf, cwf, ts, cws, has2, cnt);
+      uint32_t l, c, cwf;
+      float tf;
+      const bool entered = fast ? mesh_root<true>(sc, o, inv, tNear, tFar, l, c, tf, cwf, cnt)
+                                : mesh_root<false>(sc, o, inv, tNear, tFar, l, c, tf, cwf, cnt);
       if (entered) {
         S.flist = l; S.fcnt = c; S.tnext = tf; S.cwnext = cwf; S.depth = 1; S.have_t = true;
-        // the root frame's record
-        if constexpr (RW >= 1) st.rec(0, 0) = __float_as_uint(ts);
-        if constexpr (RW >= 2) st.rec(0, 1) = cws;
-        S.t2v = RW > 0 && has2;
         pending = true;
       }
     }
@@ -889,9 +730,8 @@ __device__ __forceinline__ bool mesh_primary_wave(const MeshDev &sc, f3 o, f3 d,
     G.gbest = __shfl(S.gbest, owner, 64);
     G.depth = __shfl(S.depth, owner, 64);
     G.have_t = __shfl((int)S.have_t, owner, 64) != 0;
-    G.t2v = __shfl((int)S.t2v, owner, 64) != 0;
     if (g < n) {
-      const LdsStack<BLOCK, F, RW> gst{stk_block + (threadIdx.x & ~63) + owner};
+      const LdsStack<BLOCK, F> gst{stk_block + (threadIdx.x & ~63) + owner};
       if (gfast)
         mesh_run_coop<BLOCK, true>(sc, go, gd, ginv, tNear, gtf, gst, G, k);
       else
@@ -908,38 +748,31 @@ __device__ __forceinline__ bool mesh_primary_wave(const MeshDev &sc, f3 o, f3 d,
   return S.gk != rtl::kInvalidChild;
 }
 
-template <int BLOCK, bool ANY, int F, int R, class CT>
+template <int BLOCK, bool ANY, int F, class CT>
 __device__ __forceinline__ bool mesh_trace(const MeshDev &sc, f3 o, f3 d, float tNear, float tFar,
-                                           LdsStack<BLOCK, F, R> st, float &out_t, uint32_t &out_k,
+                                           LdsStack<BLOCK, F> st, float &out_t, uint32_t &out_k,
                                            CT &cnt) {
   const f3 inv{1.0f / d.x, 1.0f / d.y, 1.0f / d.z};  // 1.0f / rayDir (:273)
   if (sc.root == rtl::kInvalidChild) return false;
   if (sc.root & rtl::kLeafBit)
     return mesh_continue<BLOCK, ANY>(sc, o, d, inv, tNear, tFar, st, sc.root, 0u, 0u, 0.0f,
-                                     rtl::kInvalidChild, false, false, 0, out_t, out_k, cnt);
-  uint32_t l, c, cwf, cws;
-  float tf, ts;
-  bool has2;
-  // the root frame's record (level 0)
-  const auto record = [&]() {
-    if constexpr (R >= 1) st.rec(0, 0) = __float_as_uint(ts);
-    if constexpr (R >= 2) st.rec(0, 1) = cws;
-    return R > 0 && has2;
-  };
+                                     rtl::kInvalidChild, false, 0, out_t, out_k, cnt);
+  uint32_t l, c, cwf;
+  float tf;
   if (__builtin_isfinite(inv.x) && __builtin_isfinite(inv.y) && __builtin_isfinite(inv.z) &&
       dot(d, d) <= sc.dmax2) {  // (see mesh_primary_wave)
-    if (!mesh_root<true, R >= 2>(sc, o, inv, tNear, tFar, l, c, tf, cwf, ts, cws, has2, cnt)) return false;
+    if (!mesh_root<true>(sc, o, inv, tNear, tFar, l, c, tf, cwf, cnt)) return false;
     return mesh_continue<BLOCK, ANY, true>(sc, o, d, inv, tNear, tFar, st, rtl::kInvalidChild, l, c, tf,
-                                           cwf, true, record(), 1, out_t, out_k, cnt);
+                                           cwf, true, 1, out_t, out_k, cnt);
   }
-  if (!mesh_root<false, R >= 2>(sc, o, inv, tNear, tFar, l, c, tf, cwf, ts, cws, has2, cnt)) return false;
+  if (!mesh_root<false>(sc, o, inv, tNear, tFar, l, c, tf, cwf, cnt)) return false;
   return mesh_continue<BLOCK, ANY, false>(sc, o, d, inv, tNear, tFar, st, rtl::kInvalidChild, l, c, tf,
-                                          cwf, true, record(), 1, out_t, out_k, cnt);
+                                          cwf, true, 1, out_t, out_k, cnt);
 }
 
-template <int BLOCK, int F, int R, class CT>
+template <int BLOCK, int F, class CT>
 __device__ __forceinline__ Hit mesh_intersect(const MeshDev &sc, f3 o, f3 d, float tNear, float tFar,
-                                              LdsStack<BLOCK, F, R> st, CT &cnt) {
+                                              LdsStack<BLOCK, F> st, CT &cnt) {
   float t;
   uint32_t k;
   Hit h = miss_hit();
@@ -951,9 +784,9 @@ __device__ __forceinline__ Hit mesh_intersect(const MeshDev &sc, f3 o, f3 d, flo
   }
   return h;
 }
-template <int BLOCK, int F, int R, class CT>
+template <int BLOCK, int F, class CT>
 __device__ __forceinline__ bool mesh_occluded(const MeshDev &sc, f3 o, f3 d, float tNear, float tFar,
-                                              LdsStack<BLOCK, F, R> st, CT &cnt) {
+                                              LdsStack<BLOCK, F> st, CT &cnt) {
   float t;
   uint32_t k;
   return mesh_trace<BLOCK, true>(sc, o, d, tNear, tFar, st, t, k, cnt);
@@ -976,15 +809,6 @@ __device__ __forceinline__ bool mesh_occluded(const MeshDev &sc, f3 o, f3 d, flo
 //    lines and neighbouring lanes and steps share them (256^3 grid, 1080p:
 //    0.0646 -> 0.0507 ms per frame). The padding up to a multiple of 4 per
 //    axis is never read (taps are at most size-1).
-#ifndef RT_GRID_TAP_CACHE
-#define RT_GRID_TAP_CACHE 1  // A/B switch: 0 reloads the 8 taps at every march step
-#endif
-#ifndef RT_GRID_MUL24
-#define RT_GRID_MUL24 1  // A/B switch: 0 keeps 32-bit multiplies in the tap addressing
-#endif
-#ifndef RT_GRID_MARCH
-#define RT_GRID_MARCH 1  // A/B switch: 1 the march as a one-exit loop (grid_march), 0 the two-exit form
-#endif
 constexpr uint32_t kBrick = 4;
 constexpr uint64_t kGridLinearMaxBytes = 4ull << 20;
 struct GridDev {
@@ -1010,7 +834,7 @@ constexpr int kGridBuf = 1, kGridBricked = 2;
 // VALU-bound (four of them per sdf evaluation).
 template <int kMode>
 __device__ __forceinline__ uint32_t grid_mul(uint32_t a, uint32_t b) {
-  if constexpr ((kMode & kGridBuf) != 0 && RT_GRID_MUL24) return __umul24(a, b);
+  if constexpr ((kMode & kGridBuf) != 0) return __umul24(a, b);
   return a * b;
 }
 // sample offsets of coordinate i along each axis (their sum addresses sample (x, y, z))
@@ -1151,7 +975,6 @@ __device__ __forceinline__ bool grid_march(const GridDev &g, f3 o, f3 d, float t
   p = vstd_max(p, f3{-1.0f, -1.0f, -1.0f});
   p = vstd_min(p, f3{1.0f, 1.0f, 1.0f});
   GridTaps tc;
-#if RT_GRID_MARCH
   // One exit per step, as the octree's leaf march (oct_leaf): t advances by s
   // on every step (the reference returns t + s at a hit), the next point and
   // its in-box test are computed on the hit step too, and the hit point is
@@ -1165,13 +988,12 @@ __device__ __forceinline__ bool grid_march(const GridDev &g, f3 o, f3 d, float t
     return clamp_med3(q.x, -1.0f, 1.0f) == q.x && clamp_med3(q.y, -1.0f, 1.0f) == q.y &&
            clamp_med3(q.z, -1.0f, 1.0f) == q.z;
   };
-  constexpr bool kCache = RT_GRID_TAP_CACHE != 0;
   bool hit = false;
   float tp = t;
   if (inside(p)) {
     bool in;
     do {
-      const float s = grid_sdf_t<kMode, kCache>(g, p, kCache ? nullptr : &cell, tc, cnt);
+      const float s = grid_sdf_t<kMode, true>(g, p, nullptr, tc, cnt);
       hit = s < 1e-3f;
       tp = t;
       t += s;
@@ -1182,22 +1004,9 @@ __device__ __forceinline__ bool grid_march(const GridDev &g, f3 o, f3 d, float t
   if (hit) {
     out_t = t;
     hp = vstd_min(vstd_max(o + tp * d, f3{-1.0f, -1.0f, -1.0f}), f3{1.0f, 1.0f, 1.0f});
-    if (kCache) cell = (tc.i0x * g.sy + tc.i0y) * g.sz + tc.i0z;
+    cell = (tc.i0x * g.sy + tc.i0y) * g.sz + tc.i0z;
   }
   return hit;
-#else
-  while (p.x <= 1.0f && p.y <= 1.0f && p.z <= 1.0f && p.x >= -1.0f && p.y >= -1.0f && p.z >= -1.0f) {
-    const float s = grid_sdf_t<kMode, RT_GRID_TAP_CACHE != 0>(g, p, &cell, tc, cnt);
-    if (s < 1e-3f) {
-      out_t = t + s;
-      hp = p;
-      return true;
-    }
-    t += s;
-    p = o + t * d;
-  }
-  return false;
-#endif
 }
 
 template <int kMode, class CT>
@@ -1258,7 +1067,7 @@ __device__ __forceinline__ int grid_run(const GridDev &g, f3 o, f3 d, GridRay &R
       R = GridRay{t, p};
       return RAY_PENDING;
     }
-    const float s = grid_sdf_t<kMode, RT_GRID_TAP_CACHE != 0>(g, p, &cell, tc, cnt);
+    const float s = grid_sdf_t<kMode, true>(g, p, &cell, tc, cnt);
     if (s < 1e-3f) {
       out_t = t + s;
       hp = p;
@@ -1366,10 +1175,6 @@ __device__ __forceinline__ f3 oct_normal(const OctCorners &c, f3 bmin, float inv
 // start clamp as one v_med3 per axis (t1 is finite, so p is; the clamp's
 // result differs from std's only in the sign of a zero coordinate, which the
 // march's comparisons and oct_local's clamp never see).
-// 1: the leaf march as a one-exit loop (A/B switch; 0 the two-exit form)
-#ifndef RT_OCT_MARCH
-#define RT_OCT_MARCH 1
-#endif
 
 // The box entry / exit of a node for FAST rays (bbox_intersection_fast), once
 // per visit: the leaf march starts from them and the inner expansion's
@@ -1414,7 +1219,6 @@ __device__ __forceinline__ bool oct_leaf(const OctDev &sc, uint32_t node, f3 bmi
   // The march's state (t, p, s) is all the loop carries; the hit is read off
   // it after the loop, so no output is a loop-carried value (the outputs
   // written inside the loop made the compiler copy ~13 registers per step).
-#if RT_OCT_MARCH
   // One exit per step: the reference returns t + s at a hit and continues
   // from t + s otherwise, so t advances on every step; the next point and
   // its in-box test are computed on the hit step too (unused there). The
@@ -1452,23 +1256,6 @@ __device__ __forceinline__ bool oct_leaf(const OctDev &sc, uint32_t node, f3 bmi
     }
   }
   return hit;
-#else
-  float s = 0.0f;
-  bool in = inside(p);
-  while (in) {
-    s = oct_sdf(c, bmin, inv_s, p);
-    cnt.add(C_OCT_STEP, 1);
-    if (s < 1e-4f) break;  // hit: `in` stays true
-    t += s;
-    p = o + t * d;
-    in = inside(p);
-  }
-  if (in) {
-    out_t = t + s;
-    out_p = p;
-  }
-  return in;
-#endif
 }
 
 // Where a leaf march hit: the leaf (node index, integer box coordinates at
@@ -1511,12 +1298,6 @@ __device__ __forceinline__ void oct_filter(uint32_t &list, uint32_t &cnt, uint32
   cnt = n;
 }
 
-// 1: oct_expand takes the crossing-order path when it provably gives sort8's
-// list (A/B switch; 0 always runs the 8-child slab test and sort8)
-#ifndef RT_OCT_PATH
-#define RT_OCT_PATH 1
-#endif
-
 // Expand an octree inner node: divide_box_8 + intersect_box_8 + sort8, keep
 // entries with t > 0 (octree_raytracing.cpp:175-199), then only the children
 // whose bit is set in `keep` (the child masks; 0xFF keeps all). The 8 child
@@ -1550,8 +1331,8 @@ __device__ __forceinline__ void oct_expand(f3 bmin, f3 bmax, f3 o, f3 inv, float
   const float x0 = (bmin.x - o.x) * inv.x, x1 = (center.x - o.x) * inv.x, x2 = (hi.x - o.x) * inv.x;
   const float y0 = (bmin.y - o.y) * inv.y, y1 = (center.y - o.y) * inv.y, y2 = (hi.y - o.y) * inv.y;
   const float z0 = (bmin.z - o.z) * inv.z, z1 = (center.z - o.z) * inv.z, z2 = (hi.z - o.z) * inv.z;
-  bool exact = !FAST || !RT_OCT_PATH;
-  if constexpr (FAST && RT_OCT_PATH) {
+  bool exact = !FAST;
+  if constexpr (FAST) {
     // near half per axis: 0 when the ray runs towards +axis (1/d > 0), else 1.
     // P = max(the 3 entries, tNear), Q = min(the 3 exits, tFar): oct_entry's
     // t1 / t2 (an entry is the smaller of an axis' two slab distances)
@@ -1728,54 +1509,35 @@ __device__ __forceinline__ int oct_start(const OctDev &sc, f3 o, f3 d, f3 inv, f
 // The front-to-back loop of intersectNode below the root. SUSPEND: before each
 // iteration, if `limit` or fewer lanes of the wave are still in the loop, save
 // the state and return RAY_PENDING.
-// Octree loop iterations whose lanes split between leaf marches and inner
-// expansions run only the side with more lanes (the others keep their chosen
-// child pending for the next iteration, their visit order unchanged), as the
-// mesh's primary loop does (RT_MESH_MAJ). 0: off (A/B switch).
-#ifndef RT_OCT_MAJ
-#define RT_OCT_MAJ 0
-#endif
-
 template <int BLOCK, bool FAST, bool SUSPEND, bool PACK, class CT>
 __device__ __forceinline__ int oct_run(const OctDev &sc, f3 o, f3 d, f3 inv, float tNear, float tFar,
                                        LdsStack<BLOCK, kOctFields> st, OctRay &R, int limit, float &out_t,
                                        OctHitPt &hp, CT &cnt) {
   constexpr bool MASKS = !CT::kCounts;
-  constexpr bool MAJ = RT_OCT_MAJ && MASKS && !SUSPEND;
   uint32_t fbase = R.fbase, flist = R.lc & 0xFFFFFFu, fcnt = R.lc >> 24, leafm = R.leafm;
   OctXYZ<PACK> xyz(R.ix, R.iy, R.iz);
   int depth = R.depth, sp = R.sp;
-  uint32_t pj = 8;  // MAJ: the chosen child not visited yet (8: none)
   for (;;) {
     if (SUSPEND && __popcll(__ballot(1)) <= limit) {
       R = OctRay{fbase, flist | (fcnt << 24), leafm, xyz.ix(), xyz.iy(), xyz.iz(), depth, sp};
       return RAY_PENDING;
     }
-    if (!MAJ || pj == 8) {
-      if (fcnt == 0) {
-        if (sp == 0) return RAY_MISS;
-        --sp;
-        fbase = st.at(sp, 0);
-        const uint32_t lc = st.at(sp, 1);
-        const uint32_t w2 = st.at(sp, 2);  // leaf mask | depth << 8
-        if (MASKS) leafm = w2 & 0xFFu;
-        const int d2 = (int)(w2 >> 8);
-        xyz.up((uint32_t)(depth - d2));
-        depth = d2;
-        flist = lc & 0xFFFFFFu;
-        fcnt = lc >> 24;  // >= 1: empty frames are never pushed
-      }
-      pj = flist & 7u;
-      flist >>= 3;
-      fcnt -= 1;
+    if (fcnt == 0) {
+      if (sp == 0) return RAY_MISS;
+      --sp;
+      fbase = st.at(sp, 0);
+      const uint32_t lc = st.at(sp, 1);
+      const uint32_t w2 = st.at(sp, 2);  // leaf mask | depth << 8
+      if (MASKS) leafm = w2 & 0xFFu;
+      const int d2 = (int)(w2 >> 8);
+      xyz.up((uint32_t)(depth - d2));
+      depth = d2;
+      flist = lc & 0xFFFFFFu;
+      fcnt = lc >> 24;  // >= 1: empty frames are never pushed
     }
-    const uint32_t j = pj;
-    if constexpr (MAJ) {
-      const bool lf = (leafm >> j) & 1u;
-      const uint32_t nL = (uint32_t)__popcll(__ballot(lf)), nI = (uint32_t)__popcll(__ballot(!lf));
-      if (lf ? nL < nI : nI < nL) continue;  // wait: j stays pending
-    }
-    pj = 8;
+    const uint32_t j = flist & 7u;
+    flist >>= 3;
+    fcnt -= 1;
     const uint32_t cn = fbase + j;
     const OctXYZ<PACK> cxyz = xyz.child(j);
     rtl::OctWord cw{0u, 0u};
