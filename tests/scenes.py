@@ -33,6 +33,8 @@ MODES = {
     "default": (1, True, True, True),
     "lambert_noplane": (1, False, True, True),
     "lambert_noshadow": (1, True, False, True),
+    "lambert_norefl": (1, True, True, False),
+    "lambert_plain": (1, True, False, False),
     "color_plane": (2, True, True, True),
     "normal_plane": (0, True, True, True),
 }
