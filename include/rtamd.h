@@ -294,6 +294,34 @@ int rt_ipc_close(void *d_ptr);
  * index; plane: -2; miss: -1). */
 int rt_intersect_rays(rt_scene *s, const float *o, const float *d, int64_t n, float tnear,
                       float tfar, int32_t *hit, float *t, float *normal, int64_t *prim);
+/* IScene::intersect (src/raytracing.hpp:77-79) for rays that are already on
+ * the GPU: n rays in DEVICE buffers, traced in stream order on `stream`
+ * (hipStream_t or NULL). The call only launches: no allocation, no copy, no
+ * host synchronisation. The scene's device must be the current one, as for
+ * rt_render_device. Every value written is exactly what rt_intersect_rays
+ * writes for the same ray (hit 0/1; t +inf on a miss; normal (0,1,0) on a
+ * miss, not flipped; prim as above; the scene's plane takes part). An output
+ * pointer left NULL is not written, and a batch without d_normal computes no
+ * normal at all. n == 0 launches nothing; n is limited to what one launch
+ * holds (2^32 - 64 rays), larger batches are split by the caller. */
+typedef struct rt_ray_batch {
+  int64_t n;               /* rays */
+  const float *d_origin;   /* float[3n], device */
+  const float *d_dir;      /* float[3n], device; not normalised by the library */
+  const float *d_tnear;    /* float[n] per-ray tNear, or NULL: use tnear */
+  const float *d_tfar;     /* float[n] per-ray tFar,  or NULL: use tfar  */
+  float tnear, tfar;
+  int32_t *d_hit;          /* outputs, device; each may be NULL = not wanted */
+  float   *d_t;
+  float   *d_normal;       /* float[3n] */
+  int64_t *d_prim;
+} rt_ray_batch;
+/* Any hit: only d_hit is written (d_t, d_normal, d_prim must be NULL), with
+ * HitInfo::hitten of the closest-hit query -- for the union with the plane the
+ * OR of both -- and the traversal stops at the first hit (the Lambert shadow
+ * ray's query, src/raytracing.cpp:36-41). */
+#define RT_RAYS_ANY_HIT 1u
+int rt_trace_rays_device(rt_scene *s, const rt_ray_batch *b, uint32_t flags, void *stream);
 
 /* Timing helper for benchmarks: renders `frames` frames back to back on the
  * device (buffers owned by the library), returns the mean kernel ms per frame

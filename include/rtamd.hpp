@@ -190,6 +190,13 @@ class IScene {
       out[i] = HitInfo{hit[(size_t)i] != 0, t[(size_t)i],
                        {nrm[3 * (size_t)i], nrm[3 * (size_t)i + 1], nrm[3 * (size_t)i + 2]}, prim[(size_t)i]};
   }
+  // IScene::intersect for rays already in device memory (rt_ray_batch: device
+  // pointers; outputs left NULL are not computed), queued on `stream`
+  // (hipStream_t or nullptr); flags: 0 or RT_RAYS_ANY_HIT. Returns after the
+  // launch.
+  void intersectDevice(const rt_ray_batch &batch, uint32_t flags = 0, void *stream = nullptr) const {
+    check(rt_trace_rays_device(handle(), &batch, flags, stream));
+  }
   void setPlane(const Plane *p) const {
     const float n[3] = {p ? p->normal.x : 0.0f, p ? p->normal.y : 1.0f, p ? p->normal.z : 0.0f};
     check(rt_scene_set_plane(handle(), p ? 1 : 0, n, p ? p->offset : 0.0f));

@@ -2,7 +2,7 @@
 // the launchers and schedules that instantiate the kernels, and the entry
 // points of include/rtamd.h that reach them (scene create / replicate /
 // destroy with the BVH builder choice, rt_render*, rt_untile_device,
-// rt_intersect_rays, rt_count_work, rt_bench_frames, the rtx_set_* switches
+// rt_intersect_rays, rt_trace_rays_device, rt_count_work, rt_bench_frames, the rtx_set_* switches
 // of the launchers, rti::). The rest of the C ABI is in rt_runtime.hip
 // (errors, streams, host memory, devices), rt_abi_host.hip (loaders, camera,
 // output) and rt_diag.hip (device self-checks).
@@ -24,6 +24,7 @@
 #include <map>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -1213,6 +1214,122 @@ __global__ __launch_bounds__(kBlock) void rays_kernel(S sc, PlaneDev pl, const f
   prim[i] = sh.h.hit ? sh.h.prim : -1;
 }
 
+// ---- rt_trace_rays_device: IScene::intersect on device buffers -------------
+// One ray per lane, like rays_kernel, with the work chosen at compile time:
+// kRaysAny (S::occluded, one word per ray), kRaysClosest (no normal is
+// computed: no tri_normal triangle reload, no grid_normal, oct_trace without
+// NEED_NORMAL) and kRaysNormal. The outputs the caller left NULL and the
+// per-ray tNear / tFar arrays are wave-uniform branches on kernel arguments.
+// The mesh's closest hit is mesh_primary_wave (a wave's last rays finish in
+// 8-lane groups), the other traversals are per lane (DESIGN.md section 4;
+// what was measured against them is in section 8).
+enum { kRaysAny = 0, kRaysClosest = 1, kRaysNormal = 2 };
+// Workgroup of trace_rays_kernel: one wave. A ray batch has no tile that needs
+// four waves together, and a workgroup keeps its LDS stacks until its slowest
+// wave ends.
+constexpr int kRBlock = 64;
+// a launch's global size is a 32-bit count of work-items
+constexpr int64_t kMaxRayBlocks = (int64_t)(0xFFFFFFFFu / (uint32_t)kRBlock);
+
+// S::intersect with the normal (and the primitive id's load) optional
+template <int B, bool NORMAL, class CT>
+__device__ __forceinline__ Hit rays_closest(const MeshS &sc, f3 o, f3 d, float tn, float tf,
+                                            LdsStack<B, MeshS::kFields> st, bool want_prim, CT &cnt) {
+  float t;
+  uint32_t k;
+  Hit h = miss_hit();
+  if (mesh_trace<B, false>(sc.d, o, d, tn, tf, st, t, k, cnt)) {
+    h.hit = true;
+    h.t = t;
+    if constexpr (NORMAL) h.n = tri_normal(sc.d.tris, k);
+    if (want_prim) h.prim = (int64_t)sc.d.tris[k].orig_id;
+  }
+  return h;
+}
+template <int B, bool NORMAL, int kMode, class CT>
+__device__ __forceinline__ Hit rays_closest(const GridS<kMode> &sc, f3 o, f3 d, float tn, float tf,
+                                            LdsStack<B, GridS<kMode>::kFields>, bool, CT &cnt) {
+  Hit h = miss_hit();
+  f3 p;
+  uint32_t cell;
+  if (grid_march<kMode>(sc.d, o, d, tn, tf, h.t, p, cell, cnt)) {
+    h.hit = true;
+    if constexpr (NORMAL) h.n = grid_normal<kMode>(sc.d, p, cnt);
+    h.prim = (int64_t)cell;
+  } else {
+    h.t = kInf;
+  }
+  return h;
+}
+template <int B, bool NORMAL, bool PACK, class CT>
+__device__ __forceinline__ Hit rays_closest(const OctS<PACK> &sc, f3 o, f3 d, float tn, float tf,
+                                            LdsStack<B, kOctFields> st, bool, CT &cnt) {
+  Hit h = miss_hit();
+  uint32_t node;
+  if (oct_trace<B, NORMAL, PACK>(sc.d, o, d, tn, tf, st, h.t, h.n, node, cnt)) {
+    h.hit = true;
+    h.prim = (int64_t)node;
+  } else {
+    h.t = kInf;
+  }
+  return h;
+}
+
+template <class S, int SLOTS, int MODE>
+__global__ __launch_bounds__(kRBlock) void trace_rays_kernel(S sc, PlaneDev pl, rt_ray_batch b) {
+  __shared__ uint32_t stk[stack_words<S, SLOTS>() * kRBlock];
+  const int64_t i = (int64_t)blockIdx.x * kRBlock + threadIdx.x;
+  // a partial last wave keeps its lanes without a ray: mesh_primary_wave needs
+  // the whole wave, so they carry active = false and touch no memory
+  const bool active = i < b.n;
+  StackOf<S, kRBlock> st{stk + threadIdx.x};
+  f3 o{0.0f, 0.0f, 0.0f}, d{0.0f, 0.0f, 1.0f};
+  float tn = b.tnear, tf = b.tfar;
+  if (active) {
+    o = f3{b.d_origin[3 * i], b.d_origin[3 * i + 1], b.d_origin[3 * i + 2]};
+    d = f3{b.d_dir[3 * i], b.d_dir[3 * i + 1], b.d_dir[3 * i + 2]};
+    if (b.d_tnear) tn = b.d_tnear[i];
+    if (b.d_tfar) tf = b.d_tfar[i];
+  }
+  NoCnt cnt;
+  if constexpr (MODE == kRaysAny) {
+    if (active) b.d_hit[i] = union_occluded<S, kRBlock>(sc, pl, o, d, tn, tf, st, cnt) ? 1 : 0;
+  } else {
+    Hit h = miss_hit();
+    bool traced = false;
+    if constexpr (std::is_same_v<S, MeshS>) {
+      // mesh_primary_wave takes one tNear for the wave (tFar is per ray):
+      // batches with a d_tnear array take the per-lane traversal below
+      if (!b.d_tnear) {
+        float t;
+        uint32_t k;
+        if (mesh_primary_wave<kRBlock, MeshS::kFields>(sc.d, o, d, tn, tf, active, stk, t, k) && active) {
+          h.hit = true;
+          h.t = t;
+          if constexpr (MODE == kRaysNormal) h.n = tri_normal(sc.d.tris, k);
+          if (b.d_prim) h.prim = (int64_t)sc.d.tris[k].orig_id;
+        }
+        traced = true;
+      }
+    }
+    if (!active) return;
+    if (!traced) h = rays_closest<kRBlock, MODE == kRaysNormal>(sc, o, d, tn, tf, st, b.d_prim != nullptr, cnt);
+    if (pl.on) {  // SceneUnion::intersect, as union_intersect
+      float tp = kInf, ap = 1.0f;
+      const bool ph = plane_hit(pl, o, d, tn, tf, tp, ap);
+      if (!(h.t < (ph ? tp : kInf))) h = ph ? Hit{true, tp, pl.n, -2} : miss_hit();
+    }
+    if (b.d_hit) b.d_hit[i] = h.hit ? 1 : 0;
+    if (b.d_t) b.d_t[i] = h.t;
+    if constexpr (MODE == kRaysNormal) {
+      b.d_normal[3 * i] = h.n.x;
+      b.d_normal[3 * i + 1] = h.n.y;
+      b.d_normal[3 * i + 2] = h.n.z;
+    }
+    if (b.d_prim) b.d_prim[i] = h.hit ? h.prim : -1;
+  }
+}
+
 // FrameBuffer::clear() (raytracing.hpp:16-19): 16 B per lane per buffer.
 __global__ void clear_kernel(uint32_t *c, float *t, int64_t n) {
   const int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
@@ -2220,6 +2337,50 @@ void launch_rays_t(const S &sc, const PlaneDev &pl, const float *o, const float 
   rays_kernel<S, MAXD><<<(unsigned)blocks, kBlock>>>(sc, pl, o, d, n, tn, tf, hit, t, nrm, prim);
 }
 
+template <class S, int MAXD>
+void launch_trace_t(const S &sc, const PlaneDev &pl, const rt_ray_batch &b, int mode, hipStream_t stream) {
+  const unsigned blocks = (unsigned)((b.n + kRBlock - 1) / kRBlock);
+  switch (mode) {
+    case kRaysAny: trace_rays_kernel<S, MAXD, kRaysAny><<<blocks, kRBlock, 0, stream>>>(sc, pl, b); break;
+    case kRaysClosest: trace_rays_kernel<S, MAXD, kRaysClosest><<<blocks, kRBlock, 0, stream>>>(sc, pl, b); break;
+    default: trace_rays_kernel<S, MAXD, kRaysNormal><<<blocks, kRBlock, 0, stream>>>(sc, pl, b); break;
+  }
+}
+
+// the scene-kind / grid-mode / stack-slot dispatch of rt_intersect_rays
+int launch_trace(rt_scene *s, const rt_ray_batch &b, int mode, hipStream_t stream) {
+  if (s->kind == RT_SCENE_MESH) {
+    const MeshDev md = mesh_dev(s);
+    switch (s->maxd) {
+      case 4: launch_trace_t<MeshS, 4>(MeshS{md}, s->plane, b, mode, stream); break;
+      case 7: launch_trace_t<MeshS, 7>(MeshS{md}, s->plane, b, mode, stream); break;
+      case 15: launch_trace_t<MeshS, 15>(MeshS{md}, s->plane, b, mode, stream); break;
+      default: launch_trace_t<MeshS, 31>(MeshS{md}, s->plane, b, mode, stream); break;
+    }
+  } else if (s->kind == RT_SCENE_GRID) {
+    const GridDev gd = grid_dev(s);
+    switch (grid_mode(s, gd)) {
+      case kGridBuf | kGridBricked:
+        launch_trace_t<GridS<kGridBuf | kGridBricked>, 1>({gd}, s->plane, b, mode, stream);
+        break;
+      case kGridBricked: launch_trace_t<GridS<kGridBricked>, 1>({gd}, s->plane, b, mode, stream); break;
+      default: launch_trace_t<GridS<kGridBuf>, 1>({gd}, s->plane, b, mode, stream); break;
+    }
+  } else if (s->kind == RT_SCENE_OCTREE) {
+    const OctDev od{s->d_child, s->d_ovals};
+    switch (s->maxd) {
+      case 4: launch_trace_t<OctS<true>, 4>(OctS<true>{od}, s->plane, b, mode, stream); break;
+      case 7: launch_trace_t<OctS<true>, 7>(OctS<true>{od}, s->plane, b, mode, stream); break;
+      case 15: launch_trace_t<OctS<false>, 15>(OctS<false>{od}, s->plane, b, mode, stream); break;
+      default: launch_trace_t<OctS<false>, 31>(OctS<false>{od}, s->plane, b, mode, stream); break;
+    }
+  } else {
+    return set_err(RT_E_STATE, "scene has no geometry");
+  }
+  HIP_TRY(hipGetLastError());
+  return RT_OK;
+}
+
 }  // namespace
 
 namespace {
@@ -3015,6 +3176,23 @@ int rt_intersect_rays(rt_scene *s, const float *o, const float *d, int64_t n, fl
   cleanup();
   if (e != hipSuccess) return set_err(RT_E_DEVICE, std::string("rt_intersect_rays: ") + hipGetErrorString(e));
   return RT_OK;
+}
+
+int rt_trace_rays_device(rt_scene *s, const rt_ray_batch *b, uint32_t flags, void *stream) {
+  if (!s) return set_err(RT_E_INVALID, "scene is NULL");
+  if (!b) return set_err(RT_E_INVALID, "ray batch is NULL");
+  if (flags & ~RT_RAYS_ANY_HIT) return set_err(RT_E_INVALID, "unknown ray flag");
+  if (b->n < 0) return set_err(RT_E_INVALID, "negative ray count");
+  if (!b->d_origin || !b->d_dir) return set_err(RT_E_INVALID, "NULL ray origins or directions");
+  if (!b->d_hit && !b->d_t && !b->d_normal && !b->d_prim) return set_err(RT_E_INVALID, "no output buffer");
+  const bool any = (flags & RT_RAYS_ANY_HIT) != 0;
+  if (any && (!b->d_hit || b->d_t || b->d_normal || b->d_prim))
+    return set_err(RT_E_INVALID, "RT_RAYS_ANY_HIT writes d_hit only: d_t, d_normal and d_prim must be NULL");
+  if (b->n / kRBlock + (b->n % kRBlock != 0) > kMaxRayBlocks)
+    return set_err(RT_E_INVALID, "ray count exceeds one launch (" + std::to_string(kMaxRayBlocks * kRBlock) +
+                                     " rays): split the batch");
+  if (b->n == 0) return RT_OK;
+  return launch_trace(s, *b, any ? kRaysAny : b->d_normal ? kRaysNormal : kRaysClosest, (hipStream_t)stream);
 }
 
 int rt_count_work(rt_scene *s, const rt_render_params *params, int32_t frames, int32_t W, int32_t H,

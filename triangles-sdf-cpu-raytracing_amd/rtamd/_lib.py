@@ -17,6 +17,7 @@ RT_OK = 0
 RT_FLAG_CLEAR = 1
 RT_FLAG_TILE_NATURAL = 2
 RT_FLAG_HITS_ONLY = 4
+RT_RAYS_ANY_HIT = 1
 RT_IPC_HANDLE_BYTES = 64
 RT_SCENE_MESH, RT_SCENE_GRID, RT_SCENE_OCTREE = 1, 2, 3
 
@@ -51,6 +52,13 @@ class CameraState(C.Structure):
     """rt_camera_state (include/rtamd.h)."""
     _fields_ = [("position", C.c_float * 3), ("target", C.c_float * 3), ("orientation", C.c_float * 4),
                 ("sensitivity", C.c_float), ("lock_up", C.c_int32), ("locked_up", C.c_float * 3)]
+
+
+class RayBatch(C.Structure):
+    """rt_ray_batch (include/rtamd.h): device pointers as integers, 0 / None = NULL."""
+    _fields_ = [("n", C.c_int64), ("d_origin", C.c_void_p), ("d_dir", C.c_void_p), ("d_tnear", C.c_void_p),
+                ("d_tfar", C.c_void_p), ("tnear", C.c_float), ("tfar", C.c_float), ("d_hit", C.c_void_p),
+                ("d_t", C.c_void_p), ("d_normal", C.c_void_p), ("d_prim", C.c_void_p)]
 
 
 # name -> (restype, argtypes)
@@ -111,6 +119,7 @@ _SIGS = {
     "rt_ipc_close": (C.c_int, [C.c_void_p]),
     "rt_intersect_rays": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float,
                                     C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_trace_rays_device": (C.c_int, [C.c_void_p, C.POINTER(RayBatch), C.c_uint32, C.c_void_p]),
     "rt_count_work": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
                                 C.c_uint32, C.c_void_p, C.c_void_p]),
     "rt_bench_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,

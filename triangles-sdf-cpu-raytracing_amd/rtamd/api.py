@@ -23,7 +23,8 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from ._lib import (RT_FLAG_CLEAR, RT_FLAG_HITS_ONLY, CameraState, RenderParams, RtError, Tile, check, lib)
+from ._lib import (RT_FLAG_CLEAR, RT_FLAG_HITS_ONLY, RT_RAYS_ANY_HIT, CameraState, RayBatch, RenderParams, RtError,
+                   Tile, check, lib)
 
 __all__ = [
     "ShadingMode", "SimpleMesh", "FrameBuffer", "Camera", "Renderer", "HitInfo", "IScene",
@@ -295,6 +296,23 @@ class IScene:
         check(lib().rt_render_device_frames(self._handle(), arr, n, cp, tp, W, H, flags,
                                             C.byref(tile) if tile is not None else None,
                                             C.c_void_p(stream) if stream else None))
+
+    def trace_device(self, origin_ptr: int, dir_ptr: int, n: int, *, hit_ptr: int | None = None,
+                     t_ptr: int | None = None, normal_ptr: int | None = None, prim_ptr: int | None = None,
+                     tnear: float = 0.01, tfar: float = 100.0, tnear_ptr: int | None = None,
+                     tfar_ptr: int | None = None, any_hit: bool = False, stream: int | None = None):
+        """IScene::intersect on device buffers (rt_trace_rays_device): n rays at
+        origin_ptr / dir_ptr (float32[3n], e.g. torch tensors' data_ptr()),
+        traced in stream order on `stream`; the call only launches. Outputs
+        left None are neither computed nor written (int32 hit, float32 t,
+        float32[3n] normal, int64 prim). tnear_ptr / tfar_ptr (float32[n])
+        replace the scalars per ray. any_hit: hit_ptr only, the traversal
+        stops at the first hit."""
+        b = RayBatch(int(n), origin_ptr or None, dir_ptr or None, tnear_ptr or None, tfar_ptr or None,
+                     float(tnear), float(tfar), hit_ptr or None, t_ptr or None, normal_ptr or None,
+                     prim_ptr or None)
+        check(lib().rt_trace_rays_device(self._handle(), C.byref(b), RT_RAYS_ANY_HIT if any_hit else 0,
+                                         C.c_void_p(stream) if stream else None))
 
     def bench_frames(self, params_list, W: int, H: int, clear: bool = True):
         arr = (RenderParams * len(params_list))(*params_list)

@@ -1,0 +1,92 @@
+"""Ray queries on torch tensors: IScene::intersect (raytracing.hpp:77-79) for
+rays that already live on the GPU, through rt_trace_rays_device.
+
+    from rtamd import torch_rays
+    r = torch_rays.trace(scene, origins, dirs, outputs=("hit", "t"))
+
+The launch is queued on torch.cuda.current_stream(): it is ordered with the
+torch work around it, and nothing is copied or synchronised. torch is
+imported when trace() is called, so ``import rtamd`` stays torch-free.
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass
+
+from ._lib import lib
+
+OUTPUTS = ("hit", "t", "normal", "prim")
+
+
+@dataclass
+class RayHits:
+    """The requested outputs of one trace() ([N] tensors on the rays' device;
+    normal is [N,3]); the others are None."""
+    hit: "object | None" = None      # torch.int32, 0 / 1
+    t: "object | None" = None        # torch.float32, +inf on a miss
+    normal: "object | None" = None   # torch.float32 [N,3], (0,1,0) on a miss, not flipped
+    prim: "object | None" = None     # torch.int64, include/rtamd.h's primitive id
+
+
+def _rays(torch, x, what, device):
+    if not isinstance(x, torch.Tensor):
+        raise ValueError(f"{what}: expected a torch tensor, got {type(x).__name__}")
+    if x.dtype != torch.float32:
+        raise ValueError(f"{what}: dtype {x.dtype}, expected torch.float32")
+    if x.dim() != 2 or x.shape[1] != 3:
+        raise ValueError(f"{what}: shape {tuple(x.shape)}, expected [N, 3]")
+    if x.device.type != "cuda" or x.device.index != device:
+        raise ValueError(f"{what}: on {x.device}, the scene is on HIP device {device}")
+    if not x.is_contiguous():
+        raise ValueError(f"{what}: not contiguous")
+    return x
+
+
+def _interval(torch, x, what, n, device):
+    """-> (scalar, pointer): a float, or a float32 [N] tensor on the device."""
+    if not isinstance(x, torch.Tensor):
+        return float(x), None
+    if x.dtype != torch.float32 or x.dim() != 1 or x.shape[0] != n:
+        raise ValueError(f"{what}: {x.dtype} {tuple(x.shape)}, expected a float or torch.float32 [{n}]")
+    if x.device.type != "cuda" or x.device.index != device:
+        raise ValueError(f"{what}: on {x.device}, the scene is on HIP device {device}")
+    if not x.is_contiguous():
+        raise ValueError(f"{what}: not contiguous")
+    return 0.0, x
+
+
+def trace(scene, origins, dirs, tnear=0.01, tfar=100.0, any_hit=False, outputs=OUTPUTS) -> RayHits:
+    """Closest hit (or, with any_hit, the hit flag alone) of N rays against
+    `scene` (an rtamd.IScene). origins, dirs: contiguous float32 [N,3] tensors
+    on the scene's device (dirs are used as given, not normalised); tnear,
+    tfar: floats or float32 [N] tensors. Only the outputs named are computed
+    and allocated (torch.empty); any_hit allows "hit" alone. Raises ValueError
+    on a bad tensor before anything is launched."""
+    import torch
+
+    device = int(lib().rt_scene_device(scene._handle()))
+    o = _rays(torch, origins, "origins", device)
+    d = _rays(torch, dirs, "dirs", device)
+    if o.shape != d.shape:
+        raise ValueError(f"origins {tuple(o.shape)} and dirs {tuple(d.shape)} differ in shape")
+    n = o.shape[0]
+    tn, tn_t = _interval(torch, tnear, "tnear", n, device)
+    tf, tf_t = _interval(torch, tfar, "tfar", n, device)
+    outputs = tuple(outputs)
+    if not outputs or any(k not in OUTPUTS for k in outputs) or len(set(outputs)) != len(outputs):
+        raise ValueError(f"outputs {outputs}: a non-empty selection of {OUTPUTS}")
+    if any_hit:
+        if outputs not in (OUTPUTS, ("hit",)):  # (the default selection means "hit" here)
+            raise ValueError('any_hit writes the hit flag only: outputs must be ("hit",)')
+        outputs = ("hit",)
+    kinds = {"hit": ((n,), torch.int32), "t": ((n,), torch.float32), "normal": ((n, 3), torch.float32),
+             "prim": ((n,), torch.int64)}
+    r = RayHits(**{k: torch.empty(kinds[k][0], dtype=kinds[k][1], device=o.device) for k in outputs})
+    ptr = lambda x: x.data_ptr() if x is not None and x.numel() else None
+    if n == 0:
+        return r
+    with torch.cuda.device(device):
+        scene.trace_device(o.data_ptr(), d.data_ptr(), n, hit_ptr=ptr(r.hit), t_ptr=ptr(r.t),
+                           normal_ptr=ptr(r.normal), prim_ptr=ptr(r.prim), tnear=tn, tfar=tf,
+                           tnear_ptr=ptr(tn_t), tfar_ptr=ptr(tf_t), any_hit=any_hit,
+                           stream=torch.cuda.current_stream(device).cuda_stream)
+    return r
