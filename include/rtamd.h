@@ -139,6 +139,49 @@ int rt_set_bvh_builder(int mode);
  * 8-wide SAH BVH on the host, then uploads a GPU layout of it. */
 int rt_scene_create_mesh(const float *vpos4, int64_t nverts, const uint32_t *idx, int64_t nidx,
                          rt_scene **out);
+/* The same with flags. 0: exactly rt_scene_create_mesh. RT_MESH_DYNAMIC: the
+ * scene's vertices may be moved afterwards (rt_scene_update_vertices*); it
+ * additionally keeps on the device the index array (nidx words) and a vertex
+ * staging buffer (16 * nverts bytes), both counted in rt_scene_device_bytes.
+ * Either builder (rt_set_bvh_builder) serves both. No reference counterpart:
+ * the reference's meshes are immutable. */
+#define RT_MESH_DYNAMIC 1u
+int rt_scene_create_mesh_ex(const float *vpos4, int64_t nverts, const uint32_t *idx, int64_t nidx,
+                            uint32_t flags, rt_scene **out);
+/* Deforming meshes: refit the BVH8 of an RT_MESH_DYNAMIC scene to new vertex
+ * positions, on the GPU. The triangle list and the tree topology stay;
+ * nverts must equal the creation value. Afterwards the scene is the tree of
+ * the same topology over the new positions: every leaf triangle is rewritten
+ * (v /= v.w, e1 = v1 - v0, e2 = v2 - v0, its original index kept) and every
+ * child box is the exact min/max of its subtree, so a query finds the same
+ * closest hit as on a freshly built scene of the new mesh. (As between any two
+ * valid trees, the answers can differ where two triangles give bit-equal t,
+ * and for a triangle hit before tNear: the reference's triangle test has no t
+ * range, so such a hit is reported when its leaf's box reaches into [tNear,
+ * tFar], which depends on the leaf's other triangles.)
+ * A refit keeps the old split decisions: a heavily deformed mesh
+ * traverses slower than a fresh build of it, and destroy + create is the
+ * remedy (README.md has the measured trade).
+ *   rt_scene_update_vertices         vpos4 is a host buffer (copied through
+ *                                    the scene's staging buffer).
+ *   rt_scene_update_vertices_device  d_vpos4 is device memory on the scene's
+ *       device, which must be the current one; the kernels are queued on
+ *       `stream` (hipStream_t or NULL) after the work already there, so the
+ *       buffer may be the output of the caller's previous kernel on it.
+ * Both return after ONE host wait: the scene constants the host keeps (root
+ * box, the tile cull's bounds, the reciprocal's direction bound) are read back
+ * from the refitted tree, and the call waits for that copy. Every later call
+ * on any stream therefore sees the updated scene; the caller orders the
+ * update after earlier work that still uses the scene on OTHER streams.
+ * Nothing is allocated per call. Vertex values are not validated (device data
+ * cannot be without a readback): topology is never touched, so no value can
+ * make a traversal index out of bounds; NaN or infinite positions give boxes
+ * and triangles that rays miss or hit as the arithmetic says.
+ * Errors: RT_E_INVALID for a NULL scene or pointer, nverts <= 0 or another
+ * nverts than at creation; RT_E_STATE for a scene that is not a mesh or was
+ * not created with RT_MESH_DYNAMIC. A refused call leaves the scene as it was. */
+int rt_scene_update_vertices(rt_scene *s, const float *vpos4, int64_t nverts);
+int rt_scene_update_vertices_device(rt_scene *s, const float *d_vpos4, int64_t nverts, void *stream);
 /* SDFGrid (src/grid_raytracing.hpp:10-21). values: x-major, float[sx*sy*sz]. */
 int rt_scene_create_grid(const uint32_t size[3], const float *values, rt_scene **out);
 /* SDFOctree (src/octree_raytracing.hpp:20-47). nodes36: count x 36 bytes. */
@@ -155,7 +198,10 @@ int rt_scene_destroy(rt_scene *s);
 /* A copy of scene s on another HIP device (device arrays copied device to
  * device, over xGMI between GPUs; no rebuild): the same tree, plane and kernel
  * instantiation, so every frame it renders is bitwise s's. For replicating one
- * scene on the GPUs of a single-process multi-GPU render (rt_multi_create). */
+ * scene on the GPUs of a single-process multi-GPU render (rt_multi_create).
+ * The copy of an RT_MESH_DYNAMIC scene is a plain snapshot of its current
+ * geometry: it is not dynamic and does not follow later updates (rt_multi
+ * refreshes its own replicas when the root scene has been updated). */
 int rt_scene_replicate(const rt_scene *s, int device, rt_scene **out);
 /* HIP device the scene lives on. */
 int rt_scene_device(const rt_scene *s);
@@ -241,7 +287,9 @@ int rt_stream_release(void *stream);
 typedef struct rt_multi rt_multi;
 enum rt_multi_exchange { RT_MULTI_RCCL = 1, RT_MULTI_PEER_COPY = 2 };
 /* scene must live on devices[0]; it is not owned and must outlive the handle
- * (its plane is re-read at every render). band_rows <= 0 selects 8. */
+ * (its plane is re-read at every render, and after an
+ * rt_scene_update_vertices* the replicas' trees are re-copied at the next
+ * render). band_rows <= 0 selects 8. */
 int rt_multi_create(rt_scene *scene, const int32_t *devices, int32_t n, int32_t band_rows, rt_multi **out);
 /* Slots, the exchange in use (rt_multi_exchange) and the band height. */
 int rt_multi_info(const rt_multi *m, int32_t *n, int32_t *exchange, int32_t *band_rows);

@@ -218,11 +218,22 @@ class IScene {
 // BVHBuilder::perform (triangles_raytracing.cpp:227-258): same SAH BVH8.
 class BVHBuilder : public IScene {
  public:
-  void perform(const SimpleMesh &mesh) {
+  // dynamic: the vertices may be moved afterwards (updateVertices*); no
+  // reference counterpart, the reference's meshes are immutable
+  void perform(const SimpleMesh &mesh, bool dynamic = false) {
     rt_scene *s = nullptr;
-    check(rt_scene_create_mesh(mesh.vPos4f.data(), (int64_t)(mesh.vPos4f.size() / 4), mesh.indices.data(),
-                               (int64_t)mesh.indices.size(), &s));
+    check(rt_scene_create_mesh_ex(mesh.vPos4f.data(), (int64_t)(mesh.vPos4f.size() / 4), mesh.indices.data(),
+                                  (int64_t)mesh.indices.size(), dynamic ? RT_MESH_DYNAMIC : 0u, &s));
     reset(s);
+  }
+  // Refit the tree to new positions (4 floats per vertex, nverts as at
+  // creation), from a host buffer or from device memory in stream order on
+  // `stream` (hipStream_t or nullptr). Both return after one host wait.
+  void updateVertices(const float *vpos4, int64_t nverts) const {
+    check(rt_scene_update_vertices(handle(), vpos4, nverts));
+  }
+  void updateVerticesDevice(const float *d_vpos4, int64_t nverts, void *stream = nullptr) const {
+    check(rt_scene_update_vertices_device(handle(), d_vpos4, nverts, stream));
   }
   size_t nodesCount() const {
     int64_t n = 0, inner = 0;

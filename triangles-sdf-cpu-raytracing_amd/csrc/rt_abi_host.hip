@@ -136,6 +136,30 @@ int rt_save_obj(const char *path, const float *vpos4, int64_t nverts, const uint
   return RT_OK;
 }
 
+// The host restatement of the refit, no GPU: the host builder's tree of the
+// mesh (rth::build_bvh8) in device layout -- n_inner GNode records of 224 bytes,
+// n_tris GTri records of 48 bytes -- refitted to new_vpos4 (rth::refit_bvh8),
+// or as built when new_vpos4 is NULL. Two-call protocol: with nodes224 =
+// tris48 = NULL only the counts are returned; else *n_inner / *n_tris are the
+// buffers' capacities. Not part of include/rtamd.h.
+int rtx_bvh_refit_host(const float *vpos4, int64_t nverts, const uint32_t *idx, int64_t nidx, const float *new_vpos4,
+                       void *nodes224, int64_t *n_inner, void *tris48, int64_t *n_tris) {
+  if (!vpos4 || !idx || !n_inner || !n_tris || nverts <= 0 || nidx <= 0) return set_err(RT_E_INVALID, "bad mesh");
+  rth::BVHGpu b;
+  std::string err;
+  if (!rth::build_bvh8(vpos4, nverts, idx, nidx, b, err, rth::kBvhTris)) return set_err(RT_E_INVALID, err);
+  if (nodes224 || tris48) {
+    if (!nodes224 || !tris48 || *n_inner < (int64_t)b.nodes.size() || *n_tris < (int64_t)b.tris.size())
+      return set_err(RT_E_INVALID, "buffers too small");
+    if (new_vpos4) rth::refit_bvh8(b, new_vpos4, idx);
+    if (!b.nodes.empty()) std::memcpy(nodes224, b.nodes.data(), b.nodes.size() * sizeof(rtl::GNode));
+    if (!b.tris.empty()) std::memcpy(tris48, b.tris.data(), b.tris.size() * sizeof(rtl::GTri));
+  }
+  *n_inner = (int64_t)b.nodes.size();
+  *n_tris = (int64_t)b.tris.size();
+  return RT_OK;
+}
+
 // The pageable drop-in's host copy (rth::copy_spans) on caller arrays, no GPU:
 // span[2y] = first stored column of row y, span[2y+1] = -last (INT32_MAX,
 // INT32_MAX: none); threads 0 = the library's default; clear_src != 0: the

@@ -34,6 +34,7 @@
 #include "rt_layout.h"
 #include "rt_math.h"
 #include "rt_queue.h"
+#include "rt_refit.h"
 #include "rt_scenes.h"
 
 using namespace rtd;
@@ -1434,6 +1435,22 @@ struct rt_scene {
   uint32_t n_inner = 0;  // inner nodes on the device (MeshDev::n_inner)
   float dmax2 = 0.0f;    // MeshDev::dmax2 (mesh_dmax2; 0: every ray takes the division)
   int32_t bvh_depth = 0;
+  uint32_t n_tris = 0;   // triangle slots in d_tris (8 zero triangles follow)
+  uint32_t root_nchild = 0;  // children of an inner root (slots 0 .. root_nchild-1)
+  // a mesh created with RT_MESH_DYNAMIC (rt_scene_update_vertices*): the
+  // creation index array and a vertex staging buffer on the device, the first
+  // node index of every depth level (+ the node count), the edge-bound word of
+  // tri_edge_bound_kernel and the pinned host words the update reads back
+  // (48 root child box floats, then the edge bound)
+  bool dynamic = false;
+  int64_t nverts = 0;
+  uint32_t *d_idx = nullptr;
+  float *d_vstage = nullptr;
+  uint32_t *d_edge = nullptr;
+  uint32_t *h_refit = nullptr;
+  std::vector<uint32_t> level_first;
+  int64_t dyn_bytes = 0;  // what `dynamic` added to dev_bytes
+  uint64_t version = 0;   // counts the updates (rt_multi re-copies its replicas when it moves)
   // grid
   float *d_vals = nullptr;
   uint32_t size[3] = {0, 0, 0};
@@ -2455,6 +2472,12 @@ int upload(T **dst, const T *src, size_t n, int64_t &bytes) {
   return RT_OK;
 }
 
+// the pinned host words a dynamic mesh's update reads its constants into
+int dynamic_host_words(rt_scene *s) {
+  HIP_TRY(hipHostMalloc((void **)&s->h_refit, 64 * sizeof(uint32_t), hipHostMallocDefault));
+  return RT_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2504,6 +2527,16 @@ __global__ void tri_edge_bound_kernel(const rtl::GTri *__restrict__ tris, uint32
 // |e2| |d| (1 + 2^-24)^5 < 1.5 M |d| <= 0.75 x 2^124 in magnitude: inside the
 // range where rtm::rcp_rn is the division. M = 0 (no triangle with both edges)
 // leaves every direction; M = inf or NaN leaves none.
+float dmax2_of(uint32_t edge_bits) {
+  float M;
+  std::memcpy(&M, &edge_bits, 4);
+  if (M == 0.0f) return std::numeric_limits<float>::max();
+  if (!std::isfinite(M)) return 0.0f;
+  const double r = std::ldexp(1.0, 124) / (2.0 * (double)M * (1.0 + 1e-6));
+  const double r2 = r * r;
+  return r2 >= (double)std::numeric_limits<float>::max() ? std::numeric_limits<float>::max()
+                                                          : std::nextafter((float)r2, 0.0f);
+}
 int mesh_dmax2(rt_scene *s, uint32_t n_tris) {
   s->dmax2 = 0.0f;
   if (n_tris == 0) return RT_OK;
@@ -2517,22 +2550,19 @@ int mesh_dmax2(rt_scene *s, uint32_t n_tris) {
   if (e == hipSuccess) e = hipMemcpy(&h, d, 4, hipMemcpyDeviceToHost);
   HIP_NOTE(hipFree(d));
   if (e != hipSuccess) return set_err(RT_E_DEVICE, std::string("triangle edge bound: ") + hipGetErrorString(e));
-  float M;
-  std::memcpy(&M, &h, 4);
-  if (M == 0.0f) {
-    s->dmax2 = std::numeric_limits<float>::max();
-  } else if (std::isfinite(M)) {
-    const double r = std::ldexp(1.0, 124) / (2.0 * (double)M * (1.0 + 1e-6));
-    const double r2 = r * r;
-    s->dmax2 = r2 >= (double)std::numeric_limits<float>::max() ? std::numeric_limits<float>::max()
-                                                                  : std::nextafter((float)r2, 0.0f);
-  }
+  s->dmax2 = dmax2_of(h);
   return RT_OK;
 }
 
 int rt_scene_create_mesh(const float *vpos4, int64_t nverts, const uint32_t *idx, int64_t nidx,
                          rt_scene **out) {
+  return rt_scene_create_mesh_ex(vpos4, nverts, idx, nidx, 0u, out);
+}
+
+int rt_scene_create_mesh_ex(const float *vpos4, int64_t nverts, const uint32_t *idx, int64_t nidx,
+                            uint32_t flags, rt_scene **out) {
   if (!vpos4 || !idx || nverts <= 0 || nidx <= 0) return set_err(RT_E_INVALID, "empty mesh");
+  if (flags & ~RT_MESH_DYNAMIC) return set_err(RT_E_INVALID, "rt_scene_create_mesh_ex: unknown flags");
   rth::BVHGpu b;
   if (int rc = build_bvh(vpos4, nverts, idx, nidx, b, rth::kBvhTris | rth::kBvhDeviceTris)) return rc;
   int32_t maxd = 8;
@@ -2560,7 +2590,58 @@ int rt_scene_create_mesh(const float *vpos4, int64_t nverts, const uint32_t *idx
     rt_scene_destroy(s);
     return rc;
   }
+  s->n_tris = b.n_tris;
+  if (!b.nodes.empty())
+    for (uint32_t w : b.nodes[0].child) s->root_nchild += w != rtl::kInvalidChild;
+  if (flags & RT_MESH_DYNAMIC) {
+    const int64_t before = s->dev_bytes;
+    s->nverts = nverts;
+    s->level_first = rth::bvh_level_first(b.nodes);
+    if ((rc = upload(&s->d_idx, idx, (size_t)nidx, s->dev_bytes)) ||
+        (rc = upload(&s->d_vstage, (const float *)nullptr, 4 * (size_t)nverts, s->dev_bytes)) ||
+        (rc = upload(&s->d_edge, (const uint32_t *)nullptr, 1, s->dev_bytes)) || (rc = dynamic_host_words(s))) {
+      rt_scene_destroy(s);
+      return rc;
+    }
+    s->dyn_bytes = s->dev_bytes - before;
+    s->dynamic = true;
+  }
   *out = s;
+  return RT_OK;
+}
+
+// The refit behind both update entries: d_vpos4 (device, on the scene's
+// device) is read in stream order on `stream`; returns after the constants
+// are back on the host.
+static int update_vertices_device(rt_scene *s, const float *d_vpos4, hipStream_t st) {
+  const rti::RefitArgs a{s->d_nodes, s->d_tris, s->root, d_vpos4, s->d_idx, s->level_first.data(),
+                         s->level_first.empty() ? 0 : (int32_t)s->level_first.size() - 1};
+  if (int rc = rti::refit_launch(a, st)) return rc;
+  // the constants the host keeps: the triangles' edge bound (dmax2) and, for
+  // an inner root, its eight child boxes (root_child, root_box)
+  const bool inner = a.levels > 0;
+  HIP_TRY(hipMemsetAsync(s->d_edge, 0, 4, st));
+  if (s->n_tris) {
+    tri_edge_bound_kernel<<<(s->n_tris + 255) / 256, 256, 0, st>>>(s->d_tris, s->n_tris, s->d_edge);
+    HIP_TRY(hipGetLastError());
+  }
+  if (inner) HIP_TRY(hipMemcpyAsync(s->h_refit, s->d_nodes[0].box, 192, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(s->h_refit + 48, s->d_edge, 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  if (inner) {
+    std::memcpy(s->root_child, s->h_refit, 192);
+    const float inf = std::numeric_limits<float>::infinity();
+    float mn[3] = {inf, inf, inf}, mx[3] = {-inf, -inf, -inf};
+    for (uint32_t c = 0; c < s->root_nchild; ++c) {  // bvh_layout's root box: the union over c = 0 .. nchild-1
+      for (int k = 0; k < 3; ++k) {
+        mn[k] = std::min(mn[k], s->root_child[6 * c + 2 * k]);
+        mx[k] = std::max(mx[k], s->root_child[6 * c + 2 * k + 1]);
+      }
+    }
+    for (int k = 0; k < 3; ++k) { s->root_box[k] = mn[k]; s->root_box[3 + k] = mx[k]; }
+  }
+  s->dmax2 = s->n_tris ? dmax2_of(s->h_refit[48]) : 0.0f;
+  ++s->version;
   return RT_OK;
 }
 
@@ -2655,7 +2736,10 @@ int rt_scene_replicate(const rt_scene *src, int device, rt_scene **out) {
   s->grid_bricked = src->grid_bricked;
   s->oct_depth = src->oct_depth;
   s->plane = src->plane;
-  s->dev_bytes = src->dev_bytes;
+  s->n_tris = src->n_tris;
+  s->root_nchild = src->root_nchild;
+  s->version = src->version;
+  s->dev_bytes = src->dev_bytes - src->dyn_bytes;  // (a plain snapshot: not dynamic)
   s->sched_on = src->sched_on;
   s->coop = src->coop;
   s->pump_on = src->pump_on;
@@ -2682,6 +2766,72 @@ int rt_scene_replicate(const rt_scene *src, int device, rt_scene **out) {
 }
 
 int rt_scene_device(const rt_scene *s) { return s ? s->device : RT_E_INVALID; }
+
+static int check_update(const rt_scene *s, const float *vpos4, int64_t nverts, const char *who) {
+  if (!s) return set_err(RT_E_INVALID, std::string(who) + ": scene is NULL");
+  if (!vpos4) return set_err(RT_E_INVALID, std::string(who) + ": vertex pointer is NULL");
+  if (nverts <= 0) return set_err(RT_E_INVALID, std::string(who) + ": nverts must be positive");
+  if (s->kind != RT_SCENE_MESH) return set_err(RT_E_STATE, std::string(who) + ": not a mesh scene");
+  if (!s->dynamic)
+    return set_err(RT_E_STATE, std::string(who) + ": the mesh was not created with RT_MESH_DYNAMIC");
+  if (nverts != s->nverts)
+    return set_err(RT_E_INVALID, std::string(who) + ": nverts is " + std::to_string(nverts) + ", the mesh was created with " +
+                                     std::to_string(s->nverts));
+  return RT_OK;
+}
+
+int rt_scene_update_vertices_device(rt_scene *s, const float *d_vpos4, int64_t nverts, void *stream) {
+  if (int rc = check_update(s, d_vpos4, nverts, "rt_scene_update_vertices_device")) return rc;
+  return update_vertices_device(s, d_vpos4, (hipStream_t)stream);
+}
+
+int rt_scene_update_vertices(rt_scene *s, const float *vpos4, int64_t nverts) {
+  if (int rc = check_update(s, vpos4, nverts, "rt_scene_update_vertices")) return rc;
+  int prev = 0;
+  HIP_TRY(hipGetDevice(&prev));
+  HIP_TRY(hipSetDevice(s->device));
+  int rc = RT_OK;
+  if (const hipError_t e = rtdma::h2d(s->d_vstage, vpos4, 16 * (size_t)nverts, nullptr))
+    rc = set_err(RT_E_DEVICE, rterr::hip_fail("rt_scene_update_vertices: vertex upload", e));
+  if (!rc) rc = update_vertices_device(s, s->d_vstage, nullptr);
+  HIP_NOTE(hipSetDevice(prev));
+  return rc;
+}
+
+// Diagnostic (not part of include/rtamd.h): a mesh scene's device tree, as it
+// is now: n_inner GNode records (224 bytes each) and n_tris GTri records (48
+// bytes each). Two-call protocol: with nodes224 = tris48 = NULL only the counts
+// are returned; else *n_inner / *n_tris are the buffers' capacities.
+int rtx_scene_mesh_download(rt_scene *s, void *nodes224, int64_t *n_inner, void *tris48, int64_t *n_tris) {
+  if (!s || !n_inner || !n_tris) return set_err(RT_E_INVALID, "rtx_scene_mesh_download: NULL argument");
+  if (s->kind != RT_SCENE_MESH) return set_err(RT_E_STATE, "rtx_scene_mesh_download: not a mesh scene");
+  if (nodes224 || tris48) {
+    if (!nodes224 || !tris48 || *n_inner < (int64_t)s->n_inner || *n_tris < (int64_t)s->n_tris)
+      return set_err(RT_E_INVALID, "rtx_scene_mesh_download: buffers too small");
+    int prev = 0;
+    HIP_TRY(hipGetDevice(&prev));
+    HIP_TRY(hipSetDevice(s->device));
+    hipError_t e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = rtdma::d2h(nodes224, s->d_nodes, (size_t)s->n_inner * sizeof(rtl::GNode), nullptr);
+    if (e == hipSuccess) e = rtdma::d2h(tris48, s->d_tris, (size_t)s->n_tris * sizeof(rtl::GTri), nullptr);
+    HIP_NOTE(hipSetDevice(prev));
+    if (e != hipSuccess) return set_err(RT_E_DEVICE, rterr::hip_fail("rtx_scene_mesh_download", e));
+  }
+  *n_inner = s->n_inner;
+  *n_tris = s->n_tris;
+  return RT_OK;
+}
+
+// Diagnostic (not part of include/rtamd.h): the constants the host keeps of a
+// mesh scene: root_box[6], the root's child boxes root_child[48], dmax2.
+int rtx_scene_mesh_constants(const rt_scene *s, float root_box[6], float root_child[48], float *dmax2) {
+  if (!s) return set_err(RT_E_INVALID, "rtx_scene_mesh_constants: scene is NULL");
+  if (s->kind != RT_SCENE_MESH) return set_err(RT_E_STATE, "rtx_scene_mesh_constants: not a mesh scene");
+  if (root_box) std::memcpy(root_box, s->root_box, sizeof s->root_box);
+  if (root_child) std::memcpy(root_child, s->root_child, sizeof s->root_child);
+  if (dmax2) *dmax2 = s->dmax2;
+  return RT_OK;
+}
 
 int rt_scene_get_plane(const rt_scene *s, int *enabled, float normal[3], float *offset) {
   if (!s) return set_err(RT_E_INVALID, "scene is NULL");
@@ -2741,9 +2891,10 @@ int rt_scene_destroy(rt_scene *s) {
     if (x) HIP_NOTE(hipStreamSynchronize(x));
   if (s->sched_os) HIP_NOTE(hipStreamSynchronize(s->sched_os));
   void *ptrs[] = {s->d_nodes, s->d_tris, s->d_vals, s->d_child, s->d_ovals, s->d_color, s->d_t,
-                  s->d_cost[0], s->d_order[0], s->d_cost[1], s->d_order[1]};
+                  s->d_cost[0], s->d_order[0], s->d_cost[1], s->d_order[1], s->d_idx, s->d_vstage, s->d_edge};
   for (void *p : ptrs)
     if (p) HIP_NOTE(hipFree(p));
+  if (s->h_refit) HIP_NOTE(hipHostFree(s->h_refit));
   for (hipEvent_t e : s->ord_ev)
     if (e) HIP_NOTE(hipEventDestroy(e));
   if (s->frame_ev) HIP_NOTE(hipEventDestroy(s->frame_ev));
@@ -3404,5 +3555,27 @@ int render_band_host(rt_scene *s, const rt_render_params *p, uint32_t *dc, float
   fa.flags |= kFlagHostFrame | kFlagNatural | (d_span ? kFlagRowSpan : 0u);
   fa.hit_box = d_span;
   return launch_render(s, fa, stream);
+}
+
+uint64_t scene_version(const rt_scene *s) { return s ? s->version : 0; }
+
+// A replica (rt_scene_replicate) of mesh scene `src` brought up to src's last
+// update: nodes and triangles copied device to device (the sizes never
+// change), the three host constants taken over. Blocking; the caller has
+// drained the streams that use the replica.
+int scene_refresh_replica(rt_scene *rep, const rt_scene *src) {
+  if (!rep || !src || rep->kind != src->kind) return set_err(RT_E_INVALID, "scene_refresh_replica: bad arguments");
+  if (rep->version == src->version || src->kind != RT_SCENE_MESH) return RT_OK;
+  if (rep->n_inner != src->n_inner || rep->n_tris != src->n_tris)
+    return set_err(RT_E_STATE, "scene_refresh_replica: the replica is not of this scene");
+  if (src->n_inner)
+    HIP_TRY(hipMemcpyPeer(rep->d_nodes, rep->device, src->d_nodes, src->device, (size_t)src->n_inner * sizeof(rtl::GNode)));
+  if (src->n_tris)
+    HIP_TRY(hipMemcpyPeer(rep->d_tris, rep->device, src->d_tris, src->device, (size_t)src->n_tris * sizeof(rtl::GTri)));
+  std::memcpy(rep->root_box, src->root_box, sizeof rep->root_box);
+  std::memcpy(rep->root_child, src->root_child, sizeof rep->root_child);
+  rep->dmax2 = src->dmax2;
+  rep->version = src->version;
+  return RT_OK;
 }
 }  // namespace rti

@@ -96,6 +96,10 @@ struct HostStage {
 namespace rti {  // librtamd-internal entry points shared between its translation units
 int render_band_host(rt_scene *s, const rt_render_params *p, uint32_t *dc, float *dt, int32_t W, int32_t H,
                      const rt_tile *tile, int32_t *d_span, hipStream_t stream);
+// A scene's update counter (rt_scene_update_vertices*), and a replica of it
+// brought up to date: rt_multi re-copies its replicas when the root has moved.
+uint64_t scene_version(const rt_scene *s);
+int scene_refresh_replica(rt_scene *rep, const rt_scene *src);
 }  // namespace rti
 
 #define HIP_NOTE(expr) ((void)rterr::note(#expr, (expr)))

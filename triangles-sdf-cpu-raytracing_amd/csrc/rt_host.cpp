@@ -650,6 +650,71 @@ void bvh_layout(const float *vpos4, const uint32_t *idx, int64_t nidx, HostNodes
   fill_tris();
 }
 
+// ---------------------------------------------------------------- refit ---
+std::vector<uint32_t> bvh_level_first(const std::vector<rtl::GNode> &nodes) {
+  std::vector<uint32_t> first;
+  if (nodes.empty()) return first;
+  uint32_t lo = 0, hi = 1;
+  for (;;) {
+    first.push_back(lo);
+    uint32_t last = 0;  // the largest inner child index of this level
+    for (uint32_t i = lo; i < hi; ++i)
+      for (uint32_t w : nodes[i].child)
+        if (!(w & rtl::kLeafBit)) last = std::max(last, w);
+    if (last < hi || last >= nodes.size()) break;  // (no inner child: the deepest level)
+    lo = hi;
+    hi = last + 1;
+  }
+  first.push_back((uint32_t)nodes.size());
+  return first;
+}
+
+void refit_bvh8(BVHGpu &b, const float *vpos4, const uint32_t *idx) {
+  auto leaf_box = [&](uint32_t word) {
+    const uint32_t first = (word & ~rtl::kLeafBit) >> 3, nt = (word & 7u) + 1u;
+    Box box = empty_box();
+    for (uint32_t k = 0; k < nt; ++k) {
+      rtl::GTri &g = b.tris[first + k];
+      const uint32_t *tv = idx + 3 * (size_t)g.orig_id;
+      float v[3][3];
+      for (int j = 0; j < 3; ++j) {
+        const float *p = vpos4 + 4 * (size_t)tv[j];
+        const float w = p[3];
+        v[j][0] = p[0] / w; v[j][1] = p[1] / w; v[j][2] = p[2] / w;
+        grow(box, Box{{v[j][0], v[j][1], v[j][2]}, {v[j][0], v[j][1], v[j][2]}});
+      }
+      g.v0x = v[0][0]; g.v0y = v[0][1]; g.v0z = v[0][2];
+      g.e1x = v[1][0] - v[0][0]; g.e1y = v[1][1] - v[0][1]; g.e1z = v[1][2] - v[0][2];
+      g.e2x = v[2][0] - v[0][0]; g.e2y = v[2][1] - v[0][1]; g.e2z = v[2][2] - v[0][2];
+      g.pad1 = g.pad2 = 0.0f;
+    }
+    return box;
+  };
+  // the union of a node's child boxes, c = 0 .. nchild-1
+  auto node_box = [&](const rtl::GNode &n) {
+    Box u = empty_box();
+    for (int c = 0; c < 8; ++c)
+      if (n.child[c] != rtl::kInvalidChild)
+        grow(u, Box{{n.box[c][0], n.box[c][2], n.box[c][4]}, {n.box[c][1], n.box[c][3], n.box[c][5]}});
+    return u;
+  };
+  if (b.nodes.empty()) {  // root is a leaf: only its triangles
+    if (b.root_word != rtl::kInvalidChild) leaf_box(b.root_word);
+    return;
+  }
+  for (size_t i = b.nodes.size(); i-- > 0;) {  // children have larger indices: they are done
+    rtl::GNode &n = b.nodes[i];
+    for (int c = 0; c < 8; ++c) {
+      const uint32_t w = n.child[c];
+      if (w == rtl::kInvalidChild) continue;
+      const Box box = (w & rtl::kLeafBit) ? leaf_box(w) : node_box(b.nodes[w]);
+      for (int k = 0; k < 3; ++k) { n.box[c][2 * k] = box.mn[k]; n.box[c][2 * k + 1] = box.mx[k]; }
+    }
+  }
+  const Box u = node_box(b.nodes[0]);
+  for (int k = 0; k < 3; ++k) { b.root_box[k] = u.mn[k]; b.root_box[3 + k] = u.mx[k]; }
+}
+
 // --------------------------------------------------------------- octree ---
 bool flatten_octree(const uint8_t *nodes36, int64_t count, OctGpu &out, std::string &err) {
   out = OctGpu();

@@ -140,6 +140,22 @@ struct HostNodes {
 // only. host_tris false: the leaf table instead of BVHGpu::tris.
 void bvh_layout(const float *vpos4, const uint32_t *idx, int64_t nidx, HostNodes H,
                 const std::vector<uint32_t> &cur, BVHGpu &out, unsigned want, bool host_tris);
+// First node index of every depth level of a laid-out tree, plus the node count
+// as the last entry (levels = size() - 1; empty for a root-is-leaf tree).
+// bvh_layout stores inner nodes in BFS order, so a level is one index range
+// and every child index is larger than its parent's.
+std::vector<uint32_t> bvh_level_first(const std::vector<rtl::GNode> &nodes);
+// Refit: the tree of the same topology over new vertex positions. Every GTri
+// of b.tris is rewritten (v /= v.w, e1, e2; orig_id kept) and every child box
+// becomes the min/max of its subtree; child words, empty slots (+inf boxes)
+// and the triangle order stay. b.root_box is refreshed. This is the
+// definition of the evaluation order that the device refit (rt_refit.hip)
+// reproduces bit for bit: nodes from the last to the first; a leaf child's box
+// starts from the empty box and grows over its triangles in slot order,
+// vertices 0, 1, 2; an inner child's box grows over that node's child boxes
+// c = 0 .. nchild-1; both with std::min / std::max (left operand kept on
+// ties). Needs the host triangles (kBvhTris from build_bvh8).
+void refit_bvh8(BVHGpu &b, const float *vpos4, const uint32_t *idx);
 // The same tree built on the current HIP device (rt_bvhgpu.hip): libstdc++'s
 // introsort replicated with parallel Hoare partitions, SAH sweeps as device
 // scans. Identical output to build_bvh8.

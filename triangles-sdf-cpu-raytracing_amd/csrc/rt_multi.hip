@@ -218,6 +218,17 @@ int sync_planes(rt_multi *m) {
   if (int rc = rt_scene_get_plane(m->root, &on, nrm, &off)) return rc;
   for (int32_t i = 1; i < m->n; ++i)
     if (int rc = rt_scene_set_plane(m->scene[i], on, nrm, off)) return rc;
+  // and its geometry, when rt_scene_update_vertices* moved it since the
+  // replicas were made or last refreshed: the update has completed on the root
+  // (it waits before it returns), each slot's stream is drained, then the
+  // replica's arrays are re-copied
+  const uint64_t v = rti::scene_version(m->root);
+  for (int32_t i = 1; i < m->n; ++i) {
+    if (rti::scene_version(m->scene[i]) == v) continue;
+    HIP_TRY(hipSetDevice(m->dev[i]));
+    HIP_TRY(hipStreamSynchronize(m->st[i]));
+    if (int rc = rti::scene_refresh_replica(m->scene[i], m->root)) return rc;
+  }
   return RT_OK;
 }
 

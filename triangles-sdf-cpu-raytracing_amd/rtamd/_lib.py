@@ -18,6 +18,7 @@ RT_FLAG_CLEAR = 1
 RT_FLAG_TILE_NATURAL = 2
 RT_FLAG_HITS_ONLY = 4
 RT_RAYS_ANY_HIT = 1
+RT_MESH_DYNAMIC = 1
 RT_IPC_HANDLE_BYTES = 64
 RT_SCENE_MESH, RT_SCENE_GRID, RT_SCENE_OCTREE = 1, 2, 3
 
@@ -79,6 +80,10 @@ _SIGS = {
     "rt_set_bvh_builder": (C.c_int, [C.c_int]),
     "rt_scene_create_mesh": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
                                        C.POINTER(C.c_void_p)]),
+    "rt_scene_create_mesh_ex": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_uint32,
+                                          C.POINTER(C.c_void_p)]),
+    "rt_scene_update_vertices": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
+    "rt_scene_update_vertices_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "rt_scene_create_grid": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
     "rt_scene_create_octree": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(C.c_void_p)]),
     "rt_scene_set_plane": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_float]),
@@ -152,6 +157,13 @@ EXPORTED = tuple(_SIGS)
 _XSIGS = {
     "rtx_set_tile_cull": (C.c_int, [C.c_int]),
     "rtx_cull_rect": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    # the refit's diagnostics: a mesh scene's device tree and host constants,
+    # and the host restatement of build + refit (no GPU)
+    "rtx_scene_mesh_download": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_void_p,
+                                          C.POINTER(C.c_int64)]),
+    "rtx_scene_mesh_constants": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]),
+    "rtx_bvh_refit_host": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                     C.POINTER(C.c_int64), C.c_void_p, C.POINTER(C.c_int64)]),
 }
 
 

@@ -23,8 +23,8 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from ._lib import (RT_FLAG_CLEAR, RT_FLAG_HITS_ONLY, RT_RAYS_ANY_HIT, CameraState, RayBatch, RenderParams, RtError,
-                   Tile, check, lib)
+from ._lib import (RT_FLAG_CLEAR, RT_FLAG_HITS_ONLY, RT_MESH_DYNAMIC, RT_RAYS_ANY_HIT, CameraState, RayBatch,
+                   RenderParams, RtError, Tile, check, lib)
 
 __all__ = [
     "ShadingMode", "SimpleMesh", "FrameBuffer", "Camera", "Renderer", "HitInfo", "IScene",
@@ -374,18 +374,39 @@ class IScene:
 class BVHBuilder(IScene):
     """BVHBuilder::perform(mesh): host SAH BVH8 build + device upload."""
 
-    def __init__(self, mesh: SimpleMesh | None = None):
+    def __init__(self, mesh: SimpleMesh | None = None, dynamic: bool = False):
         if mesh is not None:
-            self.perform(mesh)
+            self.perform(mesh, dynamic)
 
-    def perform(self, mesh: SimpleMesh):
+    def perform(self, mesh: SimpleMesh, dynamic: bool = False):
+        """dynamic: the vertices may be moved afterwards (update_vertices*,
+        RT_MESH_DYNAMIC); the scene then keeps its index array and a vertex
+        staging buffer on the device."""
         self.close()
         v = np.ascontiguousarray(mesh.vPos4f, np.float32)
         i = np.ascontiguousarray(mesh.indices, np.uint32)
         h = C.c_void_p()
-        check(lib().rt_scene_create_mesh(_p(v), len(v), _p(i), len(i), C.byref(h)))
+        if dynamic:
+            check(lib().rt_scene_create_mesh_ex(_p(v), len(v), _p(i), len(i), RT_MESH_DYNAMIC, C.byref(h)))
+        else:
+            check(lib().rt_scene_create_mesh(_p(v), len(v), _p(i), len(i), C.byref(h)))
         self._h = h
         return self
+
+    def update_vertices(self, vPos4f):
+        """Refit the tree to new positions (float32 [N, 4] on the host, N as at
+        creation): rt_scene_update_vertices. Returns when the scene is updated."""
+        v = np.ascontiguousarray(vPos4f, np.float32)
+        if v.ndim != 2 or v.shape[1] != 4:
+            raise RtError(f"update_vertices: shape {v.shape}, expected [N, 4]")
+        check(lib().rt_scene_update_vertices(self._handle(), _p(v), len(v)))
+
+    def update_vertices_device(self, ptr: int, nverts: int, stream: int | None = None):
+        """The same from device memory (float32[4 * nverts] at ptr, e.g. a torch
+        tensor's data_ptr()), queued on `stream` after the work already there:
+        rt_scene_update_vertices_device. One host wait; no allocation."""
+        check(lib().rt_scene_update_vertices_device(self._handle(), C.c_void_p(ptr) if ptr else None, int(nverts),
+                                                    C.c_void_p(stream) if stream else None))
 
 
 class SDFGrid(IScene):

@@ -7,6 +7,12 @@ rays that already live on the GPU, through rt_trace_rays_device.
 The launch is queued on torch.cuda.current_stream(): it is ordered with the
 torch work around it, and nothing is copied or synchronised. torch is
 imported when trace() is called, so ``import rtamd`` stays torch-free.
+
+    torch_rays.update_vertices(scene, verts)
+
+moves the vertices of a dynamic mesh scene (BVHBuilder(mesh, dynamic=True))
+to a tensor's positions: the BVH8 refit of rt_scene_update_vertices_device, on
+the same stream.
 """
 from __future__ import annotations
 
@@ -52,6 +58,35 @@ def _interval(torch, x, what, n, device):
     if not x.is_contiguous():
         raise ValueError(f"{what}: not contiguous")
     return 0.0, x
+
+
+def update_vertices(scene, verts) -> None:
+    """Refit a dynamic mesh scene (rtamd.BVHBuilder(mesh, dynamic=True)) to the
+    positions in `verts`, a contiguous float32 tensor on the scene's device
+    with one row per creation vertex: [V, 4] (x, y, z, w) is read in place;
+    [V, 3] gets a w = 1 column through torch first -- the one allocation, a
+    [V, 4] tensor. The refit is queued on torch.cuda.current_stream(), after
+    the torch kernels that produced `verts` there, and the call returns after
+    its one host wait (rt_scene_update_vertices_device). Raises ValueError on a
+    bad tensor before anything is launched."""
+    import torch
+
+    device = int(lib().rt_scene_device(scene._handle()))
+    if not isinstance(verts, torch.Tensor):
+        raise ValueError(f"verts: expected a torch tensor, got {type(verts).__name__}")
+    if verts.dtype != torch.float32:
+        raise ValueError(f"verts: dtype {verts.dtype}, expected torch.float32")
+    if verts.dim() != 2 or verts.shape[1] not in (3, 4) or verts.shape[0] == 0:
+        raise ValueError(f"verts: shape {tuple(verts.shape)}, expected [V, 4] or [V, 3]")
+    if verts.device.type != "cuda" or verts.device.index != device:
+        raise ValueError(f"verts: on {verts.device}, the scene is on HIP device {device}")
+    if not verts.is_contiguous():
+        raise ValueError("verts: not contiguous")
+    with torch.cuda.device(device):
+        if verts.shape[1] == 3:
+            verts = torch.cat([verts, verts.new_ones((verts.shape[0], 1))], dim=1)
+        scene.update_vertices_device(verts.data_ptr(), verts.shape[0],
+                                     stream=torch.cuda.current_stream(device).cuda_stream)
 
 
 def trace(scene, origins, dirs, tnear=0.01, tfar=100.0, any_hit=False, outputs=OUTPUTS) -> RayHits:
