@@ -39,7 +39,7 @@ enum rt_status {
 /* ShadingMode, same order as the reference enum (src/raytracing.hpp:99). */
 enum rt_shading_mode { RT_SHADING_NORMAL = 0, RT_SHADING_LAMBERT = 1, RT_SHADING_COLOR = 2 };
 
-enum rt_scene_kind { RT_SCENE_MESH = 1, RT_SCENE_GRID = 2, RT_SCENE_OCTREE = 3 };
+enum rt_scene_kind { RT_SCENE_MESH = 1, RT_SCENE_GRID = 2, RT_SCENE_OCTREE = 3, RT_SCENE_INSTANCED = 4 };
 
 /* rt_render flags */
 #define RT_FLAG_CLEAR 1u /* treat the framebuffer as FrameBuffer::clear()ed (color=0, t=+inf;
@@ -208,6 +208,95 @@ int rt_scene_device(const rt_scene *s);
 /* The plane last given to rt_scene_set_plane (enabled, normal, offset). */
 int rt_scene_get_plane(const rt_scene *s, int *enabled, float normal[3], float *offset);
 
+/* ---- instanced scenes: rigid (affine) copies of mesh scenes under one query --
+ * An instanced scene (RT_SCENE_INSTANCED) is a list of K >= 1 instances over
+ * B >= 1 bottom-level scenes ("BLAS"): existing RT_SCENE_MESH scenes on the
+ * same device, dynamic or not. Instance i is {blas index, xform[12]}; xform is
+ * the object-to-world affine map, row-major 3x4:
+ *     p_world[r] = x[4r]*p.x + x[4r+1]*p.y + x[4r+2]*p.z + x[4r+3].
+ * The library stores its inverse M (world to object, the same layout), as
+ * rt_affine_inverse computes it. No reference counterpart: the reference's
+ * scenes are one mesh in one pose.
+ *
+ * THE ORDER IS THE DEFINITION. The reference's triangle test has no t range
+ * (see rt_scene_update_vertices above: a triangle hit before tNear is reported
+ * when its leaf's box reaches into [tNear, tFar]), so no order-free definition
+ * is exact. For a ray (o, d, tNear, tFar), in float arithmetic without fusing:
+ *     best = +inf; win = none
+ *     for i = 0 .. K-1 in index order, skipping disabled (and skipped) instances:
+ *         o'[r] = ((M[4r]*o.x + M[4r+1]*o.y) + M[4r+2]*o.z) + M[4r+3]
+ *         d'[r] =  (M[4r]*d.x + M[4r+1]*d.y) + M[4r+2]*d.z     (not renormalised: t is shared)
+ *         tf_i  = best < tFar ? best : tFar
+ *         h = IScene::intersect of BLAS[blas_i] alone (its own plane ignored) on (o', d', tNear, tf_i)
+ *         if h.hit and h.t < best: best = h.t; win = (i, h)    (ties keep the lower index)
+ * A hit gives t = best and prim = ((int64)i << 32) | original triangle id
+ * (misses stay -1, the plane -2). With n the object-space normal the BLAS
+ * reports, w[c] = (M[c]*n.x + M[4+c]*n.y) + M[8+c]*n.z (the inverse transpose)
+ * and normal = w / sqrt((w.x*w.x + w.y*w.y) + w.z*w.z), computed for the winner
+ * only, after the loop, not flipped. The instanced scene's own plane
+ * (rt_scene_set_plane, world space) takes part exactly as for the other kinds.
+ * RT_RAYS_ANY_HIT is the OR over the instances of the BLAS any hit on
+ * (o', d', tNear, tFar), stopping at the first hit; it equals the closest-hit
+ * query's flag. There is no top-level tree: every ray
+ * visits every instance, and skips one only by the traversal's own root-box
+ * test on the transformed ray, which cannot change an answer.
+ *
+ * rt_trace_rays_device and rt_intersect_rays accept the kind with all their
+ * argument rules; rt_scene_kind, rt_scene_device, rt_scene_device_bytes (the
+ * instance and BLAS tables only), rt_scene_set_plane, rt_scene_get_plane and
+ * rt_scene_destroy work. Every other entry that takes a scene (rt_render*,
+ * rt_bench_frames, rt_count_work, rt_scene_replicate, rt_multi_create,
+ * rt_scene_update_vertices*, rt_scene_bvh_stats) returns RT_E_STATE and
+ * touches nothing.
+ * A BLAS refitted by rt_scene_update_vertices* is seen by the next trace: each
+ * trace compares the BLAS scenes' update counters with the ones it last saw
+ * and rewrites stale table entries in stream order ahead of its launch,
+ * without a host wait. The caller orders BLAS and pose updates against traces
+ * that are still running on OTHER streams. */
+#define RT_INSTANCE_DISABLED 1u /* the instance is skipped by every query */
+typedef struct rt_instance {
+  int32_t blas;    /* index into the BLAS list given at creation */
+  uint32_t flags;  /* 0 or RT_INSTANCE_DISABLED */
+  float xform[12]; /* object to world, row-major 3x4 */
+} rt_instance;
+/* Host-only: inv = the inverse of the affine map xform (both row-major 3x4),
+ * the one definition of M: cofactors over the determinant expanded along the
+ * first row, then -(inv3 * translation) summed left to right; exact for the
+ * identity, translations, power-of-two scales and signed axis permutations.
+ * The device pose update runs the same code and gives the same bits.
+ * RT_E_INVALID when the 3x3 determinant is zero or not finite, or when any
+ * entry is not finite (inv is then untouched). */
+int rt_affine_inverse(const float xform[12], float inv[12]);
+/* The BLAS scenes are not owned and must outlive the handle, as with
+ * rt_multi_create. The scene is created on the current device. RT_E_STATE for
+ * a BLAS that is not a mesh; RT_E_INVALID for a NULL pointer, nblas or
+ * ninst < 1, a blas index out of range, unknown flag bits, a BLAS on another
+ * device, or a matrix rt_affine_inverse refuses. */
+int rt_scene_create_instanced(rt_scene *const *blas, int32_t nblas, const rt_instance *inst, int32_t ninst,
+                              rt_scene **out);
+/* Replace instances first .. first + count - 1 from a host buffer (blas, flags
+ * and pose); validated as at creation, and a refused call leaves the scene
+ * unchanged. The records are copied to the device before the call returns. */
+int rt_scene_update_instances(rt_scene *s, int32_t first, int32_t count, const rt_instance *inst);
+/* New poses from DEVICE memory: count object-to-world matrices (12 floats
+ * each) at d_xform12 are inverted by a kernel queued on `stream` (hipStream_t
+ * or NULL), so the buffer may be the output of the caller's previous kernel
+ * there. The call only launches: no allocation, no copy, no host wait (nothing
+ * the host keeps depends on a pose). The scene's device must be the current
+ * one. Device data cannot be validated: an instance whose matrix
+ * rt_affine_inverse would refuse is skipped by every query until its next
+ * update, and an accepted matrix clears that mark. The blas index and flags
+ * given at creation or by rt_scene_update_instances stay. */
+int rt_scene_update_instances_device(rt_scene *s, int32_t first, int32_t count, const float *d_xform12,
+                                     void *stream);
+/* What the device holds for instances first .. first + count - 1, after one
+ * device synchronisation: inst[j] = {blas, flags, the inverse of the stored M
+ * (the given xform up to rounding; zeros for a skipped instance)}, inv12[12j ..]
+ * = M itself, skipped[j] = 1 for an instance the device pose update refused.
+ * Any output may be NULL. */
+int rt_scene_get_instances(const rt_scene *s, int32_t first, int32_t count, rt_instance *inst, float *inv12,
+                           uint32_t *skipped);
+
 /* ---- frames ------------------------------------------------------------- */
 /* Renderer::draw on HOST buffers color[W*H] (RGBA8 packed, R in the low byte)
  * and t[W*H] (row-major y*W+x). Uploads, renders, downloads, synchronises.
@@ -339,7 +428,8 @@ int rt_ipc_close(void *d_ptr);
  * as HitInfo (src/raytracing.hpp:67-73; normal NOT flipped toward the ray),
  * prim[i] = primitive id (mesh: original triangle index in OBJ face order;
  * grid: linear index of the c0 cell of the hit sample; octree: leaf node
- * index; plane: -2; miss: -1). */
+ * index; instanced: (instance << 32) | original triangle index; plane: -2;
+ * miss: -1). */
 int rt_intersect_rays(rt_scene *s, const float *o, const float *d, int64_t n, float tnear,
                       float tfar, int32_t *hit, float *t, float *normal, int64_t *prim);
 /* IScene::intersect (src/raytracing.hpp:77-79) for rays that are already on

@@ -277,6 +277,46 @@ inline void loadSDFOctree(SDFOctree &o, const std::string &path) {  // octree_ra
   o.upload();
 }
 
+// Rigid (affine) copies of mesh scenes under one ray query
+// (rt_scene_create_instanced; no reference counterpart). Ray queries only:
+// intersect / intersectDevice, with prim = (instance << 32) | triangle id. The
+// BLAS scenes are not owned and must outlive this scene.
+class InstancedScene : public IScene {
+ public:
+  void perform(const std::vector<const BVHBuilder *> &blas, const std::vector<rt_instance> &instances) {
+    std::vector<rt_scene *> h;
+    for (const BVHBuilder *b : blas) h.push_back(b ? b->handle() : nullptr);
+    rt_scene *s = nullptr;
+    check(rt_scene_create_instanced(h.data(), (int32_t)h.size(), instances.data(), (int32_t)instances.size(), &s));
+    reset(s);
+    count_ = (int32_t)instances.size();
+  }
+  int32_t size() const { return count_; }
+  // New blas / flags / poses for instances first .. first + n - 1 (host
+  // buffer, validated; a refused call changes nothing).
+  void updateInstances(int32_t first, const std::vector<rt_instance> &instances) const {
+    check(rt_scene_update_instances(handle(), first, (int32_t)instances.size(), instances.data()));
+  }
+  // New poses from device memory (12 floats per matrix, object to world),
+  // inverted by a kernel queued on `stream`; only launches.
+  void updateInstancesDevice(int32_t first, int32_t count, const float *d_xform12, void *stream = nullptr) const {
+    check(rt_scene_update_instances_device(handle(), first, count, d_xform12, stream));
+  }
+  // What the device holds (one synchronisation); inv12 / skipped may be null.
+  std::vector<rt_instance> instances(std::vector<float> *inv12 = nullptr,
+                                     std::vector<uint32_t> *skipped = nullptr) const {
+    std::vector<rt_instance> out((size_t)count_);
+    if (inv12) inv12->resize((size_t)count_ * 12);
+    if (skipped) skipped->resize((size_t)count_);
+    check(rt_scene_get_instances(handle(), 0, count_, out.data(), inv12 ? inv12->data() : nullptr,
+                                 skipped ? skipped->data() : nullptr));
+    return out;
+  }
+
+ private:
+  int32_t count_ = 0;
+};
+
 // SceneUnion(scene, plane) (raytracing.hpp:83-97): the reference application
 // only ever unions a scene with the ground plane (main.cpp:64, 190).
 struct SceneUnion {

@@ -31,6 +31,7 @@
 #include "../../include/rtamd.h"
 #include "rt_error.h"
 #include "rt_host.h"
+#include "rt_instances.h"
 #include "rt_layout.h"
 #include "rt_math.h"
 #include "rt_queue.h"
@@ -1459,6 +1460,15 @@ struct rt_scene {
   rtl::OctWord *d_child = nullptr;
   rtl::OctVals *d_ovals = nullptr;
   int32_t oct_depth = 0;
+  // instanced (RT_SCENE_INSTANCED): the instance records and the table of the
+  // bottom-level scenes' MeshDev on the device; the scenes themselves (not
+  // owned) and the update counter each table entry was written from. Nothing
+  // here depends on a pose.
+  rti::InstRec *d_inst = nullptr;
+  MeshDev *d_blas = nullptr;
+  int32_t ninst = 0;
+  std::vector<rt_scene *> blas;
+  std::vector<uint64_t> blas_seen;
   PlaneDev plane{};
   int64_t dev_bytes = 0;
   // cached buffers for host-buffer entry points
@@ -2391,10 +2401,27 @@ int launch_trace(rt_scene *s, const rt_ray_batch &b, int mode, hipStream_t strea
       case 15: launch_trace_t<OctS<false>, 15>(OctS<false>{od}, s->plane, b, mode, stream); break;
       default: launch_trace_t<OctS<false>, 31>(OctS<false>{od}, s->plane, b, mode, stream); break;
     }
+  } else if (s->kind == RT_SCENE_INSTANCED) {
+    // a bottom-level scene refitted since its table entry was written: the
+    // entry is rewritten in stream order ahead of the trace, no host wait
+    for (size_t j = 0; j < s->blas.size(); ++j) {
+      if (s->blas[j]->version == s->blas_seen[j]) continue;
+      if (int rc = rti::blas_entry_launch(s->d_blas + j, mesh_dev(s->blas[j]), stream)) return rc;
+      s->blas_seen[j] = s->blas[j]->version;
+    }
+    return rti::trace_instances_launch(rti::InstArgs{s->d_inst, s->d_blas, s->ninst, s->maxd}, s->plane, b, mode,
+                                       stream);
   } else {
     return set_err(RT_E_STATE, "scene has no geometry");
   }
   HIP_TRY(hipGetLastError());
+  return RT_OK;
+}
+
+// the entries that render frames or copy a scene take no instanced scene
+int no_instanced(const rt_scene *s, const char *who) {
+  if (s && s->kind == RT_SCENE_INSTANCED)
+    return set_err(RT_E_STATE, std::string(who) + ": not available for an instanced scene");
   return RT_OK;
 }
 
@@ -2712,6 +2739,7 @@ int rt_scene_create_octree(const void *nodes36, int64_t count, rt_scene **out) {
 
 int rt_scene_replicate(const rt_scene *src, int device, rt_scene **out) {
   if (!src || !out) return set_err(RT_E_INVALID, "bad arguments");
+  if (int rc = no_instanced(src, "rt_scene_replicate")) return rc;
   *out = nullptr;
   int ndev = 0;
   HIP_TRY(hipGetDeviceCount(&ndev));
@@ -2777,6 +2805,124 @@ static int check_update(const rt_scene *s, const float *vpos4, int64_t nverts, c
   if (nverts != s->nverts)
     return set_err(RT_E_INVALID, std::string(who) + ": nverts is " + std::to_string(nverts) + ", the mesh was created with " +
                                      std::to_string(s->nverts));
+  return RT_OK;
+}
+
+// ---- instanced scenes (include/rtamd.h; kernels in rt_instances.hip) -------
+namespace {
+// one rt_instance -> its device record; `who` names the entry in the message
+int instance_record(const rt_instance &in, int32_t nblas, int64_t index, const char *who, rti::InstRec &r) {
+  const std::string at = std::string(who) + ": instance " + std::to_string(index);
+  if (in.blas < 0 || in.blas >= nblas) return set_err(RT_E_INVALID, at + ": blas index out of range");
+  if (in.flags & ~RT_INSTANCE_DISABLED) return set_err(RT_E_INVALID, at + ": unknown flag bits");
+  if (!rti::affine_inverse(in.xform, r.m))
+    return set_err(RT_E_INVALID, at + ": the matrix is singular or has a non-finite entry");
+  r.blas = in.blas;
+  r.flags = in.flags;
+  r.skipped = 0;
+  r.pad = 0;
+  return RT_OK;
+}
+
+int instance_range(const rt_scene *s, int32_t first, int32_t count, const char *who) {
+  if (!s) return set_err(RT_E_INVALID, std::string(who) + ": scene is NULL");
+  if (s->kind != RT_SCENE_INSTANCED) return set_err(RT_E_STATE, std::string(who) + ": not an instanced scene");
+  if (first < 0 || count < 0 || (int64_t)first + count > s->ninst)
+    return set_err(RT_E_INVALID, std::string(who) + ": range outside the scene's " + std::to_string(s->ninst) +
+                                     " instances");
+  return RT_OK;
+}
+}  // namespace
+
+int rt_scene_create_instanced(rt_scene *const *blas, int32_t nblas, const rt_instance *inst, int32_t ninst,
+                              rt_scene **out) {
+  const char *who = "rt_scene_create_instanced";
+  if (!blas || !inst || !out) return set_err(RT_E_INVALID, std::string(who) + ": NULL argument");
+  *out = nullptr;
+  if (nblas < 1 || ninst < 1) return set_err(RT_E_INVALID, std::string(who) + ": nblas and ninst must be at least 1");
+  int dev = 0;
+  HIP_TRY(hipGetDevice(&dev));
+  int32_t maxd = 1;
+  for (int32_t j = 0; j < nblas; ++j) {
+    if (!blas[j]) return set_err(RT_E_INVALID, std::string(who) + ": BLAS " + std::to_string(j) + " is NULL");
+    if (blas[j]->kind != RT_SCENE_MESH)
+      return set_err(RT_E_STATE, std::string(who) + ": BLAS " + std::to_string(j) + " is not a mesh scene");
+    if (blas[j]->device != dev)
+      return set_err(RT_E_INVALID, std::string(who) + ": BLAS " + std::to_string(j) + " lives on device " +
+                                       std::to_string(blas[j]->device) + ", the current device is " + std::to_string(dev));
+    maxd = std::max(maxd, blas[j]->maxd);
+  }
+  std::vector<rti::InstRec> recs((size_t)ninst);
+  for (int32_t i = 0; i < ninst; ++i)
+    if (int rc = instance_record(inst[i], nblas, i, who, recs[(size_t)i])) return rc;
+  std::vector<MeshDev> tab;
+  for (int32_t j = 0; j < nblas; ++j) tab.push_back(mesh_dev(blas[j]));
+  rt_scene *s = nullptr;
+  if (int rc = new_scene(&s)) return rc;
+  s->kind = RT_SCENE_INSTANCED;
+  s->maxd = maxd;  // the LDS stack of the deepest bottom-level tree
+  s->ninst = ninst;
+  s->blas.assign(blas, blas + nblas);
+  for (int32_t j = 0; j < nblas; ++j) s->blas_seen.push_back(blas[j]->version);
+  int rc = upload(&s->d_inst, recs.data(), recs.size(), s->dev_bytes);
+  if (!rc) rc = upload(&s->d_blas, tab.data(), tab.size(), s->dev_bytes);
+  if (rc) {
+    rt_scene_destroy(s);
+    return rc;
+  }
+  *out = s;
+  return RT_OK;
+}
+
+int rt_scene_update_instances(rt_scene *s, int32_t first, int32_t count, const rt_instance *inst) {
+  const char *who = "rt_scene_update_instances";
+  if (int rc = instance_range(s, first, count, who)) return rc;
+  if (!inst) return set_err(RT_E_INVALID, std::string(who) + ": instance pointer is NULL");
+  if (count == 0) return RT_OK;
+  std::vector<rti::InstRec> recs((size_t)count);
+  for (int32_t i = 0; i < count; ++i)
+    if (int rc = instance_record(inst[i], (int32_t)s->blas.size(), (int64_t)first + i, who, recs[(size_t)i])) return rc;
+  int prev = 0;
+  HIP_TRY(hipGetDevice(&prev));
+  HIP_TRY(hipSetDevice(s->device));
+  const hipError_t e = rtdma::h2d(s->d_inst + first, recs.data(), recs.size() * sizeof(rti::InstRec), nullptr);
+  HIP_NOTE(hipSetDevice(prev));
+  if (e != hipSuccess) return set_err(RT_E_DEVICE, rterr::hip_fail("rt_scene_update_instances: upload", e));
+  return RT_OK;
+}
+
+int rt_scene_update_instances_device(rt_scene *s, int32_t first, int32_t count, const float *d_xform12,
+                                     void *stream) {
+  const char *who = "rt_scene_update_instances_device";
+  if (int rc = instance_range(s, first, count, who)) return rc;
+  if (!d_xform12) return set_err(RT_E_INVALID, std::string(who) + ": matrix pointer is NULL");
+  if (count == 0) return RT_OK;
+  return rti::pose_launch(s->d_inst, first, count, d_xform12, (hipStream_t)stream);
+}
+
+int rt_scene_get_instances(const rt_scene *s, int32_t first, int32_t count, rt_instance *inst, float *inv12,
+                           uint32_t *skipped) {
+  if (int rc = instance_range(s, first, count, "rt_scene_get_instances")) return rc;
+  if (count == 0) return RT_OK;
+  std::vector<rti::InstRec> recs((size_t)count);
+  int prev = 0;
+  HIP_TRY(hipGetDevice(&prev));
+  HIP_TRY(hipSetDevice(s->device));
+  hipError_t e = hipDeviceSynchronize();  // pose updates queued on any stream
+  if (e == hipSuccess) e = rtdma::d2h(recs.data(), s->d_inst + first, recs.size() * sizeof(rti::InstRec), nullptr);
+  HIP_NOTE(hipSetDevice(prev));
+  if (e != hipSuccess) return set_err(RT_E_DEVICE, rterr::hip_fail("rt_scene_get_instances", e));
+  for (int32_t i = 0; i < count; ++i) {
+    const rti::InstRec &r = recs[(size_t)i];
+    if (inst) {
+      inst[i].blas = r.blas;
+      inst[i].flags = r.flags;
+      for (float &x : inst[i].xform) x = 0.0f;
+      if (!r.skipped) (void)rti::affine_inverse(r.m, inst[i].xform);
+    }
+    if (inv12) std::memcpy(inv12 + 12 * (size_t)i, r.m, sizeof r.m);
+    if (skipped) skipped[i] = r.skipped;
+  }
   return RT_OK;
 }
 
@@ -2891,7 +3037,7 @@ int rt_scene_destroy(rt_scene *s) {
     if (x) HIP_NOTE(hipStreamSynchronize(x));
   if (s->sched_os) HIP_NOTE(hipStreamSynchronize(s->sched_os));
   void *ptrs[] = {s->d_nodes, s->d_tris, s->d_vals, s->d_child, s->d_ovals, s->d_color, s->d_t,
-                  s->d_cost[0], s->d_order[0], s->d_cost[1], s->d_order[1], s->d_idx, s->d_vstage, s->d_edge};
+                  s->d_cost[0], s->d_order[0], s->d_cost[1], s->d_order[1], s->d_idx, s->d_vstage, s->d_edge, s->d_inst, s->d_blas};
   for (void *p : ptrs)
     if (p) HIP_NOTE(hipFree(p));
   if (s->h_refit) HIP_NOTE(hipHostFree(s->h_refit));
@@ -2924,8 +3070,9 @@ int rt_scene_destroy(rt_scene *s) {
 int rt_render_device(rt_scene *s, const rt_render_params *p, uint32_t *d_color, float *d_t, int32_t W,
                      int32_t H, uint32_t flags, const rt_tile *tile, void *stream) {
   if (!s) return set_err(RT_E_INVALID, "scene is NULL");
-  int rc = check_params(p, W, H);
+  int rc = no_instanced(s, "rt_render_device");
   if (rc) return rc;
+  if ((rc = check_params(p, W, H))) return rc;
   if (!d_color || !d_t) return set_err(RT_E_INVALID, "NULL framebuffer");
   FrameArgs fa;
   if ((rc = fill_frame(fa, s, p, d_color, d_t, W, H, flags, tile))) return rc;
@@ -2937,6 +3084,7 @@ int rt_render_device_frames(rt_scene *s, const rt_render_params *params, int32_t
                             uint32_t *const *d_color, float *const *d_t, int32_t W, int32_t H,
                             uint32_t flags, const rt_tile *tile, void *stream) {
   if (!s || !params || !d_color || !d_t || frames < 0) return set_err(RT_E_INVALID, "bad arguments");
+  if (int rc = no_instanced(s, "rt_render_device_frames")) return rc;
   if (frames == 1) return rt_render_device(s, params, d_color[0], d_t[0], W, H, flags, tile, stream);
   FrameBatch fb;
   for (int32_t f0 = 0; f0 < frames; f0 += kMaxBatch) {
@@ -3151,8 +3299,9 @@ int render_cleared_zero_copy(rt_scene *s, FrameArgs fa, uint32_t *color, float *
 int rt_render(rt_scene *s, const rt_render_params *p, uint32_t *color, float *t, int32_t W, int32_t H,
               uint32_t flags, float *ms) {
   if (!s) return set_err(RT_E_INVALID, "scene is NULL");
-  int rc = check_params(p, W, H);
+  int rc = no_instanced(s, "rt_render");
   if (rc) return rc;
+  if ((rc = check_params(p, W, H))) return rc;
   if (!color || !t) return set_err(RT_E_INVALID, "NULL framebuffer");
   if (flags & RT_FLAG_TILE_NATURAL) return set_err(RT_E_INVALID, "rt_render renders whole frames (no tile)");
   // every argument is checked before the first copy is queued
@@ -3310,6 +3459,16 @@ int rt_intersect_rays(rt_scene *s, const float *o, const float *d, int64_t n, fl
           break;
         default: launch_rays_t<GridS<kGridBuf>, 1>({gd}, s->plane, dO, dD, n, tnear, tfar, dH, dT, dN, dP); break;
       }
+    } else if (s->kind == RT_SCENE_INSTANCED) {
+      // the device entry's kernel on the staged buffers (the same values)
+      const rt_ray_batch b{n, dO, dD, nullptr, nullptr, tnear, tfar, dH, dT, dN, dP};
+      if (const int rc = launch_trace(s, b, kRaysNormal, nullptr)) {
+        cleanup();
+        return rc;
+      }
+    } else if (s->kind != RT_SCENE_OCTREE) {
+      cleanup();
+      return set_err(RT_E_STATE, "rt_intersect_rays: scene has no geometry");
     } else {
       const OctDev od{s->d_child, s->d_ovals};
       switch (s->maxd) {
@@ -3349,8 +3508,9 @@ int rt_trace_rays_device(rt_scene *s, const rt_ray_batch *b, uint32_t flags, voi
 int rt_count_work(rt_scene *s, const rt_render_params *params, int32_t frames, int32_t W, int32_t H,
                   uint32_t flags, const rt_tile *tile, int64_t counters[9]) {
   if (!s || !params || frames <= 0 || !counters) return set_err(RT_E_INVALID, "bad arguments");
-  int rc = check_params(params, W, H);
+  int rc = no_instanced(s, "rt_count_work");
   if (rc) return rc;
+  if ((rc = check_params(params, W, H))) return rc;
   const size_t px = (size_t)W * H;
   if ((rc = ensure_fb(s, px))) return rc;
   unsigned long long *d = nullptr;
@@ -3510,8 +3670,9 @@ int rtx_set_schedule(rt_scene *s, int on) {
 int rt_bench_frames(rt_scene *s, const rt_render_params *params, int32_t frames, int32_t W, int32_t H,
                     uint32_t flags, float *mean_ms, float *total_ms) {
   if (!s || !params || frames <= 0) return set_err(RT_E_INVALID, "bad arguments");
-  int rc = check_params(params, W, H);
+  int rc = no_instanced(s, "rt_bench_frames");
   if (rc) return rc;
+  if ((rc = check_params(params, W, H))) return rc;
   const size_t px = (size_t)W * H;
   if ((rc = ensure_fb(s, px)) || (rc = ensure_events(s))) return rc;
   HIP_TRY(hipMemset(s->d_t, 0x7f, px * 4));

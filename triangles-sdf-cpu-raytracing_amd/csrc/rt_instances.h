@@ -1,0 +1,75 @@
+// rt_instances.h -- instanced scenes (RT_SCENE_INSTANCED, include/rtamd.h):
+// the device records, the one function that defines an instance's
+// world-to-object matrix, and the launches of rt_instances.hip as rt_device.hip
+// queues them.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/rtamd.h"
+#include "rt_scenes.h"
+
+namespace rti {
+
+// One instance on the device: 64 bytes, read by the trace kernel through a
+// wave-uniform address. m is the world-to-object map M (row-major 3x4, the
+// inverse of rt_instance::xform); skipped is set by the device pose update for
+// a matrix affine_inverse refuses and cleared by every accepted update.
+struct InstRec {
+  float m[12];
+  int32_t blas;
+  uint32_t flags;
+  uint32_t skipped;
+  uint32_t pad;
+};
+static_assert(sizeof(InstRec) == 64, "instance record: 64 bytes");
+
+// inv = the inverse of the affine map x (row-major 3x4), by cofactors: nine
+// 2x2 minors, the determinant along the first row, nine divisions, then
+// -(inv3 * translation) summed left to right. Plain float operations in this
+// order on both sides (-ffp-contract=off, correctly rounded division), so the
+// host entry rt_affine_inverse and the device pose kernel give the same bits.
+// Exact for the identity, translations, power-of-two scales and signed axis
+// permutations (every product and quotient is then exact). False, with inv
+// untouched, when an entry is not finite or the determinant is zero or not
+// finite.
+__host__ __device__ inline bool affine_inverse(const float x[12], float inv[12]) {
+  for (int k = 0; k < 12; ++k)
+    if (!__builtin_isfinite(x[k])) return false;
+  const float a = x[0], b = x[1], c = x[2], d = x[4], e = x[5], f = x[6], g = x[8], h = x[9], i = x[10];
+  const float c00 = e * i - f * h, c01 = f * g - d * i, c02 = d * h - e * g;
+  const float det = (a * c00 + b * c01) + c * c02;
+  if (det == 0.0f || !__builtin_isfinite(det)) return false;
+  const float r[9] = {c00 / det, (c * h - b * i) / det, (b * f - c * e) / det,
+                      c01 / det, (a * i - c * g) / det, (c * d - a * f) / det,
+                      c02 / det, (b * g - a * h) / det, (a * e - b * d) / det};
+  for (int k = 0; k < 3; ++k) {
+    inv[4 * k] = r[3 * k];
+    inv[4 * k + 1] = r[3 * k + 1];
+    inv[4 * k + 2] = r[3 * k + 2];
+    inv[4 * k + 3] = -((r[3 * k] * x[3] + r[3 * k + 1] * x[7]) + r[3 * k + 2] * x[11]);
+  }
+  return true;
+}
+
+// What one trace of an instanced scene needs: the instance records, the table
+// of its bottom-level scenes (one MeshDev each, in device memory) and the LDS
+// stack slots of the deepest of them (4, 7, 15 or 31).
+struct InstArgs {
+  const InstRec *inst;
+  const rtd::MeshDev *blas;
+  int32_t ninst;
+  int32_t maxd;
+};
+// mode: 0 any hit, 1 closest hit without the normal, 2 with it (rt_device.hip's
+// kRaysAny / kRaysClosest / kRaysNormal). Only launches.
+int trace_instances_launch(const InstArgs &a, const rtd::PlaneDev &pl, const rt_ray_batch &b, int mode,
+                           hipStream_t st);
+// Writes one table entry in stream order (the entry travels as a kernel
+// argument: no host mirror that a later update could overwrite under a copy).
+int blas_entry_launch(rtd::MeshDev *entry, const rtd::MeshDev &md, hipStream_t st);
+// inst[first + j].m = affine_inverse(d_xform12 + 12 j) for j < count, one
+// matrix per lane; blas and flags stay. Only launches.
+int pose_launch(InstRec *inst, int32_t first, int32_t count, const float *d_xform12, hipStream_t st);
+
+}  // namespace rti

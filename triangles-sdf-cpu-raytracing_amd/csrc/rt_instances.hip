@@ -1,0 +1,235 @@
+// rt_instances.hip -- instanced scenes on the device (gfx950): the trace kernel
+// that walks a flat list of placements of mesh scenes, the pose update that
+// inverts object-to-world matrices, and the one-entry write of the table of
+// bottom-level scenes. Semantics: include/rtamd.h and DESIGN.md section 4a.
+//
+// A translation unit of its own: the kernels of rt_device.hip compile exactly
+// as before whatever is instantiated here.
+//
+// The instance loop is wave-uniform. An instance record (64 bytes) and the
+// MeshDev of its bottom-level scene are read through addresses every lane
+// shares, from memory no kernel of a trace writes (__restrict__ const), so they
+// arrive by scalar loads and the MeshDev handed to the traversal stays in
+// SGPRs, as the by-value kernel argument of trace_rays_kernel does. Per lane
+// the loop keeps the world ray, tNear / tFar, the best t and the winner
+// (instance, triangle slot). All stores are plain vector stores; there is no
+// inline assembly and no device-scope waiting.
+#include <hip/hip_runtime.h>
+
+#include "rt_error.h"
+#include "rt_instances.h"
+#include "rt_layout.h"
+#include "rt_math.h"
+#include "rt_scenes.h"
+
+using namespace rtd;
+
+namespace {
+
+constexpr int kIBlock = 64;  // one wave, as trace_rays_kernel (rt_device.hip)
+enum { kAny = 0, kClosest = 1, kNormal = 2 };
+constexpr int kF = 3;  // LDS words per stack slot of the mesh traversal (MeshS::kFields)
+
+// world -> object, with the operation order of include/rtamd.h (no fusing)
+__device__ __forceinline__ f3 xf_point(const float *m, f3 p) {
+  return f3{((m[0] * p.x + m[1] * p.y) + m[2] * p.z) + m[3], ((m[4] * p.x + m[5] * p.y) + m[6] * p.z) + m[7],
+            ((m[8] * p.x + m[9] * p.y) + m[10] * p.z) + m[11]};
+}
+__device__ __forceinline__ f3 xf_dir(const float *m, f3 d) {
+  return f3{(m[0] * d.x + m[1] * d.y) + m[2] * d.z, (m[4] * d.x + m[5] * d.y) + m[6] * d.z,
+            (m[8] * d.x + m[9] * d.y) + m[10] * d.z};
+}
+
+// The traversal's own root test on the transformed ray, ahead of the traversal:
+// mesh_root evaluates root_box_miss on exactly these operands first, so a lane
+// it rejects here would return "no hit" there. A leaf root has no such test
+// and is never pre-culled. (root_box_miss itself passes every ray whose 1/d
+// has a non-finite component.)
+__device__ __forceinline__ bool root_passes(const MeshDev &md, f3 o, f3 d, float tn, float tf) {
+  if (md.root & rtl::kLeafBit) return true;
+  const f3 inv{1.0f / d.x, 1.0f / d.y, 1.0f / d.z};
+  return !root_box_miss(md.rbox, o, inv, tn, tf);
+}
+
+template <int SLOTS, int MODE>
+__global__ __launch_bounds__(kIBlock) void trace_instances_kernel(const rti::InstRec *__restrict__ inst,
+                                                                  const MeshDev *__restrict__ tab, int32_t ninst,
+                                                                  PlaneDev pl, rt_ray_batch b) {
+  __shared__ uint32_t stk[SLOTS * kF * kIBlock];
+  const int64_t i = (int64_t)blockIdx.x * kIBlock + threadIdx.x;
+  // a partial last wave keeps its lanes without a ray (mesh_primary_wave needs
+  // the whole wave): they carry active = false and touch no memory
+  const bool active = i < b.n;
+  LdsStack<kIBlock, kF> st{stk + threadIdx.x};
+  f3 o{0.0f, 0.0f, 0.0f}, d{0.0f, 0.0f, 1.0f};
+  float tn = b.tnear, tf = b.tfar;
+  if (active) {
+    o = f3{b.d_origin[3 * i], b.d_origin[3 * i + 1], b.d_origin[3 * i + 2]};
+    d = f3{b.d_dir[3 * i], b.d_dir[3 * i + 1], b.d_dir[3 * i + 2]};
+    if (b.d_tnear) tn = b.d_tnear[i];
+    if (b.d_tfar) tf = b.d_tfar[i];
+  }
+  NoCnt cnt;
+  if constexpr (MODE == kAny) {
+    // OR over the instances of the bottom-level any hit under the full tFar;
+    // a lane that has its hit goes inactive, the wave stops when none is left
+    bool live = active, occ = false;
+    for (int32_t k = 0; k < ninst; ++k) {
+      if (__ballot(live) == 0) break;
+      const rti::InstRec r = inst[k];
+      if ((r.flags & RT_INSTANCE_DISABLED) || r.skipped) continue;
+      const MeshDev md = tab[r.blas];
+      if (md.root == rtl::kInvalidChild) continue;
+      if (live) {
+        const f3 oo = xf_point(r.m, o), dd = xf_dir(r.m, d);
+        if (root_passes(md, oo, dd, tn, tf) && mesh_occluded<kIBlock>(md, oo, dd, tn, tf, st, cnt)) {
+          occ = true;
+          live = false;
+        }
+      }
+    }
+    if (!active) return;
+    if (!occ && pl.on) {  // HitInfo::hitten of the union: the OR of both
+      float tp, ap;
+      occ = plane_hit(pl, o, d, tn, tf, tp, ap);
+    }
+    b.d_hit[i] = occ ? 1 : 0;
+  } else {
+    float best = kInf;
+    int32_t wi = -1;      // winning instance
+    uint32_t wk = 0;      // its triangle slot
+    for (int32_t k = 0; k < ninst; ++k) {
+      const rti::InstRec r = inst[k];
+      if ((r.flags & RT_INSTANCE_DISABLED) || r.skipped) continue;
+      const MeshDev md = tab[r.blas];
+      if (md.root == rtl::kInvalidChild) continue;
+      const f3 oo = xf_point(r.m, o), dd = xf_dir(r.m, d);
+      const float tfi = best < tf ? best : tf;
+      const bool go = active && root_passes(md, oo, dd, tn, tfi);
+      if (__ballot(go) == 0) continue;  // the whole wave misses this instance's root box
+      float t = kInf;
+      uint32_t tri = 0;
+      bool h;
+      // mesh_primary_wave takes one tNear for the wave (tFar is per ray):
+      // batches with a d_tnear array take the per-lane traversal
+      if (!b.d_tnear)
+        h = mesh_primary_wave<kIBlock, kF>(md, oo, dd, tn, tfi, go, stk, t, tri) && go;
+      else
+        h = go && mesh_trace<kIBlock, false>(md, oo, dd, tn, tfi, st, t, tri, cnt);
+      if (h && t < best) {  // ties keep the lower index
+        best = t;
+        wi = k;
+        wk = tri;
+      }
+    }
+    if (!active) return;
+    Hit h = miss_hit();
+    if (wi >= 0) {
+      // the winner's record and triangle, per lane (lanes differ in wi)
+      const float *m = inst[wi].m;
+      const rtl::GTri *tris = tab[inst[wi].blas].tris;
+      h.hit = true;
+      h.t = best;
+      if constexpr (MODE == kNormal) {
+        const f3 n = tri_normal(tris, wk);  // object space
+        // the inverse transpose of the object-to-world map: M^T n
+        h.n = normalize(f3{(m[0] * n.x + m[4] * n.y) + m[8] * n.z, (m[1] * n.x + m[5] * n.y) + m[9] * n.z,
+                           (m[2] * n.x + m[6] * n.y) + m[10] * n.z});
+      }
+      if (b.d_prim) h.prim = (int64_t)(((uint64_t)(uint32_t)wi << 32) | (uint64_t)tris[wk].orig_id);
+    }
+    if (pl.on) {  // SceneUnion::intersect, as trace_rays_kernel
+      float tp = kInf, ap = 1.0f;
+      const bool ph = plane_hit(pl, o, d, tn, tf, tp, ap);
+      if (!(h.t < (ph ? tp : kInf))) h = ph ? Hit{true, tp, pl.n, -2} : miss_hit();
+    }
+    if (b.d_hit) b.d_hit[i] = h.hit ? 1 : 0;
+    if (b.d_t) b.d_t[i] = h.t;
+    if constexpr (MODE == kNormal) {
+      b.d_normal[3 * i] = h.n.x;
+      b.d_normal[3 * i + 1] = h.n.y;
+      b.d_normal[3 * i + 2] = h.n.z;
+    }
+    if (b.d_prim) b.d_prim[i] = h.hit ? h.prim : -1;
+  }
+}
+
+// One table entry, taken by value and written word by word by one lane.
+__global__ void blas_entry_kernel(MeshDev *entry, MeshDev md) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  entry->nodes = md.nodes;
+  entry->tris = md.tris;
+  entry->root = md.root;
+  for (int k = 0; k < 6; ++k) entry->rbox[k] = md.rbox[k];
+  entry->coop = md.coop;
+  entry->n_inner = md.n_inner;
+  entry->dmax2 = md.dmax2;
+}
+
+// One matrix per lane: twelve loads, rti::affine_inverse, three 16-byte stores
+// of M and the skipped word. blas and flags are not touched.
+__global__ __launch_bounds__(64) void pose_kernel(rti::InstRec *inst, int32_t first, int32_t count,
+                                                  const float *__restrict__ xf) {
+  const int32_t j = (int32_t)(blockIdx.x * 64u + threadIdx.x);
+  if (j >= count) return;
+  float x[12], m[12] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+  for (int k = 0; k < 12; ++k) x[k] = xf[12 * (int64_t)j + k];
+  const bool ok = rti::affine_inverse(x, m);
+  rti::InstRec *r = inst + (int64_t)first + j;
+  float4 *q = reinterpret_cast<float4 *>(r->m);
+  q[0] = make_float4(m[0], m[1], m[2], m[3]);
+  q[1] = make_float4(m[4], m[5], m[6], m[7]);
+  q[2] = make_float4(m[8], m[9], m[10], m[11]);
+  r->skipped = ok ? 0u : 1u;
+}
+
+template <int SLOTS>
+void launch_t(const rti::InstArgs &a, const PlaneDev &pl, const rt_ray_batch &b, int mode, hipStream_t st) {
+  const unsigned blocks = (unsigned)((b.n + kIBlock - 1) / kIBlock);
+  switch (mode) {
+    case kAny: trace_instances_kernel<SLOTS, kAny><<<blocks, kIBlock, 0, st>>>(a.inst, a.blas, a.ninst, pl, b); break;
+    case kClosest:
+      trace_instances_kernel<SLOTS, kClosest><<<blocks, kIBlock, 0, st>>>(a.inst, a.blas, a.ninst, pl, b);
+      break;
+    default: trace_instances_kernel<SLOTS, kNormal><<<blocks, kIBlock, 0, st>>>(a.inst, a.blas, a.ninst, pl, b); break;
+  }
+}
+
+}  // namespace
+
+namespace rti {
+
+int trace_instances_launch(const InstArgs &a, const PlaneDev &pl, const rt_ray_batch &b, int mode, hipStream_t st) {
+  switch (a.maxd) {
+    case 4: launch_t<4>(a, pl, b, mode, st); break;
+    case 7: launch_t<7>(a, pl, b, mode, st); break;
+    case 15: launch_t<15>(a, pl, b, mode, st); break;
+    default: launch_t<31>(a, pl, b, mode, st); break;
+  }
+  HIP_TRY(hipGetLastError());
+  return RT_OK;
+}
+
+int blas_entry_launch(MeshDev *entry, const MeshDev &md, hipStream_t st) {
+  blas_entry_kernel<<<1, 64, 0, st>>>(entry, md);
+  HIP_TRY(hipGetLastError());
+  return RT_OK;
+}
+
+int pose_launch(InstRec *inst, int32_t first, int32_t count, const float *d_xform12, hipStream_t st) {
+  pose_kernel<<<(unsigned)((count + 63) / 64), 64, 0, st>>>(inst, first, count, d_xform12);
+  HIP_TRY(hipGetLastError());
+  return RT_OK;
+}
+
+}  // namespace rti
+
+extern "C" int rt_affine_inverse(const float xform[12], float inv[12]) {
+  if (!xform || !inv) return set_err(RT_E_INVALID, "rt_affine_inverse: NULL argument");
+  float m[12];
+  if (!rti::affine_inverse(xform, m))
+    return set_err(RT_E_INVALID, "rt_affine_inverse: the matrix is singular or has a non-finite entry");
+  for (int k = 0; k < 12; ++k) inv[k] = m[k];
+  return RT_OK;
+}

@@ -315,6 +315,8 @@ extern "C" {
 
 int rt_multi_create(rt_scene *scene, const int32_t *devices, int32_t n, int32_t band_rows, rt_multi **out) {
   if (!scene || !devices || n < 1 || !out) return rterr::set(RT_E_INVALID, "rt_multi_create: bad arguments");
+  if (rt_scene_kind(scene) == RT_SCENE_INSTANCED)
+    return rterr::set(RT_E_STATE, "rt_multi_create: not available for an instanced scene");
   *out = nullptr;
   if (n > 64) return rterr::set(RT_E_INVALID, "rt_multi_create: at most 64 slots");
   int ndev = 0;

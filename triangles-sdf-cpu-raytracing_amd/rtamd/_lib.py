@@ -20,7 +20,8 @@ RT_FLAG_HITS_ONLY = 4
 RT_RAYS_ANY_HIT = 1
 RT_MESH_DYNAMIC = 1
 RT_IPC_HANDLE_BYTES = 64
-RT_SCENE_MESH, RT_SCENE_GRID, RT_SCENE_OCTREE = 1, 2, 3
+RT_SCENE_MESH, RT_SCENE_GRID, RT_SCENE_OCTREE, RT_SCENE_INSTANCED = 1, 2, 3, 4
+RT_INSTANCE_DISABLED = 1
 
 _lib = None
 
@@ -62,6 +63,11 @@ class RayBatch(C.Structure):
                 ("d_t", C.c_void_p), ("d_normal", C.c_void_p), ("d_prim", C.c_void_p)]
 
 
+class Instance(C.Structure):
+    """rt_instance (include/rtamd.h): xform is object to world, row-major 3x4."""
+    _fields_ = [("blas", C.c_int32), ("flags", C.c_uint32), ("xform", C.c_float * 12)]
+
+
 # name -> (restype, argtypes)
 _SIGS = {
     "rt_last_error": (C.c_char_p, []),
@@ -84,6 +90,13 @@ _SIGS = {
                                           C.POINTER(C.c_void_p)]),
     "rt_scene_update_vertices": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
     "rt_scene_update_vertices_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "rt_affine_inverse": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "rt_scene_create_instanced": (C.c_int, [C.POINTER(C.c_void_p), C.c_int32, C.POINTER(Instance), C.c_int32,
+                                            C.POINTER(C.c_void_p)]),
+    "rt_scene_update_instances": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(Instance)]),
+    "rt_scene_update_instances_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "rt_scene_get_instances": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(Instance), C.c_void_p,
+                                         C.c_void_p]),
     "rt_scene_create_grid": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
     "rt_scene_create_octree": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(C.c_void_p)]),
     "rt_scene_set_plane": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_float]),

@@ -23,12 +23,12 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from ._lib import (RT_FLAG_CLEAR, RT_FLAG_HITS_ONLY, RT_MESH_DYNAMIC, RT_RAYS_ANY_HIT, CameraState, RayBatch,
-                   RenderParams, RtError, Tile, check, lib)
+from ._lib import (RT_FLAG_CLEAR, RT_FLAG_HITS_ONLY, RT_INSTANCE_DISABLED, RT_MESH_DYNAMIC, RT_RAYS_ANY_HIT,
+                   CameraState, Instance, RayBatch, RenderParams, RtError, Tile, check, lib)
 
 __all__ = [
     "ShadingMode", "SimpleMesh", "FrameBuffer", "Camera", "Renderer", "HitInfo", "IScene",
-    "BVHBuilder", "SDFGrid", "SDFOctree", "Plane", "SceneUnion", "load_mesh_from_obj",
+    "BVHBuilder", "SDFGrid", "SDFOctree", "InstancedScene", "InstanceTable", "affine_inverse", "Plane", "SceneUnion", "load_mesh_from_obj",
     "load_sdf_grid", "load_sdf_octree", "camera_matrices", "render_params", "RtError",
     "RT_FLAG_CLEAR", "Tile", "device_count", "SDFMesh", "subdivide_mesh", "save_mesh_to_obj",
     "MultiRenderer",
@@ -425,6 +425,97 @@ class SDFOctree(IScene):
         h = C.c_void_p()
         check(lib().rt_scene_create_octree(_p(nodes36), nodes36.nbytes // 36, C.byref(h)))
         self._h = h
+
+
+def affine_inverse(xform) -> np.ndarray:
+    """rt_affine_inverse: the world-to-object matrix M the library stores for an
+    object-to-world map (12 floats, row-major 3x4), as float32 [3, 4]. Raises
+    RtError for a singular or non-finite matrix."""
+    x = np.ascontiguousarray(xform, np.float32).reshape(12)
+    inv = np.zeros(12, np.float32)
+    check(lib().rt_affine_inverse(_p(x), _p(inv)))
+    return inv.reshape(3, 4)
+
+
+@dataclass
+class InstanceTable:
+    """What the device holds of an InstancedScene (rt_scene_get_instances)."""
+    blas: np.ndarray     # int32 [K]
+    flags: np.ndarray    # uint32 [K]
+    xform: np.ndarray    # float32 [K, 3, 4]: the inverse of inv (zeros for a skipped instance)
+    inv: np.ndarray      # float32 [K, 3, 4]: M, world to object
+    skipped: np.ndarray  # uint32 [K]: 1 = refused by the device pose update
+
+
+def _instance_array(blas, xforms, flags):
+    x = np.ascontiguousarray(xforms, np.float32)
+    if x.ndim < 2 or x.size != x.shape[0] * 12:
+        raise RtError(f"instance matrices: shape {x.shape}, expected [K, 3, 4] or [K, 12]")
+    x = x.reshape(-1, 12)
+    arr = (Instance * len(x))()
+    for k in range(len(x)):
+        arr[k].blas = int(blas[k])
+        arr[k].flags = int(flags[k])
+        arr[k].xform[:] = x[k].tolist()
+    return arr
+
+
+class InstancedScene(IScene):
+    """Rigid (affine) copies of mesh scenes under one ray query
+    (rt_scene_create_instanced). blas_list: BVHBuilder scenes on the current
+    device; instances: (blas index, xform) or (blas index, xform, flags)
+    tuples, xform the object-to-world map as 12 floats (row-major 3x4). Ray
+    queries only (intersect, trace_device, torch_rays.trace): prim is
+    (instance << 32) | triangle id. Keeps its BLAS objects alive."""
+
+    DISABLED = RT_INSTANCE_DISABLED
+
+    def __init__(self, blas_list, instances):
+        self._blas_objs = list(blas_list)
+        inst = [tuple(t) for t in instances]
+        self._blas_idx = np.asarray([t[0] for t in inst], np.int32)
+        self._flags = np.asarray([t[2] if len(t) > 2 else 0 for t in inst], np.uint32)
+        handles = (C.c_void_p * len(self._blas_objs))(*[b._handle() for b in self._blas_objs])
+        xforms = np.asarray([np.asarray(t[1], np.float32).reshape(12) for t in inst], np.float32).reshape(-1, 12)
+        arr = _instance_array(self._blas_idx, xforms, self._flags)
+        h = C.c_void_p()
+        check(lib().rt_scene_create_instanced(handles, len(self._blas_objs), arr, len(inst), C.byref(h)))
+        self._h = h
+
+    def __len__(self):
+        return len(self._blas_idx)
+
+    def update_instances(self, xforms, first: int = 0, flags=None):
+        """New poses (and, with flags, new flags) for instances first ..
+        first + K - 1 from host matrices [K, 3, 4] or [K, 12]; the blas indices
+        stay (rt_scene_update_instances). A refused call changes nothing."""
+        x = np.ascontiguousarray(xforms, np.float32)
+        k = x.shape[0] if x.ndim >= 2 else 0
+        if first < 0 or first + k > len(self):
+            raise RtError(f"update_instances: [{first}, {first + k}) outside the scene's {len(self)} instances")
+        fl = self._flags[first:first + k] if flags is None else np.broadcast_to(np.asarray(flags, np.uint32), (k,))
+        arr = _instance_array(self._blas_idx[first:first + k], x, fl)
+        check(lib().rt_scene_update_instances(self._handle(), int(first), k, arr))
+        self._flags[first:first + k] = fl
+
+    def update_instances_device(self, ptr: int, count: int, first: int = 0, stream: int | None = None):
+        """The same from device memory: `count` matrices (float32[12 * count] at
+        ptr) inverted by a kernel queued on `stream`; only launches
+        (rt_scene_update_instances_device). A matrix the inverse refuses makes
+        its instance skipped until its next update."""
+        check(lib().rt_scene_update_instances_device(self._handle(), int(first), int(count),
+                                                     C.c_void_p(ptr) if ptr else None,
+                                                     C.c_void_p(stream) if stream else None))
+
+    def instances(self) -> InstanceTable:
+        """Read the instance table back from the device (one synchronisation)."""
+        k = len(self)
+        arr = (Instance * k)()
+        inv = np.zeros((k, 3, 4), np.float32)
+        skipped = np.zeros(k, np.uint32)
+        check(lib().rt_scene_get_instances(self._handle(), 0, k, arr, _p(inv), _p(skipped)))
+        return InstanceTable(np.asarray([a.blas for a in arr], np.int32), np.asarray([a.flags for a in arr], np.uint32),
+                             np.asarray([list(a.xform) for a in arr], np.float32).reshape(k, 3, 4), inv, skipped)
 
 
 @dataclass

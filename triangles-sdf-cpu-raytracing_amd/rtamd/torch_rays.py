@@ -13,6 +13,13 @@ imported when trace() is called, so ``import rtamd`` stays torch-free.
 moves the vertices of a dynamic mesh scene (BVHBuilder(mesh, dynamic=True))
 to a tensor's positions: the BVH8 refit of rt_scene_update_vertices_device, on
 the same stream.
+
+    torch_rays.update_instances(scene, xforms, first=0)
+
+gives an rtamd.InstancedScene new poses from a tensor of object-to-world
+matrices (rt_scene_update_instances_device: one small kernel on the same
+stream, nothing else), and split_prim() takes such a scene's primitive ids
+apart into (instance, triangle).
 """
 from __future__ import annotations
 
@@ -87,6 +94,49 @@ def update_vertices(scene, verts) -> None:
             verts = torch.cat([verts, verts.new_ones((verts.shape[0], 1))], dim=1)
         scene.update_vertices_device(verts.data_ptr(), verts.shape[0],
                                      stream=torch.cuda.current_stream(device).cuda_stream)
+
+
+def update_instances(scene, xforms, first: int = 0) -> None:
+    """New poses for instances first .. first + K - 1 of an
+    rtamd.InstancedScene from `xforms`, a contiguous float32 [K, 3, 4] or
+    [K, 12] tensor of object-to-world matrices (row-major 3x4) on the scene's
+    device. The inversion kernel is queued on torch.cuda.current_stream(),
+    after the torch kernels that produced `xforms` there; the call only
+    launches. A singular or non-finite matrix cannot be refused (the data is
+    on the device): its instance is skipped by every query until its next
+    update. Raises ValueError on a bad tensor or range before anything is
+    launched."""
+    import torch
+
+    device = int(lib().rt_scene_device(scene._handle()))
+    if not isinstance(xforms, torch.Tensor):
+        raise ValueError(f"xforms: expected a torch tensor, got {type(xforms).__name__}")
+    if xforms.dtype != torch.float32:
+        raise ValueError(f"xforms: dtype {xforms.dtype}, expected torch.float32")
+    if not ((xforms.dim() == 3 and tuple(xforms.shape[1:]) == (3, 4)) or (xforms.dim() == 2 and xforms.shape[1] == 12)):
+        raise ValueError(f"xforms: shape {tuple(xforms.shape)}, expected [K, 3, 4] or [K, 12]")
+    if xforms.device.type != "cuda" or xforms.device.index != device:
+        raise ValueError(f"xforms: on {xforms.device}, the scene is on HIP device {device}")
+    if not xforms.is_contiguous():
+        raise ValueError("xforms: not contiguous")
+    k = int(xforms.shape[0])
+    if first < 0 or first + k > len(scene):
+        raise ValueError(f"instances [{first}, {first + k}) outside the scene's {len(scene)}")
+    if k == 0:
+        return
+    with torch.cuda.device(device):
+        scene.update_instances_device(xforms.data_ptr(), k, first=int(first),
+                                      stream=torch.cuda.current_stream(device).cuda_stream)
+
+
+def split_prim(prim):
+    """(instance, triangle) of an InstancedScene's primitive ids (an int64
+    tensor or numpy array): prim = (instance << 32) | triangle on a hit.
+    Misses (-1) and the plane (-2) give instance -1 and triangle -1 / -2."""
+    neg = prim < 0
+    inst = prim >> 32  # arithmetic shift: -1 for the negative ids
+    tri = prim & 0xFFFFFFFF
+    return inst, tri * (~neg) + prim * neg
 
 
 def trace(scene, origins, dirs, tnear=0.01, tfar=100.0, any_hit=False, outputs=OUTPUTS) -> RayHits:
