@@ -150,6 +150,27 @@ def test_parity_with_oracle(gpu, name, plane, tn, tf):
 
 @pytest.mark.parametrize("name", NAMES)
 @pytest.mark.parametrize("plane", [False, True])
+@pytest.mark.parametrize("tn,tf", PAIRS)
+def test_parity_with_oracle_shuffled(gpu, name, plane, tn, tf):
+    """test_parity_with_oracle on a seeded permutation of the same rays
+    (ray_cases.shuffle_perm): _random_rays puts its exact-path rays into the
+    first n / 8, eight whole waves; shuffled, every wave holds rays of both
+    flavours (tests/test_ray_cases_host.py asserts that). The oracle answers
+    ray by ray, so its result is permuted with the rays."""
+    import ray_cases as RC
+    perm = RC.shuffle_perm(N)
+    ref = tuple(a[perm] for a in _oracle(name, plane, tn, tf))
+    _, gs = _set_plane(name, plane)
+    o, d, _, _ = _rays(name)
+    o_t = torch.from_numpy(np.ascontiguousarray(o[perm])).cuda()
+    d_t = torch.from_numpy(np.ascontiguousarray(d[perm])).cuda()
+    _assert_oracle(ref, _trace(gs, o_t, d_t, N, tn=tn, tf=tf), f"{name} shuffled plane={plane} [{tn}, {tf}]")
+    a = _trace(gs, o_t, d_t, N, outputs=("hit",), tn=tn, tf=tf, any_hit=True)
+    assert np.array_equal(ref[0], a["hit"]), "any-hit mask differs"
+
+
+@pytest.mark.parametrize("name", NAMES)
+@pytest.mark.parametrize("plane", [False, True])
 def test_per_ray_intervals(gpu, name, plane):
     """d_tnear / d_tfar: each ray draws one of the three intervals; also one of
     the two pointers NULL (that side's scalar applies)."""

@@ -199,6 +199,35 @@ def test_exact_translation_end_to_end(gpu):
         assert np.array_equal(hs.hitten, ref["hit"].astype(bool))
 
 
+def test_refitted_lattice_against_the_oracle_on_exact_path_rays(gpu):
+    """A dynamic lattice mesh updated by the exact translation, traced with the
+    lattice_axis and one_zero rays of ray_cases.py shifted by the same vector
+    (origins on the moved box bounds, 1/d infinite): closest hit and any hit
+    are the ORACLE's on the translated vertices, bitwise -- not another GPU
+    scene's. test_ray_cases_host.py::test_refit_sets pins at least 100 oracle
+    hits per set and interval."""
+    import ray_cases as RC
+    from test_rays_device import _assert_oracle
+    from test_rays_device import _trace as trace_guarded
+    rt = gpu
+    v, i = RC.scene_input("lattice")[1]
+    w = R.translate(v)
+    rs = cpuref.RefScene.mesh(w, i)
+    with _scene(rt, v, i) as s:
+        s.update_vertices(w)
+        for cls in ("lattice_axis", "one_zero"):
+            o, d = RC.plain_sets("lattice")[cls]
+            o = np.ascontiguousarray(o + R.SHIFT)
+            o_t, d_t = torch.from_numpy(o).cuda(), torch.from_numpy(np.array(d)).cuda()
+            for tn, tf in RC.PAIRS:
+                ref = rs.intersect_rays(o, d, tn, tf)
+                assert int(ref[0].sum()) >= 100
+                what = f"refitted lattice {cls} [{tn}, {tf}]"
+                _assert_oracle(ref, trace_guarded(s, o_t, d_t, len(o), tn=tn, tf=tf), what)
+                a = trace_guarded(s, o_t, d_t, len(o), outputs=("hit",), tn=tn, tf=tf, any_hit=True)
+                assert np.array_equal(ref[0], a["hit"]), f"{what}: any-hit mask differs"
+
+
 # ------------------------------------------- general deformation, bunny --
 @functools.lru_cache(maxsize=None)
 def _bunny_deformed():
