@@ -20,6 +20,11 @@
 // keeping its second child's entry t; see resume_model below
 // (profiles/r07/trav_sim_resume.txt).
 //
+// trav_sim --share [obj[@N] W H [px py pz]]: per wave-level expansion, the lanes
+// that expand and the distinct nodes among them -- what a fetch shared through
+// LDS can take off the vector L1; see share_model below
+// (profiles/r16/trav_sim_share.txt).
+//
 // build: g++ -O2 -std=c++17 -Iinclude tools/trav_sim.cpp
 //          -Ltriangles-sdf-cpu-raytracing_amd/lib -lrtamd -Wl,-rpath,... -o /tmp/trav_sim
 #include <algorithm>
@@ -217,6 +222,7 @@ void replay(const std::vector<std::string> &s, int policy, double cI, double cL,
 struct Iter {
   char top;      // 'I', 'L' (leaf, either batch count), 'P'
   bool second;   // the tail needs a global round trip after the top part's
+  uint32_t node = 0;  // 'I': the node expanded (--share)
 };
 struct RayCounts {
   double inner = 0, leaf = 0, two = 0, pushed = 0, resume_visit = 0, resume_prune = 0, prune_second = 0,
@@ -267,7 +273,7 @@ void run_ray(V3 o, V3 d, V3 inv, float tn, float tf, int variant, std::vector<It
   bool have_t = true;
   int64_t word = -1;
   for (;;) {
-    Iter it{'P', false};
+    Iter it{'P', false, 0};
     if (word >= 0) {
       const Node &nd = nodes[(size_t)word];
       if (nd.leaf) {
@@ -281,6 +287,7 @@ void run_ray(V3 o, V3 d, V3 inv, float tn, float tf, int variant, std::vector<It
         if (lt < st.back().best) st.back().best = lt;
       } else {
         it.top = 'I';
+        it.node = (uint32_t)word;
         rc.inner += 1;
         Frame f = expand((uint32_t)word, o, inv, tn, tf);
         rc.two += f.n >= 2;
@@ -469,22 +476,140 @@ int resume_model(Eye eye, V3 org, int W, int H) {
   return 0;
 }
 
+// ---- --share: how many expansions fetch a node the whole wave shares -------
+// The shipped loop (V0, the minority side of a leaf / inner split waits) in
+// lockstep per 8x8 wave tile; a frame whose size is no multiple of 8 has
+// partial tiles at its right and bottom edges, as the kernels do. For every
+// wave-level expansion (an iteration in which at least one lane expands an
+// inner node): the lanes that expand and the distinct nodes among them. An
+// expansion with one distinct node and at least kShareLanes lanes is what the
+// shared fetch (RT_NODE_SHARE, csrc/rt_scenes.h) takes: one 14-lane load and
+// 14 LDS broadcasts in place of 14 per-lane vector loads. The cooperative tail
+// is not modelled: it starts at 8 rays or fewer, below the threshold.
+constexpr int kShareLanes = 14;
+struct ShareBin {
+  double waves = 0, lanes = 0;
+};
+
+template <class Eye>
+int share_model(Eye eye, V3 org, int W, int H) {
+  // [distinct nodes: 1, 2, 3+][lanes: >= kShareLanes, fewer]
+  ShareBin bin[3][2];
+  double wave_iters = 0, lane_inner = 0, lane_leaf = 0, busy_tiles = 0, mixed_tiles = 0;
+  RayCounts rc;
+  for (int ty = 0; ty < (H + 7) / 8; ++ty)
+    for (int tx = 0; tx < (W + 7) / 8; ++tx) {
+      std::vector<std::vector<Iter>> s(64);
+      bool any = false;
+      for (int l = 0; l < 64; ++l) {
+        const int x = tx * 8 + (l & 7), yo = ty * 8 + (l >> 3), y = H - yo - 1;
+        if (x >= W || yo >= H) continue;
+        const V3 d = eye(x, y);
+        const V3 inv{1.0f / d.x, 1.0f / d.y, 1.0f / d.z};
+        run_ray(org, d, inv, 0.01f, 100.0f, 0, s[l], rc);
+        any |= !s[l].empty();
+      }
+      if (!any) continue;
+      busy_tiles += 1;
+      bool t_shared = false, t_lane = false;
+      std::vector<size_t> pos(64, 0);
+      for (;;) {
+        int nI = 0, nL = 0, live = 0;
+        for (int k = 0; k < 64; ++k) {
+          if (pos[k] >= s[k].size()) continue;
+          ++live;
+          nI += s[k][pos[k]].top == 'I';
+          nL += s[k][pos[k]].top == 'L';
+        }
+        if (!live) break;
+        const bool waitL = nL < nI, waitI = !waitL && nI < nL;
+        std::vector<uint32_t> exp;
+        for (int k = 0; k < 64; ++k) {
+          if (pos[k] >= s[k].size()) continue;
+          const Iter &i = s[k][pos[k]];
+          if ((i.top == 'L' && waitL) || (i.top == 'I' && waitI)) continue;
+          if (i.top == 'I') exp.push_back(i.node);
+          lane_leaf += i.top == 'L';
+          ++pos[k];
+        }
+        wave_iters += 1;
+        if (exp.empty()) continue;
+        const int n = (int)exp.size();
+        std::sort(exp.begin(), exp.end());
+        const int dn = (int)(std::unique(exp.begin(), exp.end()) - exp.begin());
+        ShareBin &b = bin[std::min(dn, 3) - 1][n >= kShareLanes ? 0 : 1];
+        b.waves += 1;
+        b.lanes += n;
+        lane_inner += n;
+        (dn == 1 && n >= kShareLanes ? t_shared : t_lane) = true;
+      }
+      mixed_tiles += t_shared && t_lane;
+    }
+  double waves = 0;
+  for (auto &r : bin)
+    for (auto &b : r) waves += b.waves;
+  std::printf("frame %d x %d, rays %d, wave tiles with a ray past the root %.0f, wave iterations %.0f\n", W, H, W * H,
+              busy_tiles, wave_iters);
+  std::printf("inner visits below the root (lane level) %.0f, leaf visits %.0f\n", lane_inner, lane_leaf);
+  std::printf("wave-level expansions %.0f (14 node-vector loads each: %.0f)\n\n", waves, 14 * waves);
+  std::printf("%-34s%12s%10s%12s%12s\n", "distinct nodes, expanding lanes", "expansions", "share", "lanes", "lanes/exp");
+  const char *dn[3] = {"1 node", "2 nodes", "3+ nodes"};
+  for (int d = 0; d < 3; ++d)
+    for (int h = 0; h < 2; ++h) {
+      const ShareBin &b = bin[d][h];
+      char name[64];
+      std::snprintf(name, sizeof name, "%s, %s %d lanes", dn[d], h == 0 ? ">=" : "< ", kShareLanes);
+      std::printf("%-34s%12.0f%9.1f %%%12.0f%12.1f\n", name, b.waves, waves ? 100.0 * b.waves / waves : 0.0, b.lanes,
+                  b.waves ? b.lanes / b.waves : 0.0);
+    }
+  const double sh = bin[0][0].waves, two = bin[1][0].waves;
+  std::printf("\nshared expansions (1 node, >= %d lanes): %.0f of %.0f = %.1f %% of the expansions and of the\n"
+              "  frame's node-vector loads; per-lane expansions %.0f; tiles that run both forms %.0f\n",
+              kShareLanes, sh, waves, waves ? 100.0 * sh / waves : 0.0, waves - sh, mixed_tiles);
+  std::printf("node-vector loads: %.0f -> %.0f (one 14-lane load per shared expansion), LDS reads + %.0f, LDS stores + %.0f\n",
+              14 * waves, 14 * (waves - sh) + sh, 14 * sh, sh);
+  std::printf("bound for a second round (2 nodes, >= %d lanes): %.0f expansions = %.1f %%\n", kShareLanes, two,
+              waves ? 100.0 * two / waves : 0.0);
+  return 0;
+}
+
 }  // namespace
 
 int main(int argc, char **argv) {
   const bool resume = argc > 1 && std::strcmp(argv[1], "--resume") == 0;
-  if (resume) { --argc; ++argv; }
+  const bool share = argc > 1 && std::strcmp(argv[1], "--share") == 0;
+  if (resume || share) { --argc; ++argv; }
   const char *obj = argc > 1 ? argv[1] : "data/_unpacked/stanford-bunny.obj";
   const int W = argc > 2 ? std::atoi(argv[2]) : 1920, H = argc > 3 ? std::atoi(argv[3]) : 1080;
   const double cI = argc > 4 ? std::atof(argv[4]) : 250, cL = argc > 5 ? std::atof(argv[5]) : 360,
                cC = argc > 6 ? std::atof(argv[6]) : 40;
   g_k = argc > 7 ? std::atof(argv[7]) : 1.0;
   g_split = argc > 8 && std::atoi(argv[8]) != 0;
+  // "file.obj@N": the mesh subdivided N times (rt_mesh_subdivide; @2 of the
+  // bunny is the 1.1 M-triangle stand-in of bench.py's mesh_large)
+  std::string path = obj;
+  int levels = 0;
+  if (const size_t at = path.rfind('@'); at != std::string::npos) {
+    levels = std::atoi(path.c_str() + at + 1);
+    path.resize(at);
+  }
   int64_t nv = 0, ni = 0;
-  if (rt_load_obj(obj, 1, nullptr, &nv, nullptr, &ni)) return std::printf("load: %s\n", rt_last_error()), 1;
+  if (rt_load_obj(path.c_str(), 1, nullptr, &nv, nullptr, &ni)) return std::printf("load: %s\n", rt_last_error()), 1;
   vpos.resize(4 * nv);
   idx.resize(ni);
-  rt_load_obj(obj, 1, vpos.data(), &nv, idx.data(), &ni);
+  rt_load_obj(path.c_str(), 1, vpos.data(), &nv, idx.data(), &ni);
+  if (levels > 0) {
+    int64_t sv = 0, si = 0;
+    if (rt_mesh_subdivide(vpos.data(), nv, idx.data(), ni, levels, nullptr, &sv, nullptr, &si))
+      return std::printf("subdivide: %s\n", rt_last_error()), 1;
+    std::vector<float> v2(4 * sv);
+    std::vector<uint32_t> i2(si);
+    rt_mesh_subdivide(vpos.data(), nv, idx.data(), ni, levels, v2.data(), &sv, i2.data(), &si);
+    vpos.swap(v2);
+    idx.swap(i2);
+    nv = sv;
+    ni = si;
+  }
   rt_set_bvh_builder(RT_BVH_HOST);
   int64_t nn = 0;
   int32_t depth = 0;
@@ -496,8 +621,12 @@ int main(int argc, char **argv) {
   size_t at = 0;
   parse(at);
   std::printf("%zu nodes, depth %d, %lld tris\n", nodes.size(), depth, (long long)ni / 3);
-  // orbit frame 0 of bench.py (pos = (0, 0.5, 2.5)), the kernel's eye rays
-  const float pos[3] = {0.0f, 0.5f, 2.5f}, tgt[3] = {0, 0, 0}, up[3] = {0, 1, 0};
+  // orbit frame 0 of bench.py (pos = (0, 0.5, 2.5)), the kernel's eye rays;
+  // --share takes another camera position as its arguments 4 to 6
+  float pos[3] = {0.0f, 0.5f, 2.5f};
+  const float tgt[3] = {0, 0, 0}, up[3] = {0, 1, 0};
+  if (share && argc > 6)
+    for (int k = 0; k < 3; ++k) pos[k] = (float)std::atof(argv[4 + k]);
   float vi[16], pi[16];
   rt_camera(pos, tgt, up, 45.0f, (float)W / (float)H, 0.01f, 100.0f, vi, pi);
   auto eye = [&](int x, int y) {
@@ -512,6 +641,7 @@ int main(int argc, char **argv) {
               vi[2] * dd.x + vi[6] * dd.y + vi[10] * dd.z};
   };
   if (resume) return resume_model(eye, V3{pos[0], pos[1], pos[2]}, W, H);
+  if (share) return share_model(eye, V3{pos[0], pos[1], pos[2]}, W, H);
   Cost c[3];
   double both = 0, iters0 = 0, steps = 0;
   long tiles = 0, busy_tiles = 0, root_only = 0;

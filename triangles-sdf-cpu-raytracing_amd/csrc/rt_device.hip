@@ -140,6 +140,26 @@ struct MeshS {
     }
     return h;
   }
+  // the counting kernel's primary rays: the same wave path with the work
+  // counters, its cooperative tail off (the 8-lane groups do not count; they
+  // start below the shared fetch's lane threshold, so the wave-level counters
+  // are the timed kernels')
+  template <int B, class CT>
+  __device__ __forceinline__ Hit primary_counted(f3 o, f3 dir, float tn, float tf, bool active, uint32_t *stk,
+                                                 CT &cnt) const {
+    float t;
+    uint32_t k;
+    Hit h = miss_hit();
+    MeshDev dc = d;
+    dc.coop = false;
+    if (mesh_primary_wave<B, kFields>(dc, o, dir, tn, tf, active, stk, t, k, kCoopRays, 0, cnt) && active) {
+      h.hit = true;
+      h.t = t;
+      h.n = tri_normal(d.tris, k);
+      h.prim = (int64_t)d.tris[k].orig_id;
+    }
+    return h;
+  }
   template <int B, class CT>
   __device__ __forceinline__ Hit intersect(f3 o, f3 dir, float tn, float tf,
                                            LdsStack<B, kFields> st, CT &cnt) const {
@@ -380,7 +400,7 @@ struct CntSel<2> { using T = LaneCnt; };
 __device__ __forceinline__ void flush_counts(NoCnt &, unsigned long long *) {}
 __device__ __forceinline__ void flush_counts(LaneCnt &c, unsigned long long *out) {
 #pragma unroll
-  for (int i = 0; i < C_NUM; ++i) {
+  for (int i = 0; i < C_ALL; ++i) {
     unsigned long long v = c.v[i];
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
@@ -432,8 +452,11 @@ __device__ __forceinline__ bool render_pixels(const S &sc, const PlaneDev &pl, c
   const bool active = xo < fa.W && yl < fa.rows_local;
   // wave-cooperative primary path: every lane of the wave takes part
   constexpr bool kWaveCoop = DIAG == 0 && !GENERAL && S::kCoop;
+  // the counting variant of that path: the same waves, so that its wave-level
+  // counters (C_BVH_SHARED) are those of the timed kernels
+  constexpr bool kWaveCount = DIAG == 1 && !GENERAL && S::kCoop;
   if (DIAG == 0 && !kWaveCoop && !active) return false;
-  if (active || kWaveCoop) {  // (the counting variant keeps every lane for its wave reduction)
+  if (active || kWaveCoop || kWaveCount) {  // (the counting variant keeps every lane for its wave reduction)
     StackOf<S, B> st{stk + threadIdx.x};
     if constexpr (kWaveCoop) {
       const int yo = image_row(active ? yl : 0, fa);
@@ -493,10 +516,12 @@ __device__ __forceinline__ bool render_pixels(const S &sc, const PlaneDev &pl, c
     float t;
     f4 c;
     if (!GENERAL) {
-      cnt.add(C_RAYS, 1);
+      if (active) cnt.add(C_RAYS, 1);
       Hit h;
       if constexpr (kWaveCoop)
         h = sc.template primary<B>(o, d, 0.01f, tFarEff, active, stk);
+      else if constexpr (kWaveCount)
+        h = sc.template primary_counted<B>(o, d, 0.01f, tFarEff, active, stk, cnt);
       else
         h = sc.template intersect<B>(o, d, 0.01f, tFarEff, st, cnt);
       hit = h.hit;
@@ -1277,8 +1302,16 @@ __device__ __forceinline__ Hit rays_closest(const OctS<PACK> &sc, f3 o, f3 d, fl
   return h;
 }
 
+// Occupancy floor of the mesh's closest-hit query at 4 and 7 slots: the
+// primary kernels' 5 waves per SIMD. Left to itself the compiler took 94 VGPRs
+// there before the shared node fetch and 118 (4 waves) with it.
 template <class S, int SLOTS, int MODE>
-__global__ __launch_bounds__(kRBlock) void trace_rays_kernel(S sc, PlaneDev pl, rt_ray_batch b) {
+constexpr int trace_min_waves() {
+  return (S::kCoop && SLOTS <= 7 && MODE != kRaysAny) ? S::kMinWaves : 1;
+}
+template <class S, int SLOTS, int MODE>
+__global__ __launch_bounds__(kRBlock) __attribute__((amdgpu_waves_per_eu(trace_min_waves<S, SLOTS, MODE>())))
+void trace_rays_kernel(S sc, PlaneDev pl, rt_ray_batch b) {
   __shared__ uint32_t stk[stack_words<S, SLOTS>() * kRBlock];
   const int64_t i = (int64_t)blockIdx.x * kRBlock + threadIdx.x;
   // a partial last wave keeps its lanes without a ray: mesh_primary_wave needs
@@ -1433,7 +1466,7 @@ struct rt_scene {
   // empty slot is all +inf): the bounds a camera must not sit on (cull_rect)
   float root_child[48] = {};
   int64_t host_nodes = 0, host_inner = 0;
-  uint32_t n_inner = 0;  // inner nodes on the device (MeshDev::n_inner)
+  uint32_t n_inner = 0;  // inner nodes on the device
   float dmax2 = 0.0f;    // MeshDev::dmax2 (mesh_dmax2; 0: every ray takes the division)
   int32_t bvh_depth = 0;
   uint32_t n_tris = 0;   // triangle slots in d_tris (8 zero triangles follow)
@@ -1566,7 +1599,7 @@ __global__ __launch_bounds__(256) void brick_kernel(const float *__restrict__ sr
 }
 
 MeshDev mesh_dev(const rt_scene *s) {
-  MeshDev m{s->d_nodes, s->d_tris, s->root, {}, s->coop, s->n_inner, s->dmax2};
+  MeshDev m{s->d_nodes, s->d_tris, s->root, {}, s->coop, s->dmax2};
   for (int k = 0; k < 6; ++k) m.rbox[k] = s->root_box[k];
   return m;
 }
@@ -3505,17 +3538,18 @@ int rt_trace_rays_device(rt_scene *s, const rt_ray_batch *b, uint32_t flags, voi
   return launch_trace(s, *b, any ? kRaysAny : b->d_normal ? kRaysNormal : kRaysClosest, (hipStream_t)stream);
 }
 
-int rt_count_work(rt_scene *s, const rt_render_params *params, int32_t frames, int32_t W, int32_t H,
-                  uint32_t flags, const rt_tile *tile, int64_t counters[9]) {
-  if (!s || !params || frames <= 0 || !counters) return set_err(RT_E_INVALID, "bad arguments");
+// the counting kernel over `frames` frames: all C_ALL counters
+static int count_frames(rt_scene *s, const rt_render_params *params, int32_t frames, int32_t W, int32_t H,
+                        uint32_t flags, const rt_tile *tile, unsigned long long (&h)[C_ALL]) {
+  if (!s || !params || frames <= 0) return set_err(RT_E_INVALID, "bad arguments");
   int rc = no_instanced(s, "rt_count_work");
   if (rc) return rc;
   if ((rc = check_params(params, W, H))) return rc;
   const size_t px = (size_t)W * H;
   if ((rc = ensure_fb(s, px))) return rc;
   unsigned long long *d = nullptr;
-  HIP_TRY(hipMalloc(&d, C_NUM * sizeof(unsigned long long)));
-  hipError_t e = hipMemset(d, 0, C_NUM * sizeof(unsigned long long));
+  HIP_TRY(hipMalloc(&d, C_ALL * sizeof(unsigned long long)));
+  hipError_t e = hipMemset(d, 0, C_ALL * sizeof(unsigned long long));
   if (e == hipSuccess) HIP_NOTE(hipMemset(s->d_t, 0x7f, px * 4));
   for (int32_t f = 0; f < frames && e == hipSuccess && rc == RT_OK; ++f) {
     FrameArgs fa;
@@ -3523,12 +3557,36 @@ int rt_count_work(rt_scene *s, const rt_render_params *params, int32_t frames, i
         !(rc = fill_frame(fa, s, params + f, s->d_color, s->d_t, W, H, flags, tile)))
       rc = launch_render(s, fa, 0, d, 1);
   }
-  unsigned long long h[C_NUM] = {};
   if (e == hipSuccess && rc == RT_OK) e = hipMemcpy(h, d, sizeof(h), hipMemcpyDeviceToHost);
   HIP_NOTE(hipFree(d));
   if (rc) return rc;
   if (e != hipSuccess) return set_err(RT_E_DEVICE, std::string("rt_count_work: ") + hipGetErrorString(e));
+  return RT_OK;
+}
+
+int rt_count_work(rt_scene *s, const rt_render_params *params, int32_t frames, int32_t W, int32_t H,
+                  uint32_t flags, const rt_tile *tile, int64_t counters[9]) {
+  if (!counters) return set_err(RT_E_INVALID, "bad arguments");
+  unsigned long long h[C_ALL] = {};
+  const int rc = count_frames(s, params, frames, W, H, flags, tile, h);
+  if (rc) return rc;
   for (int i = 0; i < C_NUM; ++i) counters[i] = (int64_t)h[i];
+  return RT_OK;
+}
+
+// Diagnostic (not part of include/rtamd.h): the wave-level counters of the
+// primary mesh path over the same frames as rt_count_work. out[0] = expansions
+// that took the shared fetch (C_BVH_SHARED), out[1] = wave-level expansions of
+// either form below the root (C_BVH_WAVE_EXP). Zero for scenes and shading
+// modes that do not take that path.
+int rtx_count_share(rt_scene *s, const rt_render_params *params, int32_t frames, int32_t W, int32_t H,
+                    uint32_t flags, int64_t out[2]) {
+  if (!out) return set_err(RT_E_INVALID, "bad arguments");
+  unsigned long long h[C_ALL] = {};
+  const int rc = count_frames(s, params, frames, W, H, flags, nullptr, h);
+  if (rc) return rc;
+  out[0] = (int64_t)h[C_BVH_SHARED];
+  out[1] = (int64_t)h[C_BVH_WAVE_EXP];
   return RT_OK;
 }
 

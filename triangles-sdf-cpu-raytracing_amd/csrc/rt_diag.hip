@@ -8,6 +8,8 @@
 
 #include <algorithm>
 #include <string>
+#include <utility>
+#include <vector>
 
 #include "../../include/rtamd.h"
 #include "rt_error.h"
@@ -30,6 +32,80 @@ __global__ __launch_bounds__(256) void calib_read_kernel(const T *__restrict__ p
   uint32_t acc = 0;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) acc ^= fold(p[i]);
   if (acc == 0x9E3779B9u) out[0] = acc;
+}
+
+// rtx_l1_rate: how fast one CU's vector L1, and its LDS, answer loads that
+// always hit -- the two ways a wave can get a BVH node all its lanes share
+// (expand_node's per-lane loads against the shared fetch, rt_scenes.h).
+// Every wave runs `iters` rounds of kRateLoads 16-byte loads and waits for
+// each round, then leaves its shader cycles (s_memtime) and its 100 MHz ticks
+// (s_memrealtime). The loads are asm volatile so that none is merged or hoisted.
+//   mode 0: global_load_dwordx4, all 64 lanes on the same 16 bytes;
+//   mode 1: global_load_dwordx4, every lane on its own 16 bytes, the rounds'
+//           loads walking a 4 KiB set (L1-resident after the first round);
+//   mode 2: ds_read_b128 at 14 constant offsets of the wave's 224-byte pad,
+//           one address for all lanes (broadcast); a round is 14 reads.
+typedef unsigned int rate_u4 __attribute__((ext_vector_type(4)));
+constexpr int kRateLoads = 8, kRateLds = 14, kRateBlock = 1024;
+template <int OFF>
+__device__ __forceinline__ rate_u4 rate_lds_read(uint32_t l) {
+  rate_u4 v;
+  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=&v"(v) : "v"(l), "n"(OFF));
+  return v;
+}
+template <int OFF>
+__device__ __forceinline__ rate_u4 rate_global_read(const char *g) {
+  rate_u4 v;
+  asm volatile("global_load_dwordx4 %0, %1, off offset:%2" : "=&v"(v) : "v"(g), "n"(OFF));
+  return v;
+}
+template <int... K>
+__device__ __forceinline__ void rate_lds_round(uint32_t l, rate_u4 (&v)[kRateLds], std::integer_sequence<int, K...>) {
+  ((v[K] = rate_lds_read<16 * K>(l)), ...);
+}
+template <int... K>
+__device__ __forceinline__ void rate_global_round(const char *g, rate_u4 (&v)[kRateLoads],
+                                                  std::integer_sequence<int, K...>) {
+  ((v[K] = rate_global_read<1024 * (K & 3)>(g)), ...);  // mode 1: 4 x 1 KiB, twice
+}
+__global__ __launch_bounds__(kRateBlock) void l1_rate_kernel(int mode, int iters, const char *buf,
+                                                             unsigned long long *out) {
+  __shared__ __attribute__((aligned(16))) uint32_t pad[(kRateBlock / 64) * 56];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int i = lane; i < 56; i += 64) pad[wave * 56 + i] = (uint32_t)i;
+  __syncthreads();
+  const char *g = buf + (mode == 1 ? lane * 16 : 0);  // within buf's first 4 KiB
+  const uint32_t l = (uint32_t)(uintptr_t)(pad + wave * 56);  // LDS byte address of the wave's pad
+  rate_u4 acc = {0u, 0u, 0u, 0u};
+  const unsigned long long c0 = __builtin_amdgcn_s_memtime(), r0 = __builtin_amdgcn_s_memrealtime();
+  for (int it = 0; it < iters; ++it) {
+    if (mode == 2) {
+      rate_u4 v[kRateLds];
+      rate_lds_round(l, v, std::make_integer_sequence<int, kRateLds>{});
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+      for (int k = 0; k < kRateLds; ++k) {
+        asm volatile("" : "+v"(v[k]));
+        acc ^= v[k];
+      }
+    } else {
+      rate_u4 v[kRateLoads];
+      rate_global_round(g, v, std::make_integer_sequence<int, kRateLoads>{});
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#pragma unroll
+      for (int k = 0; k < kRateLoads; ++k) {
+        asm volatile("" : "+v"(v[k]));
+        acc ^= v[k];
+      }
+    }
+  }
+  const unsigned long long c1 = __builtin_amdgcn_s_memtime(), r1 = __builtin_amdgcn_s_memrealtime();
+  const uint32_t f = acc.x ^ acc.y ^ acc.z ^ acc.w;
+  const size_t w = (size_t)blockIdx.x * (kRateBlock / 64) + wave;
+  if (lane == 0) {
+    out[2 * w] = c1 - c0;
+    out[2 * w + 1] = (r1 - r0) | (f == 0x9E3779B9u ? 1ull << 63 : 0ull);  // (keeps acc alive; the buffer is zero)
+  }
 }
 
 __global__ void rcp_check_kernel(uint32_t base, unsigned long long *out) {
@@ -221,6 +297,39 @@ int rtx_calib_read(int64_t bytes, int32_t width, uint32_t *sink) {
   if (o) HIP_NOTE(hipFree(o));
   if (e != hipSuccess) return set_err(RT_E_DEVICE, std::string("calib read: ") + hipGetErrorString(e));
   if (sink) *sink = h;
+  return RT_OK;
+}
+
+// Diagnostic (tools/l1_rate.py): l1_rate_kernel's `mode` with `blocks`
+// workgroups of 16 waves, `iters` rounds per wave. out[0] = waves, out[1] =
+// load instructions per wave, out[2] / out[3] = sum / max over waves of shader
+// cycles, out[4] = sum over waves of 100 MHz ticks. Not part of rtamd.h.
+int rtx_l1_rate(int32_t mode, int32_t iters, int32_t blocks, uint64_t out[5]) {
+  if (!out || mode < 0 || mode > 2 || iters <= 0 || iters > (1 << 20) || blocks <= 0 || blocks > 4096)
+    return set_err(RT_E_INVALID, "bad arguments");
+  const size_t waves = (size_t)blocks * (kRateBlock / 64);
+  char *buf = nullptr;
+  unsigned long long *d = nullptr;
+  HIP_TRY(hipMalloc(&buf, 8192));
+  hipError_t e = hipMalloc(&d, waves * 2 * sizeof(unsigned long long));
+  if (e == hipSuccess) e = hipMemset(buf, 0, 8192);
+  if (e == hipSuccess) {
+    l1_rate_kernel<<<(unsigned)blocks, kRateBlock>>>(mode, iters, buf, d);
+    e = hipGetLastError();
+  }
+  std::vector<unsigned long long> h(waves * 2);
+  if (e == hipSuccess) e = hipMemcpy(h.data(), d, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost);
+  HIP_NOTE(hipFree(buf));
+  if (d) HIP_NOTE(hipFree(d));
+  if (e != hipSuccess) return set_err(RT_E_DEVICE, std::string("l1 rate: ") + hipGetErrorString(e));
+  out[0] = waves;
+  out[1] = (uint64_t)iters * (mode == 2 ? kRateLds : kRateLoads);
+  out[2] = out[3] = out[4] = 0;
+  for (size_t w = 0; w < waves; ++w) {
+    out[2] += h[2 * w];
+    out[3] = std::max<uint64_t>(out[3], h[2 * w]);
+    out[4] += h[2 * w + 1] & ~(1ull << 63);
+  }
   return RT_OK;
 }
 

@@ -162,7 +162,6 @@ __global__ void blas_entry_kernel(MeshDev *entry, MeshDev md) {
   entry->root = md.root;
   for (int k = 0; k < 6; ++k) entry->rbox[k] = md.rbox[k];
   entry->coop = md.coop;
-  entry->n_inner = md.n_inner;
   entry->dmax2 = md.dmax2;
 }
 

@@ -17,15 +17,20 @@ namespace rtd {
 // 0 bvh_inner 1 bvh_leaf 2 bvh_tri 3 grid_sdf 4 oct_node 5 oct_leaf 6 oct_step
 // 7 oct_normal 8 rays. NoCnt compiles away; LaneCnt is used only by the
 // counting kernel variant that feeds the algorithmic-bytes model.
+// After those nine (C_NUM: what rt_count_work returns and the byte model reads),
+// two wave-level counters of the primary mesh path, each added once per wave
+// and expansion by the first expanding lane: C_BVH_SHARED expansions that took
+// the shared fetch (RT_NODE_SHARE below), C_BVH_WAVE_EXP expansions of either
+// form (rtx_count_share).
 enum { C_BVH_INNER = 0, C_BVH_LEAF, C_BVH_TRI, C_GRID_SDF, C_OCT_NODE, C_OCT_LEAF, C_OCT_STEP,
-       C_OCT_NORMAL, C_RAYS, C_NUM };
+       C_OCT_NORMAL, C_RAYS, C_NUM, C_BVH_SHARED = C_NUM, C_BVH_WAVE_EXP, C_ALL };
 struct NoCnt {
   static constexpr bool kCounts = false;
   __device__ __forceinline__ void add(int, uint32_t) {}
 };
 struct LaneCnt {
   static constexpr bool kCounts = true;
-  uint32_t v[C_NUM];
+  uint32_t v[C_ALL];
   __device__ __forceinline__ void add(int i, uint32_t n) { v[i] += n; }
 };
 
@@ -60,11 +65,6 @@ struct MeshDev {
   // be fetched. Used only when all three 1/d components are finite.
   float rbox[6];
   bool coop;  // primary rays: cooperative tail enabled (diagnostic switch rtx_set_coop)
-  // inner nodes (BFS order: the first ones are the top levels). No kernel reads
-  // it at present; it keeps its place because without it the argument loads of
-  // coop and dmax2 merge and every mesh kernel's SGPR allocation shifts
-  // (profiles/r11/README.md): drop it in a pass that may move registers.
-  uint32_t n_inner;
   // rays with dot(d, d) <= dmax2 cannot make any triangle's |det| reach 2^125
   // (|det| <= 1.5 |e1| |e2| |d| in float arithmetic, max |e1| |e2| of the
   // scene measured at creation, mesh_dmax2): they take the triangle test with
@@ -170,19 +170,64 @@ __device__ __forceinline__ uint32_t select_word(uint4 cw0, uint4 cw1, uint32_t f
   for (int c = 1; c < 8; ++c) cf = (first_id == (uint32_t)c) ? cws[c] : cf;
   return cf;
 }
-template <bool FAST>
-__device__ __forceinline__ void expand_node(const rtl::GNode *__restrict__ node, f3 o, f3 inv,
-                                            float tNear, float tFar, uint32_t &list,
-                                            uint32_t &cnt, float &tfirst, uint32_t &cwfirst) {
+// The load phase of an expansion: the node's 14 vectors (12 of boxes, 2 of
+// child words), each lane from its own node.
+__device__ __forceinline__ void node_load(const rtl::GNode *__restrict__ node, float (&bx)[48], uint4 &cw0,
+                                          uint4 &cw1) {
   const float4 *p = reinterpret_cast<const float4 *>(node);
-  float bx[48];
 #pragma unroll
   for (int i = 0; i < 12; ++i) {
     const float4 v = p[i];
     bx[4 * i] = v.x; bx[4 * i + 1] = v.y; bx[4 * i + 2] = v.z; bx[4 * i + 3] = v.w;
   }
-  const uint4 cw0 = reinterpret_cast<const uint4 *>(node->child)[0];
-  const uint4 cw1 = reinterpret_cast<const uint4 *>(node->child)[1];
+  cw0 = reinterpret_cast<const uint4 *>(node->child)[0];
+  cw1 = reinterpret_cast<const uint4 *>(node->child)[1];
+}
+
+// The load phase where every expanding lane of the wave is at the same node
+// (RT_NODE_SHARE, primary mesh path): the per-lane form sends the vector L1 14
+// loads of 64 lanes for the same 224 bytes. Here the lane of rank r < 14 among
+// the expanding lanes loads vector r (one load instruction, 14 lanes) and
+// leaves it at 16 r of the wave's pad in LDS; every expanding lane then reads
+// the 14 vectors back at constant offsets, one address for all lanes: an LDS
+// broadcast each. The pad is private to the wave and a wave's LDS operations
+// complete in order, so the store, the reads and the next expansion's store
+// need no barrier; the wavefront-scope fences keep the compiler from moving
+// them past each other. node: the wave-uniform node; act: the expanding lanes
+// (at least kNodeVecs of them).
+#ifndef RT_NODE_SHARE
+#define RT_NODE_SHARE 1  // 0: every expansion loads per lane (A/B switch)
+#endif
+constexpr int kNodeVecs = 14;  // sizeof(GNode) / 16
+static_assert(sizeof(rtl::GNode) == 16 * kNodeVecs, "node pad: 14 vectors of 16 bytes");
+// The pad is addressed as LDS by type: through a generic pointer the compiler
+// sinks the two load forms into one sequence of flat loads at a selected
+// address, which pass the vector memory path again and wait on both counters.
+typedef float node_vec __attribute__((ext_vector_type(4)));
+typedef __attribute__((address_space(3))) node_vec NodePad;
+__device__ __forceinline__ void node_load_shared(const rtl::GNode *__restrict__ node, uint64_t act, NodePad *pad,
+                                                 float (&bx)[48], uint4 &cw0, uint4 &cw1) {
+  const uint32_t r = __builtin_amdgcn_mbcnt_hi((uint32_t)(act >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)act, 0u));
+  if (r < (uint32_t)kNodeVecs) pad[r] = reinterpret_cast<const node_vec *>(node)[r];
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+#pragma unroll
+  for (int i = 0; i < 12; ++i) {
+    const node_vec v = pad[i];
+    bx[4 * i] = v.x; bx[4 * i + 1] = v.y; bx[4 * i + 2] = v.z; bx[4 * i + 3] = v.w;
+  }
+  const node_vec w0 = pad[12], w1 = pad[13];
+  cw0 = uint4{__float_as_uint(w0.x), __float_as_uint(w0.y), __float_as_uint(w0.z), __float_as_uint(w0.w)};
+  cw1 = uint4{__float_as_uint(w1.x), __float_as_uint(w1.y), __float_as_uint(w1.z), __float_as_uint(w1.w)};
+}
+
+// The rest of an expansion, on the node's boxes and child words in registers.
+template <bool FAST>
+__device__ __forceinline__ void expand_loaded(const rtl::GNode *__restrict__ node, const float (&bx)[48],
+                                              uint4 cw0, uint4 cw1, f3 o, f3 inv, float tNear, float tFar,
+                                              uint32_t &list, uint32_t &cnt, float &tfirst,
+                                              uint32_t &cwfirst) {
   float t[8];
   uint32_t id[8];
 #pragma unroll
@@ -239,6 +284,15 @@ __device__ __forceinline__ void expand_node(const rtl::GNode *__restrict__ node,
     // across the network
     cwfirst = node->child[first_id];
   }
+}
+template <bool FAST>
+__device__ __forceinline__ void expand_node(const rtl::GNode *__restrict__ node, f3 o, f3 inv,
+                                            float tNear, float tFar, uint32_t &list,
+                                            uint32_t &cnt, float &tfirst, uint32_t &cwfirst) {
+  float bx[48];
+  uint4 cw0, cw1;
+  node_load(node, bx, cw0, cw1);
+  expand_loaded<FAST>(node, bx, cw0, cw1, o, inv, tNear, tFar, list, cnt, tfirst, cwfirst);
 }
 
 // A lane's stack: slots of F words each (a stack of SLOTS slots takes
@@ -332,10 +386,17 @@ constexpr int kCoopRays = RT_COOP_RAYS;
 //
 // Resuming a frame: its first child is visited from the expansion's registers;
 // every later child reloads its box and child word and redoes the slab test.
-template <int BLOCK, bool ANY, bool FAST, bool TAIL, uint32_t LB = RT_LEAF_BATCH, bool MAJ = false, int F, class CT>
+//
+// SHARE (with MAJ, the primary path): an expansion whose lanes are all at the
+// same node, at least kNodeVecs of them, fetches the node once for the wave
+// through pad, the wave's 224 bytes of LDS (node_load_shared); any other
+// expansion loads per lane. Modelled first on the CPU (tools/trav_sim.cpp
+// --share, bunny 1080p: 39 % of a frame's wave-level expansions).
+template <int BLOCK, bool ANY, bool FAST, bool TAIL, uint32_t LB = RT_LEAF_BATCH, bool MAJ = false, bool SHARE = false,
+          int F, class CT>
 __device__ __forceinline__ bool mesh_run(const MeshDev &sc, f3 o, f3 d, f3 inv, float tNear, float tFar,
                                          LdsStack<BLOCK, F> st, MState &S, CT &cnt, int coop_rays = kCoopRays,
-                                         int prio_iters = 0) {
+                                         int prio_iters = 0, NodePad *pad = nullptr) {
   uint32_t word = S.word, flist = S.flist, fcnt = S.fcnt, fnode = S.fnode, gk = S.gk;
   float fbest = S.fbest, gbest = S.gbest;
   int depth = S.depth;
@@ -400,7 +461,24 @@ __device__ __forceinline__ bool mesh_run(const MeshDev &sc, f3 o, f3 d, f3 inv, 
         uint32_t l, c, cwf;
         float tf;
         cnt.add(C_BVH_INNER, 1);
-        expand_node<FAST>(sc.nodes + word, o, inv, tNear, tFar, l, c, tf, cwf);
+        if constexpr (SHARE) {
+          const uint64_t act = __ballot(1);  // the expanding lanes
+          const uint32_t w0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)word);
+          const bool shared = __ballot(word != w0) == 0 && __popcll(act) >= kNodeVecs;
+          if constexpr (CT::kCounts) {
+            if ((threadIdx.x & 63) == (uint32_t)__builtin_ctzll(act)) {
+              cnt.add(C_BVH_WAVE_EXP, 1);
+              if (shared) cnt.add(C_BVH_SHARED, 1);
+            }
+          }
+          float bx[48];
+          uint4 cw0, cw1;
+          if (shared) node_load_shared(sc.nodes + w0, act, pad, bx, cw0, cw1);
+          else node_load(sc.nodes + word, bx, cw0, cw1);
+          expand_loaded<FAST>(sc.nodes + word, bx, cw0, cw1, o, inv, tNear, tFar, l, c, tf, cwf);
+        } else {
+          expand_node<FAST>(sc.nodes + word, o, inv, tNear, tFar, l, c, tf, cwf);
+        }
         if (c != 0) {
           if (depth >= 1 && fcnt == 0) {
             // tail call: the top frame has no child left, so it is replaced,
@@ -655,13 +733,18 @@ __device__ __forceinline__ void mesh_run_coop(const MeshDev &sc, f3 o, f3 d, f3 
 // call it, with active = false for lanes without a pixel): each lane traverses
 // its own ray until at most kCoopRays rays remain, then those finish in 8-lane
 // groups. The result is the same as mesh_trace's, bit for bit.
-template <int BLOCK, int F>
+// The node pad of the shared fetch (mesh_run, SHARE) is declared here, 224
+// bytes per wave of the block, so every kernel on this path gets it with the
+// call. cnt: the counting kernel's counters (with sc.coop off: the groups do
+// not count); the timed kernels pass none.
+template <int BLOCK, int F, class CT>
 __device__ __forceinline__ bool mesh_primary_wave(const MeshDev &sc, f3 o, f3 d, float tNear, float tFar,
                                                   bool active, uint32_t *stk_block, float &out_t,
-                                                  uint32_t &out_k, int coop_rays = kCoopRays,
-                                                  int prio_iters = 0) {
+                                                  uint32_t &out_k, int coop_rays, int prio_iters, CT &cnt) {
   if (prio_iters > 0) __builtin_amdgcn_s_setprio(0);  // a new tile starts at normal priority
-  NoCnt cnt;
+  constexpr bool kShare = RT_NODE_SHARE != 0;
+  __shared__ node_vec node_pad[kShare ? kNodeVecs * (BLOCK / 64) : 1];
+  NodePad *pad = (NodePad *)node_pad + (kShare ? kNodeVecs * (int)(threadIdx.x >> 6) : 0);
   const int lane = threadIdx.x & 63;
   LdsStack<BLOCK, F> st{stk_block + threadIdx.x};
   const f3 inv{1.0f / d.x, 1.0f / d.y, 1.0f / d.z};  // 1.0f / rayDir (:273)
@@ -688,13 +771,15 @@ __device__ __forceinline__ bool mesh_primary_wave(const MeshDev &sc, f3 o, f3 d,
   }
   bool suspended = false;
   if (pending && sc.coop)
-    suspended = fast ? mesh_run<BLOCK, false, true, true, RT_LEAF_BATCH_PRIMARY, true>(sc, o, d, inv, tNear, tFar, st, S,
-                                                                                        cnt, coop_rays, prio_iters)
-                     : mesh_run<BLOCK, false, false, true, RT_LEAF_BATCH_PRIMARY, true>(sc, o, d, inv, tNear, tFar, st, S,
-                                                                                         cnt, coop_rays, prio_iters);
+    suspended = fast ? mesh_run<BLOCK, false, true, true, RT_LEAF_BATCH_PRIMARY, true, kShare>(
+                           sc, o, d, inv, tNear, tFar, st, S, cnt, coop_rays, prio_iters, pad)
+                     : mesh_run<BLOCK, false, false, true, RT_LEAF_BATCH_PRIMARY, true, kShare>(
+                           sc, o, d, inv, tNear, tFar, st, S, cnt, coop_rays, prio_iters, pad);
   else if (pending)
-    (void)(fast ? mesh_run<BLOCK, false, true, false, RT_LEAF_BATCH_PRIMARY, true>(sc, o, d, inv, tNear, tFar, st, S, cnt)
-                : mesh_run<BLOCK, false, false, false, RT_LEAF_BATCH_PRIMARY, true>(sc, o, d, inv, tNear, tFar, st, S, cnt));
+    (void)(fast ? mesh_run<BLOCK, false, true, false, RT_LEAF_BATCH_PRIMARY, true, kShare>(
+                      sc, o, d, inv, tNear, tFar, st, S, cnt, kCoopRays, 0, pad)
+                : mesh_run<BLOCK, false, false, false, RT_LEAF_BATCH_PRIMARY, true, kShare>(
+                      sc, o, d, inv, tNear, tFar, st, S, cnt, kCoopRays, 0, pad));
   // Rays still traversing: at most kCoopRays per branch of the fast/exact
   // dispatch above (each branch suspends on its own lane count), so up to
   // 2 * kCoopRays; they are finished 8 at a time (one per 8-lane group; a
@@ -707,7 +792,12 @@ __device__ __forceinline__ bool mesh_primary_wave(const MeshDev &sc, f3 o, f3 d,
       rest &= rest - 1ull;
     }
     U &= ~R;
-    const int g = lane >> 3, k = lane & 7;
+    const int g = lane >> 3;
+    // k is made opaque: computed ahead of the traversal loop, the address of
+    // the group's triangle (tris + k) is live across it, where it spills and is
+    // reloaded after every expansion (profiles/r16/README.md)
+    int k = lane & 7;
+    asm volatile("" : "+v"(k));
     const int n = __popcll(R);
     uint64_t m = R;
     for (int i = 0; i < g && i < n; ++i) m &= m - 1;
@@ -746,6 +836,16 @@ __device__ __forceinline__ bool mesh_primary_wave(const MeshDev &sc, f3 o, f3 d,
   out_t = S.gbest;
   out_k = S.gk;
   return S.gk != rtl::kInvalidChild;
+}
+
+template <int BLOCK, int F>
+__device__ __forceinline__ bool mesh_primary_wave(const MeshDev &sc, f3 o, f3 d, float tNear, float tFar,
+                                                  bool active, uint32_t *stk_block, float &out_t,
+                                                  uint32_t &out_k, int coop_rays = kCoopRays,
+                                                  int prio_iters = 0) {
+  NoCnt cnt;
+  return mesh_primary_wave<BLOCK, F>(sc, o, d, tNear, tFar, active, stk_block, out_t, out_k, coop_rays, prio_iters,
+                                     cnt);
 }
 
 template <int BLOCK, bool ANY, int F, class CT>

@@ -177,6 +177,10 @@ _XSIGS = {
     "rtx_scene_mesh_constants": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]),
     "rtx_bvh_refit_host": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                      C.POINTER(C.c_int64), C.c_void_p, C.POINTER(C.c_int64)]),
+    # the counting kernel's wave-level counters of the primary mesh path
+    # (shared node fetches, expansions of either form)
+    "rtx_count_share": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_uint32,
+                                  C.c_void_p]),
 }
 
 

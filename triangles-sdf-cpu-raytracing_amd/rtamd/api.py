@@ -334,6 +334,17 @@ class IScene:
                                   C.byref(tile) if tile is not None else None, _p(out)))
         return dict(zip(self.COUNTER_NAMES, out.tolist()))
 
+    def count_share(self, params_list, W: int, H: int) -> dict:
+        """Wave-level counters of the primary mesh path over the given frames
+        (rtx_count_share, the counting kernel): expansions below the root that
+        fetched their node once for the wave through LDS, and all of them.
+        They are no part of count_work's dict, so algorithmic_bytes and the
+        oracle's counters stay what they are."""
+        arr = (RenderParams * len(params_list))(*params_list)
+        out = np.zeros(2, np.int64)
+        check(lib().rtx_count_share(self._handle(), arr, len(params_list), W, H, RT_FLAG_CLEAR, _p(out)))
+        return {"bvh_shared": int(out[0]), "bvh_wave_expansions": int(out[1])}
+
     @staticmethod
     def algorithmic_bytes(c: dict, pixels: int) -> int:
         """Bytes the reference's data layout touches for this work:
