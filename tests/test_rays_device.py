@@ -6,6 +6,7 @@ everywhere, t and normal on hits), whichever outputs are asked for, for every
 ray count around the wave and workgroup edges, and nothing outside [0, n) is
 touched.
 """
+import contextlib
 import ctypes as C
 import functools
 import zlib
@@ -188,6 +189,64 @@ def test_per_ray_intervals(gpu, name, plane):
         _assert_oracle(ref, _trace(gs, o_t, d_t, N, **kw), f"{name} per-ray tn={use_tn} tf={use_tf}")
         got = _trace(gs, o_t, d_t, N, outputs=("hit",), any_hit=True, **kw)
         assert np.array_equal(ref[0], got["hit"]), "any-hit mask differs"
+
+
+# Cells of the scene dispatch (csrc/rt_dispatch.h) that NAMES does not reach:
+# key -> (scene, rtx_set_grid_force value or None)
+EDGE_MESH = (15, 6000, "same")
+DISPATCH = {"mesh-15-slots": (EDGE_MESH, None), "grid-bricked": ("example_grid.grid", 1),
+            "grid-bricked-wide": ("example_grid.grid", 3), "sdf_6.octree": ("sdf_6.octree", None)}
+
+
+@contextlib.contextmanager
+def _dispatch_scene(key):
+    """-> (the oracle's (hit, t, normal, prim) with the plane off on [0.01,
+    100], GPU scene, rays as _rays gives them). The grid is created and traced
+    under its forced layout, which is restored afterwards (as
+    tests/test_gpu_shading.py does)."""
+    import rtamd
+    from rtamd import _lib
+    scene, force = DISPATCH[key]
+    if scene == EDGE_MESH:
+        v = S.edge_mesh(*EDGE_MESH)
+        i = np.arange(len(v), dtype=np.uint32)
+        o, d = _random_rays(N, zlib.crc32(f"rays-dispatch {EDGE_MESH}".encode()))
+        with rtamd.BVHBuilder(rtamd.SimpleMesh(v, i)) as gs:
+            # 15 stack slots: a tree of 9..16 levels (pick_maxd: depth - 1 slots)
+            assert 9 <= gs.tree_stats()[2] <= 16
+            ref = cpuref.RefScene.mesh(v, i).intersect_rays(o, d, 0.01, 100.0)
+            yield ref, gs, (o, d, torch.from_numpy(o).cuda(), torch.from_numpy(d).cuda())
+    elif force is not None:
+        L = rtamd.lib()
+        L.rtx_set_grid_force.argtypes = [C.c_int]
+        _lib.check(L.rtx_set_grid_force(force))
+        try:
+            with rtamd.SDFGrid(*S.inputs(scene)[1]) as gs:
+                yield _oracle(scene, False, 0.01, 100.0), gs, _rays(scene)
+        finally:
+            _lib.check(L.rtx_set_grid_force(0))
+    else:
+        ref = _oracle(scene, False, 0.01, 100.0)
+        yield ref, _set_plane(scene, False)[1], _rays(scene)
+
+
+@pytest.mark.parametrize("key", list(DISPATCH))
+def test_parity_on_further_dispatch_cells(gpu, key):
+    """test_parity_with_oracle (plane off, [0.01, 100]) on a 15-slot mesh, the
+    grid's bricked layout with buffer and with 64-bit address loads, and a
+    7-slot octree: closest hit with all four outputs and any hit through
+    rt_trace_rays_device, then rt_intersect_rays on the same rays."""
+    with _dispatch_scene(key) as (ref, gs, (o, d, o_t, d_t)):
+        assert int(ref[0].sum()) >= 128, "the oracle hits too few rays for the comparison to mean anything"
+        _assert_oracle(ref, _trace(gs, o_t, d_t, N), key)
+        a = _trace(gs, o_t, d_t, N, outputs=("hit",), any_hit=True)
+        assert np.array_equal(ref[0], a["hit"]), "any-hit mask differs"
+        g = gs.intersect(o, d, 0.01, 100.0)
+        h = g.hitten  # (test_gpu_parity.test_intersect_rays' comparison)
+        assert np.array_equal(ref[0].astype(bool), h), "rt_intersect_rays: hit mask differs"
+        assert np.array_equal(ref[3], g.prim), "rt_intersect_rays: primitive ids differ"
+        assert np.array_equal(_bits(ref[1][h]), _bits(g.t[h])), "rt_intersect_rays: t differs"
+        assert np.array_equal(_bits(ref[2][h]), _bits(g.normal[h])), "rt_intersect_rays: normal differs"
 
 
 SHAPES = [1, 63, 64, 65, 255, 257, 4 * 256 + 1]

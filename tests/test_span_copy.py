@@ -1,4 +1,4 @@
-"""The pageable drop-in's host copy (rth::copy_spans, rt_device.hip
+"""The pageable drop-in's host copy (rth::copy_spans, rt_dropin.hip
 render_cleared_zero_copy) on the CPU, no GPU: every row's recorded span of
 the staging frame reaches the caller's colour and t buffers, nothing outside
 the spans is touched, whatever the thread count and however the spans are

@@ -4,8 +4,10 @@
 # kernels; VAR_UNIT=rt_bvhgpu: the BVH builder); the other objects are the
 # shipping build's (the Makefile's object list).
 # With REV (a git revision), the unit and its headers are taken from that
-# revision instead of the working tree (A/B against a committed state; the
-# revision must split csrc/ into the same units, as the rest links from here).
+# revision instead of the working tree (A/B against a committed state). The
+# rest links from this tree's objects, so the revision must split csrc/ into
+# the same units: where it does not, the script stops and says so, and the
+# revision's library is built from a checkout of its own (git worktree, make).
 set -e
 R=$(cd $(dirname $0)/.. && pwd)
 P=$R/triangles-sdf-cpu-raytracing_amd
@@ -14,6 +16,15 @@ mkdir -p build/var lib
 U=${VAR_UNIT:-rt_device}
 SRC=csrc/$U.hip
 if [ -n "$3" ]; then
+  THEN=$(git -C $R ls-tree --name-only $3 triangles-sdf-cpu-raytracing_amd/csrc/ | grep -E '\.(hip|cpp)$' | xargs -n1 basename | sort | tr '\n' ' ')
+  NOW=$(ls csrc/*.hip csrc/*.cpp | xargs -n1 basename | sort | tr '\n' ' ')
+  if [ "$THEN" != "$NOW" ]; then
+    echo "build_variant.sh: revision $3 splits csrc/ into other units than this tree:" >&2
+    echo "  $3: $THEN" >&2
+    echo "  tree: $NOW" >&2
+    echo "its unit cannot link against this tree's objects; build its library from a checkout of its own (git worktree add, make) and select it through RTAMD_LIB" >&2
+    exit 1
+  fi
   S=build/var/src_$1
   rm -rf $S && mkdir -p $S/include $S/p/csrc
   for f in $(git -C $R ls-tree --name-only $3 triangles-sdf-cpu-raytracing_amd/csrc/); do

@@ -1,11 +1,16 @@
-// rt_device.hip -- the renderer: its HIP kernels (gfx950), struct rt_scene,
-// the launchers and schedules that instantiate the kernels, and the entry
-// points of include/rtamd.h that reach them (scene create / replicate /
-// destroy with the BVH builder choice, rt_render*, rt_untile_device,
-// rt_intersect_rays, rt_trace_rays_device, rt_count_work, rt_bench_frames, the rtx_set_* switches
-// of the launchers, rti::). The rest of the C ABI is in rt_runtime.hip
-// (errors, streams, host memory, devices), rt_abi_host.hip (loaders, camera,
-// output) and rt_diag.hip (device self-checks).
+// rt_device.hip -- the renderer: the HIP kernels (gfx950) that render frames
+// (one frame, a batch of frames by block dispatch, the persistent work-queue
+// form and the ray pump), the launchers and schedules that instantiate them,
+// the frame set-up with the tile cull, and the entry points of include/rtamd.h
+// that reach them (rt_render_device*, rt_clear_device, rt_stream_*,
+// rt_count_work, rt_bench_frames, the rtx_set_* switches of the launchers);
+// at the end of the file the ray queries (rt_intersect_rays,
+// rt_trace_rays_device), whose kernels share the render kernels' traversal
+// code. Scenes are made in rt_scene.hip, rt_render on host buffers is
+// rt_dropin.hip; rt_dispatch.h maps a scene to the kernel template
+// arguments. The rest of the C ABI is in rt_runtime.hip (errors,
+// streams, host memory, devices), rt_abi_host.hip (loaders, camera, output)
+// and rt_diag.hip (device self-checks).
 //
 // One thread per pixel; a 256-thread workgroup renders a 16x16 pixel block as
 // four 8x8 wave tiles (coherent rays share BVH / octree nodes and grid
@@ -15,34 +20,28 @@
 
 #include <algorithm>
 #include <atomic>
-#include <chrono>
 #include <cmath>
-#include <limits>
 #include <cstdio>
-#include <cstdlib>
-#include <cstring>
+#include <limits>
 #include <map>
 #include <mutex>
 #include <string>
 #include <type_traits>
 #include <utility>
-#include <vector>
 
 #include "../../include/rtamd.h"
+#include "rt_dispatch.h"
 #include "rt_error.h"
 #include "rt_host.h"
-#include "rt_instances.h"
-#include "rt_layout.h"
-#include "rt_math.h"
 #include "rt_queue.h"
-#include "rt_refit.h"
-#include "rt_scenes.h"
+#include "rt_scene.h"
+#include "rt_shade.h"
 
 using namespace rtd;
+using namespace rti;
 
 namespace {
 
-constexpr int kBlock = 256;  // 4 waves, 16x16 pixels
 // Workgroup of the persistent multi-frame kernel (render_persist_kernel), in
 // threads. Its waves are independent (each pulls its own items), so the block
 // only sets the granularity at which a launch's resources are handed back:
@@ -56,265 +55,6 @@ constexpr int kBlock = 256;  // 4 waves, 16x16 pixels
 constexpr int kPBlock = RT_PERSIST_BLOCK;
 static_assert(kPBlock % 64 == 0 && kPBlock >= 64 && kPBlock <= 1024, "persistent block: whole waves");
 constexpr int kTile = 16;
-
-struct FrameArgs {
-  rt_render_params P;
-  uint32_t *color;
-  float *t;
-  int32_t W, H;
-  uint32_t flags;
-  int32_t band_rows, rank, nranks, rows_local;
-  // screen rectangle outside which no ray of this frame can store a hit
-  // (cull_rect, mesh primary rays), in 8-pixel tiles of image columns: first
-  // tile | (last tile + 1) << 16. Its image rows travel the same way in
-  // P.reserved (this copy of the parameters is the library's own), so the
-  // batch keeps its size. kCullWhole: no rectangle, every tile is traced
-  uint32_t cull_x;
-  const uint32_t *order;  // block -> tile schedule (NULL: blockIdx order)
-  uint32_t *cost;         // per-tile cost of this frame (shader cycles, max over waves), or NULL
-  // one-frame kernel: bounding box of the pixels a hit was stored to, as
-  // (min x, -max x, min y, -max y) in buffer coordinates (four atomicMin
-  // words, initialised to INT32_MAX), or NULL (rt_render's partial download).
-  // With kFlagRowSpan in flags: per buffer row instead, the span of those
-  // pixels as (min x, -max x), two such words per row (rt_render's zero-copy
-  // cleared frames on pageable buffers: the host copies just these spans)
-  int32_t *hit_box;
-};
-
-// ---------------------------------------------------------- scene adapters --
-// kFields = LDS words per traversal frame (mesh: node, list|count, best t;
-// octree: children block, list|count, leaf mask|depth; grid: none). StackOf:
-// the adapter's per-lane stack; stack_words: its LDS words per lane at SLOTS
-// slots.
-// occupancy floors (min_waves below), overridable for A/B builds
-#ifndef RT_GRID_WAVES
-#define RT_GRID_WAVES 1
-#endif
-#ifndef RT_OCT_WAVES
-#define RT_OCT_WAVES 6
-#endif
-// mesh primary: a floor of 5 waves per SIMD (102 VGPRs). Built without the SLP
-// vectorizer (Makefile) the persistent kernel takes 96 VGPRs and 36 B of
-// scratch per lane at 5 waves, and is faster than at 4 (117 VGPRs, no
-// scratch): bunny 8 x 2 0.0855 -> 0.0825, the 1.1 M-triangle stand-in 0.3314 ->
-// 0.3149 ms/frame (profiles/r05/slp_ab.txt, two rounds). With SLP on, 5 waves
-// were slower.
-#ifndef RT_MESH_WAVES
-#define RT_MESH_WAVES 5
-#endif
-// shading kernels (GENERAL, the reference's default mode): a floor of 4 waves
-// per SIMD. The mesh's takes 135 VGPRs (3 waves) on its own; at 4 it gets 127
-// and spills 12 B per lane, and is faster: bunny default mode 1080p, 8 frames
-// x 2 / x 1 streams, 0.2267 -> 0.2068 / 0.2877 -> 0.2738 ms/frame (same box).
-// 1 = the compiler's choice (A/B switch).
-#ifndef RT_GENERAL_WAVES
-#define RT_GENERAL_WAVES 4
-#endif
-template <class S, int B>
-using StackOf = LdsStack<B, S::kFields>;
-template <class S, int SLOTS>
-constexpr int stack_words() { return SLOTS * S::kFields; }
-struct MeshS {
-  static constexpr int kFields = 3;
-  static constexpr bool kCoop = true;  // primary rays: wave-cooperative tail (mesh_primary_wave)
-  static constexpr int kMinWaves = RT_MESH_WAVES;
-  static constexpr int kQueueGroup = 2;  // wave tiles per work-queue item (render_persist_kernel)
-  MeshDev d;
-  // rays at or below which the wave hands its remaining rays to 8-lane groups
-  // (wave-uniform; the persistent kernel raises it for a wave's last item)
-  int coop_rays = kCoopRays;
-  // traversal iterations after which a wave raises its priority (0: never;
-  // the persistent kernel sets RT_HEAVY_PRIO, the one-frame kernel keeps 0)
-  int prio_iters = 0;
-  template <int B>
-  __device__ __forceinline__ Hit primary(f3 o, f3 dir, float tn, float tf, bool active,
-                                         uint32_t *stk) const {
-    float t;
-    uint32_t k;
-    Hit h = miss_hit();
-    if (mesh_primary_wave<B, kFields>(d, o, dir, tn, tf, active, stk, t, k, coop_rays, prio_iters) && active) {
-      h.hit = true;
-      h.t = t;
-      h.n = tri_normal(d.tris, k);
-      h.prim = (int64_t)d.tris[k].orig_id;
-    }
-    return h;
-  }
-  // the counting kernel's primary rays: the same wave path with the work
-  // counters, its cooperative tail off (the 8-lane groups do not count; they
-  // start below the shared fetch's lane threshold, so the wave-level counters
-  // are the timed kernels')
-  template <int B, class CT>
-  __device__ __forceinline__ Hit primary_counted(f3 o, f3 dir, float tn, float tf, bool active, uint32_t *stk,
-                                                 CT &cnt) const {
-    float t;
-    uint32_t k;
-    Hit h = miss_hit();
-    MeshDev dc = d;
-    dc.coop = false;
-    if (mesh_primary_wave<B, kFields>(dc, o, dir, tn, tf, active, stk, t, k, kCoopRays, 0, cnt) && active) {
-      h.hit = true;
-      h.t = t;
-      h.n = tri_normal(d.tris, k);
-      h.prim = (int64_t)d.tris[k].orig_id;
-    }
-    return h;
-  }
-  template <int B, class CT>
-  __device__ __forceinline__ Hit intersect(f3 o, f3 dir, float tn, float tf,
-                                           LdsStack<B, kFields> st, CT &cnt) const {
-    return mesh_intersect<B>(d, o, dir, tn, tf, st, cnt);
-  }
-  template <int B, class CT>
-  __device__ __forceinline__ bool occluded(f3 o, f3 dir, float tn, float tf,
-                                           LdsStack<B, kFields> st, CT &cnt) const {
-    return mesh_occluded<B>(d, o, dir, tn, tf, st, cnt);
-  }
-};
-template <int kMode>
-struct GridS {
-  static constexpr int kFields = 1;  // no traversal stack (one unused LDS word per lane)
-  static constexpr bool kCoop = false;
-  static constexpr int kMinWaves = RT_GRID_WAVES;
-  // block dispatch: a grid tile is too short for the queue's claims to pay
-  // (256^3, 8 frames x 2 streams: 0.0506 ms/frame vs 0.0541 at 4 tiles per claim)
-  static constexpr int kQueueGroup = 0;
-  GridDev d;
-  template <int B, class CT>
-  __device__ __forceinline__ Hit intersect(f3 o, f3 dir, float tn, float tf,
-                                           LdsStack<B, kFields> st, CT &cnt) const {
-    return grid_intersect<kMode>(d, o, dir, tn, tf, cnt);
-  }
-  template <int B, class CT>
-  __device__ __forceinline__ bool occluded(f3 o, f3 dir, float tn, float tf,
-                                           LdsStack<B, kFields> st, CT &cnt) const {
-    return grid_occluded<kMode>(d, o, dir, tn, tf, cnt);
-  }
-};
-// PACK: the traversal carries the node coordinates packed in one register
-// (OctXYZ; trees of depth <= 8, i.e. up to 7 stack slots)
-template <bool PACK>
-struct OctS {
-  static constexpr int kFields = kOctFields;
-  static constexpr bool kCoop = false;
-  static constexpr int kMinWaves = RT_OCT_WAVES;
-  static constexpr int kQueueGroup = 2;
-  OctDev d;
-  template <int B, class CT>
-  __device__ __forceinline__ Hit intersect(f3 o, f3 dir, float tn, float tf,
-                                           LdsStack<B, kFields> st, CT &cnt) const {
-    return oct_intersect<B, PACK>(d, o, dir, tn, tf, st, cnt);
-  }
-  template <int B, class CT>
-  __device__ __forceinline__ bool occluded(f3 o, f3 dir, float tn, float tf,
-                                           LdsStack<B, kFields> st, CT &cnt) const {
-    return oct_occluded<B, PACK>(d, o, dir, tn, tf, st, cnt);
-  }
-};
-
-// SceneUnion(scene, plane)::intersect (raytracing.hpp:87-93): both are
-// intersected, the smaller t wins, ties go to the plane.
-struct SurfHit {
-  Hit h;
-  float albedo;   // grey albedo: mesh/SDF 1.0, plane checker 0.0 / 1.0
-  float refl;     // reflectiveness: plane 0.3, else 0
-};
-template <class S, int B, class CT>
-__device__ __forceinline__ SurfHit union_intersect(const S &sc, const PlaneDev &pl, f3 o, f3 d,
-                                                   float tn, float tf, StackOf<S, B> st, CT &cnt) {
-  cnt.add(C_RAYS, 1);
-  SurfHit r{sc.template intersect<B>(o, d, tn, tf, st, cnt), 1.0f, 0.0f};
-  if (pl.on) {
-    float tp = kInf, ap = 1.0f;
-    const bool ph = plane_hit(pl, o, d, tn, tf, tp, ap);
-    if (!(r.h.t < (ph ? tp : kInf))) {
-      if (ph) {
-        r.h = Hit{true, tp, pl.n, -2};
-        r.albedo = ap;
-        r.refl = 0.3f;
-      } else {
-        r.h = miss_hit();
-        r.albedo = 1.0f;
-        r.refl = 0.0f;
-      }
-    }
-  }
-  return r;
-}
-// Shadow query: HitInfo::hitten of the union is the OR of both hitten flags.
-template <class S, int B, class CT>
-__device__ __forceinline__ bool union_occluded(const S &sc, const PlaneDev &pl, f3 o, f3 d, float tn,
-                                               float tf, StackOf<S, B> st, CT &cnt) {
-  cnt.add(C_RAYS, 1);
-  if (sc.template occluded<B>(o, d, tn, tf, st, cnt)) return true;
-  if (pl.on) {
-    float tp, ap;
-    return plane_hit(pl, o, d, tn, tf, tp, ap);
-  }
-  return false;
-}
-
-// Renderer::intersectionColor (raytracing.cpp:13-65) for one ray; the one
-// reflection bounce (maxDepth 2 -> 1) is expanded in place, no recursion.
-template <class S, int B, class CT>
-__device__ __forceinline__ f4 lambert_color(const S &sc, const PlaneDev &pl,
-                                            const rt_render_params &P, f3 o, f3 d,
-                                            const SurfHit &sh, f3 n, StackOf<S, B> st, CT &cnt) {
-  bool visible = true;
-  const f3 point = o + sh.h.t * d;
-  const f3 L{P.light_pos[0], P.light_pos[1], P.light_pos[2]};
-  if (P.enable_shadows) {
-    const f3 sd = normalize(L - point);
-    visible = !union_occluded<S, B>(sc, pl, point + 0.3f * sd, sd, 0.01f, 100.0f, st, cnt);
-  }
-  const float a = sh.albedo;
-  if (!visible) return f4{a * 0.1f, a * 0.1f, a * 0.1f, 1.0f};
-  const f3 ld = normalize(point - L);
-  const float lam = std_max(dot(-ld, n), 0.0f);  // Lambert (raytracing.cpp:8-11)
-  const f3 c = f3{a * 0.1f, a * 0.1f, a * 0.1f} + lam * f3{a, a, a};
-  return f4{std_min(c.x, 1.0f), std_min(c.y, 1.0f), std_min(c.z, 1.0f), 1.0f};
-}
-
-template <class S, int B, class CT>
-__device__ __forceinline__ f4 shade_one(const S &sc, const PlaneDev &pl, const rt_render_params &P,
-                                        f3 o, f3 d, float tFarEff, bool allow_refl, bool &hit,
-                                        float &t_out, StackOf<S, B> st, int64_t *prim, CT &cnt) {
-  const SurfHit sh = union_intersect<S, B>(sc, pl, o, d, 0.01f, tFarEff, st, cnt);
-  if (prim) *prim = sh.h.hit ? sh.h.prim : -1;
-  if (!sh.h.hit) {
-    hit = false;
-    t_out = kInf;
-    return f4{0.0f, 0.0f, 0.0f, 1.0f};
-  }
-  hit = true;
-  t_out = sh.h.t;
-  f3 n = sh.h.n;
-  if (dot(n, d) > 0) n = n * -1.0f;
-  f4 c;
-  if (P.shading_mode == RT_SHADING_NORMAL) {
-    c = f4{(n.x + 1.0f) / 2.0f, (n.y + 1.0f) / 2.0f, (n.z + 1.0f) / 2.0f, (1.0f + 1.0f) / 2.0f};
-  } else if (P.shading_mode == RT_SHADING_COLOR) {
-    c = f4{sh.albedo, sh.albedo, sh.albedo, 1.0f};
-  } else {
-    c = lambert_color<S, B>(sc, pl, P, o, d, sh, n, st, cnt);
-    if (allow_refl && P.enable_reflections && sh.refl > 0.0f) {
-      const float dn = dot(d, n);
-      const f3 R = normalize(n * dn * (-2.0f) + d);  // LiteMath reflect(dir, normal)
-      const f3 point = o + sh.h.t * d;
-      // recursive call with maxDepth 1, tPrev = +inf (raytracing.cpp:51-61)
-      const SurfHit rh = union_intersect<S, B>(sc, pl, point + 0.02f * R, R, 0.01f, 100.0f, st, cnt);
-      f4 rc{0.0f, 0.0f, 0.0f, 1.0f};
-      if (rh.h.hit) {
-        f3 rn = rh.h.n;
-        if (dot(rn, R) > 0) rn = rn * -1.0f;
-        rc = lambert_color<S, B>(sc, pl, P, point + 0.02f * R, R, rh, rn, st, cnt);
-      }
-      const float r = sh.refl, k = 1.0f - sh.refl;
-      c = f4{c.x * k + r * rc.x, c.y * k + r * rc.y, c.z * k + r * rc.z, c.w * k + r * rc.w};
-    }
-  }
-  return c;
-}
 
 // Framebuffer stores. The frame (8 B/pixel, 16.6 MB at 1080p) is written once
 // and never re-read by the kernel; plain stores keep every written line in the
@@ -349,26 +89,6 @@ __device__ __forceinline__ void fb_store(T *p, T v, bool peer) {
 // A per-wave system-scope fence there costs an L2 write-back per wave: the
 // one-frame kernel's 32 k waves took the frame from 0.19 to ~0.38 ms.)
 constexpr uint32_t kSysStoreFlags = RT_FLAG_TILE_NATURAL;
-// Internal flag (never passed through the C ABI; fill_frame rejects it): the
-// frame lives in host memory (rt_render's zero-copy cleared frames) and takes
-// system-scope stores, which write through this GPU's L2, with no per-wave
-// fence. Agent-scope stores leave the lines dirty in L2 for the end-of-kernel
-// release to write back over PCIe after the last wave; RTAMD_HOST_STORES=agent
-// keeps those (A/B switch).
-constexpr uint32_t kFlagHostFrame = 1u << 30;
-// Internal flag: FrameArgs::hit_box holds per-row spans (see FrameArgs).
-constexpr uint32_t kFlagRowSpan = 1u << 29;
-// Internal flag: the frame's eye rays take eye_ray_fast (fill_frame sets it
-// when fast_eye_ok holds for its projection and size).
-constexpr uint32_t kFlagFastEye = 1u << 28;
-// Internal flag: a row-band tile's rows are stored at their own rows of a full
-// W x H frame (as RT_FLAG_TILE_NATURAL) but with the frame's plain stores and
-// no peer fence: rt_multi_render's zero-copy slots, whose frame is one host
-// frame shared by every slot (the kernels' end-of-dispatch release before the
-// host's stream synchronisation covers their stores, as for rt_render's).
-constexpr uint32_t kFlagNatural = 1u << 27;
-// FrameArgs::cull_x / P.reserved of a frame without a rectangle: tiles [0, 65535)
-constexpr uint32_t kCullWhole = 0xFFFF0000u;
 __device__ __forceinline__ void peer_release(uint32_t flags) {
 #if RT_PEER_RELEASE
   if (flags & kSysStoreFlags) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
@@ -753,20 +473,6 @@ void render_kernel(S sc_arg, PlaneDev pl, FrameArgs fa,
 // silhouette, the per-frame tail) finish, so only the batch's last frame
 // leaves a tail. The per-frame arguments travel in the kernarg segment
 // (uniform blockIdx.z index: scalar loads).
-// At most 16 frames per launch (3.7 KiB of kernel arguments): row-band ranks
-// of a multi-GPU split render 1/N of each frame, so they take 16 frames per
-// launch to keep a launch's bulk long against its tail (bench.py --group;
-// rank compute at N = 8: 0.0170 -> 0.0133 ms/frame); whole frames stay at 8.
-#ifndef RT_MAX_BATCH
-#define RT_MAX_BATCH 16
-#endif
-constexpr int kMaxBatch = RT_MAX_BATCH;
-struct FrameBatch {
-  FrameArgs f[kMaxBatch];
-};
-// the whole batch travels in the kernarg segment next to the scene, plane and queue words
-static_assert(sizeof(FrameBatch) + 256 <= 4096, "FrameBatch exceeds the 4 KiB kernel-argument budget");
-
 // Workgroup of the multi-frame block dispatch (render_batch_kernel; grids and
 // the small row bands of N >= 4 ranks): one 8x8 wave tile per workgroup, so a
 // finished wave frees its slot for the next tile at once instead of waiting for
@@ -1220,151 +926,6 @@ void render_pump_kernel(P sc, FrameBatch fb, PersistQ q, int32_t nframes, int32_
   q_leave(q, kPumpHeads, lane);
 }
 
-template <class S, int SLOTS>
-__global__ __launch_bounds__(kBlock) void rays_kernel(S sc, PlaneDev pl, const float *o3,
-                                                       const float *d3, int64_t n, float tn,
-                                                       float tf, int32_t *hit, float *t,
-                                                       float *nrm, int64_t *prim) {
-  __shared__ uint32_t stk[stack_words<S, SLOTS>() * kBlock];
-  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-  if (i >= n) return;
-  StackOf<S, kBlock> st{stk + threadIdx.x};
-  const f3 o{o3[3 * i], o3[3 * i + 1], o3[3 * i + 2]};
-  const f3 d{d3[3 * i], d3[3 * i + 1], d3[3 * i + 2]};
-  NoCnt cnt;
-  const SurfHit sh = union_intersect<S, kBlock>(sc, pl, o, d, tn, tf, st, cnt);
-  hit[i] = sh.h.hit ? 1 : 0;
-  t[i] = sh.h.t;
-  nrm[3 * i] = sh.h.n.x;
-  nrm[3 * i + 1] = sh.h.n.y;
-  nrm[3 * i + 2] = sh.h.n.z;
-  prim[i] = sh.h.hit ? sh.h.prim : -1;
-}
-
-// ---- rt_trace_rays_device: IScene::intersect on device buffers -------------
-// One ray per lane, like rays_kernel, with the work chosen at compile time:
-// kRaysAny (S::occluded, one word per ray), kRaysClosest (no normal is
-// computed: no tri_normal triangle reload, no grid_normal, oct_trace without
-// NEED_NORMAL) and kRaysNormal. The outputs the caller left NULL and the
-// per-ray tNear / tFar arrays are wave-uniform branches on kernel arguments.
-// The mesh's closest hit is mesh_primary_wave (a wave's last rays finish in
-// 8-lane groups), the other traversals are per lane (DESIGN.md section 4;
-// what was measured against them is in section 8).
-enum { kRaysAny = 0, kRaysClosest = 1, kRaysNormal = 2 };
-// Workgroup of trace_rays_kernel: one wave. A ray batch has no tile that needs
-// four waves together, and a workgroup keeps its LDS stacks until its slowest
-// wave ends.
-constexpr int kRBlock = 64;
-// a launch's global size is a 32-bit count of work-items
-constexpr int64_t kMaxRayBlocks = (int64_t)(0xFFFFFFFFu / (uint32_t)kRBlock);
-
-// S::intersect with the normal (and the primitive id's load) optional
-template <int B, bool NORMAL, class CT>
-__device__ __forceinline__ Hit rays_closest(const MeshS &sc, f3 o, f3 d, float tn, float tf,
-                                            LdsStack<B, MeshS::kFields> st, bool want_prim, CT &cnt) {
-  float t;
-  uint32_t k;
-  Hit h = miss_hit();
-  if (mesh_trace<B, false>(sc.d, o, d, tn, tf, st, t, k, cnt)) {
-    h.hit = true;
-    h.t = t;
-    if constexpr (NORMAL) h.n = tri_normal(sc.d.tris, k);
-    if (want_prim) h.prim = (int64_t)sc.d.tris[k].orig_id;
-  }
-  return h;
-}
-template <int B, bool NORMAL, int kMode, class CT>
-__device__ __forceinline__ Hit rays_closest(const GridS<kMode> &sc, f3 o, f3 d, float tn, float tf,
-                                            LdsStack<B, GridS<kMode>::kFields>, bool, CT &cnt) {
-  Hit h = miss_hit();
-  f3 p;
-  uint32_t cell;
-  if (grid_march<kMode>(sc.d, o, d, tn, tf, h.t, p, cell, cnt)) {
-    h.hit = true;
-    if constexpr (NORMAL) h.n = grid_normal<kMode>(sc.d, p, cnt);
-    h.prim = (int64_t)cell;
-  } else {
-    h.t = kInf;
-  }
-  return h;
-}
-template <int B, bool NORMAL, bool PACK, class CT>
-__device__ __forceinline__ Hit rays_closest(const OctS<PACK> &sc, f3 o, f3 d, float tn, float tf,
-                                            LdsStack<B, kOctFields> st, bool, CT &cnt) {
-  Hit h = miss_hit();
-  uint32_t node;
-  if (oct_trace<B, NORMAL, PACK>(sc.d, o, d, tn, tf, st, h.t, h.n, node, cnt)) {
-    h.hit = true;
-    h.prim = (int64_t)node;
-  } else {
-    h.t = kInf;
-  }
-  return h;
-}
-
-// Occupancy floor of the mesh's closest-hit query at 4 and 7 slots: the
-// primary kernels' 5 waves per SIMD. Left to itself the compiler took 94 VGPRs
-// there before the shared node fetch and 118 (4 waves) with it.
-template <class S, int SLOTS, int MODE>
-constexpr int trace_min_waves() {
-  return (S::kCoop && SLOTS <= 7 && MODE != kRaysAny) ? S::kMinWaves : 1;
-}
-template <class S, int SLOTS, int MODE>
-__global__ __launch_bounds__(kRBlock) __attribute__((amdgpu_waves_per_eu(trace_min_waves<S, SLOTS, MODE>())))
-void trace_rays_kernel(S sc, PlaneDev pl, rt_ray_batch b) {
-  __shared__ uint32_t stk[stack_words<S, SLOTS>() * kRBlock];
-  const int64_t i = (int64_t)blockIdx.x * kRBlock + threadIdx.x;
-  // a partial last wave keeps its lanes without a ray: mesh_primary_wave needs
-  // the whole wave, so they carry active = false and touch no memory
-  const bool active = i < b.n;
-  StackOf<S, kRBlock> st{stk + threadIdx.x};
-  f3 o{0.0f, 0.0f, 0.0f}, d{0.0f, 0.0f, 1.0f};
-  float tn = b.tnear, tf = b.tfar;
-  if (active) {
-    o = f3{b.d_origin[3 * i], b.d_origin[3 * i + 1], b.d_origin[3 * i + 2]};
-    d = f3{b.d_dir[3 * i], b.d_dir[3 * i + 1], b.d_dir[3 * i + 2]};
-    if (b.d_tnear) tn = b.d_tnear[i];
-    if (b.d_tfar) tf = b.d_tfar[i];
-  }
-  NoCnt cnt;
-  if constexpr (MODE == kRaysAny) {
-    if (active) b.d_hit[i] = union_occluded<S, kRBlock>(sc, pl, o, d, tn, tf, st, cnt) ? 1 : 0;
-  } else {
-    Hit h = miss_hit();
-    bool traced = false;
-    if constexpr (std::is_same_v<S, MeshS>) {
-      // mesh_primary_wave takes one tNear for the wave (tFar is per ray):
-      // batches with a d_tnear array take the per-lane traversal below
-      if (!b.d_tnear) {
-        float t;
-        uint32_t k;
-        if (mesh_primary_wave<kRBlock, MeshS::kFields>(sc.d, o, d, tn, tf, active, stk, t, k) && active) {
-          h.hit = true;
-          h.t = t;
-          if constexpr (MODE == kRaysNormal) h.n = tri_normal(sc.d.tris, k);
-          if (b.d_prim) h.prim = (int64_t)sc.d.tris[k].orig_id;
-        }
-        traced = true;
-      }
-    }
-    if (!active) return;
-    if (!traced) h = rays_closest<kRBlock, MODE == kRaysNormal>(sc, o, d, tn, tf, st, b.d_prim != nullptr, cnt);
-    if (pl.on) {  // SceneUnion::intersect, as union_intersect
-      float tp = kInf, ap = 1.0f;
-      const bool ph = plane_hit(pl, o, d, tn, tf, tp, ap);
-      if (!(h.t < (ph ? tp : kInf))) h = ph ? Hit{true, tp, pl.n, -2} : miss_hit();
-    }
-    if (b.d_hit) b.d_hit[i] = h.hit ? 1 : 0;
-    if (b.d_t) b.d_t[i] = h.t;
-    if constexpr (MODE == kRaysNormal) {
-      b.d_normal[3 * i] = h.n.x;
-      b.d_normal[3 * i + 1] = h.n.y;
-      b.d_normal[3 * i + 2] = h.n.z;
-    }
-    if (b.d_prim) b.d_prim[i] = h.hit ? h.prim : -1;
-  }
-}
-
 // FrameBuffer::clear() (raytracing.hpp:16-19): 16 B per lane per buffer.
 __global__ void clear_kernel(uint32_t *c, float *t, int64_t n) {
   const int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
@@ -1377,44 +938,6 @@ __global__ void clear_kernel(uint32_t *c, float *t, int64_t n) {
       t[j] = kInf;
     }
   }
-}
-
-// rt_render's hit box / row spans (n words) to their pinned, mapped host
-// copy: system-scope stores, which the host reads after synchronising the
-// stream (a kernel in stream order instead of a small DMA copy)
-__global__ void box_out_kernel(const int32_t *d_box, int32_t *h_box, int n) {
-  for (int i = (int)(blockIdx.x * blockDim.x + threadIdx.x); i < n; i += (int)(gridDim.x * blockDim.x))
-    __hip_atomic_store(h_box + i, d_box[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-
-// the staging frame's stored spans (the row spans of its last frame) cleared
-// again, and the span words reset for the next frame: block y clears row y's
-// span. A row without hits holds (INT32_MAX, INT32_MAX): it returns before
-// any index is formed from them.
-__global__ void clear_spans_kernel(uint32_t *c, float *t, int32_t *span, int32_t W) {
-  const int32_t y = (int32_t)blockIdx.x, lo = span[2 * y], hi = -span[2 * y + 1];
-  __syncthreads();  // (every thread has read the row's span)
-  if (threadIdx.x == 0) {
-    span[2 * y] = INT32_MAX;
-    span[2 * y + 1] = INT32_MAX;
-  }
-  if (lo > hi || lo < 0 || hi >= W) return;
-  for (int32_t x = lo + (int32_t)threadIdx.x; x <= hi; x += (int32_t)blockDim.x) {
-    const size_t i = (size_t)y * (size_t)W + (size_t)x;
-    c[i] = 0u;
-    t[i] = kInf;
-  }
-}
-
-__global__ void untile_kernel(const uint32_t *pc, const float *pt, int64_t per_rank, uint32_t *c,
-                              float *t, int W, int H, int band_rows, int nranks) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= (int64_t)W * H) return;
-  const int yo = (int)(i / W), x = (int)(i - (int64_t)yo * W);
-  const int b = yo / band_rows, r = b % nranks, k = b / nranks;
-  const int64_t src = (int64_t)r * per_rank + ((int64_t)k * band_rows + (yo - b * band_rows)) * W + x;
-  if (c) c[i] = pc[src];
-  if (t) t[i] = pt[src];
 }
 
 // Block schedule for the next frame from this frame's per-tile costs:
@@ -1452,192 +975,12 @@ __global__ __launch_bounds__(1024) void order_kernel(uint32_t *cost, uint32_t *o
 
 }  // namespace
 
-// ================================================================== C ABI ==
-struct rt_scene {
-  int kind = 0;
-  int device = 0;
-  int32_t maxd = 1;  // LDS stack frames the kernel is instantiated for
-  // mesh
-  rtl::GNode *d_nodes = nullptr;
-  rtl::GTri *d_tris = nullptr;
-  uint32_t root = rtl::kInvalidChild;
-  float root_box[6] = {0, 0, 0, 0, 0, 0};
-  // the root node's eight child boxes (xMin xMax yMin yMax zMin zMax each; an
-  // empty slot is all +inf): the bounds a camera must not sit on (cull_rect)
-  float root_child[48] = {};
-  int64_t host_nodes = 0, host_inner = 0;
-  uint32_t n_inner = 0;  // inner nodes on the device
-  float dmax2 = 0.0f;    // MeshDev::dmax2 (mesh_dmax2; 0: every ray takes the division)
-  int32_t bvh_depth = 0;
-  uint32_t n_tris = 0;   // triangle slots in d_tris (8 zero triangles follow)
-  uint32_t root_nchild = 0;  // children of an inner root (slots 0 .. root_nchild-1)
-  // a mesh created with RT_MESH_DYNAMIC (rt_scene_update_vertices*): the
-  // creation index array and a vertex staging buffer on the device, the first
-  // node index of every depth level (+ the node count), the edge-bound word of
-  // tri_edge_bound_kernel and the pinned host words the update reads back
-  // (48 root child box floats, then the edge bound)
-  bool dynamic = false;
-  int64_t nverts = 0;
-  uint32_t *d_idx = nullptr;
-  float *d_vstage = nullptr;
-  uint32_t *d_edge = nullptr;
-  uint32_t *h_refit = nullptr;
-  std::vector<uint32_t> level_first;
-  int64_t dyn_bytes = 0;  // what `dynamic` added to dev_bytes
-  uint64_t version = 0;   // counts the updates (rt_multi re-copies its replicas when it moves)
-  // grid
-  float *d_vals = nullptr;
-  uint32_t size[3] = {0, 0, 0};
-  bool grid_bricked = false;  // device layout (rt_scenes.h GridDev): bricked, or the reference's linear
-  // octree
-  rtl::OctWord *d_child = nullptr;
-  rtl::OctVals *d_ovals = nullptr;
-  int32_t oct_depth = 0;
-  // instanced (RT_SCENE_INSTANCED): the instance records and the table of the
-  // bottom-level scenes' MeshDev on the device; the scenes themselves (not
-  // owned) and the update counter each table entry was written from. Nothing
-  // here depends on a pose.
-  rti::InstRec *d_inst = nullptr;
-  MeshDev *d_blas = nullptr;
-  int32_t ninst = 0;
-  std::vector<rt_scene *> blas;
-  std::vector<uint64_t> blas_seen;
-  PlaneDev plane{};
-  int64_t dev_bytes = 0;
-  // cached buffers for host-buffer entry points
-  uint32_t *d_color = nullptr;
-  float *d_t = nullptr;
-  size_t fb_cap = 0;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  hipEvent_t ev_host = nullptr;  // rt_render's pageable cleared frame: the spans are on the host
-  hipStream_t xs[2] = {nullptr, nullptr};  // rt_render: colour / t copy streams (render on xs[0])
-  hipEvent_t xev = nullptr;
-  // rt_render: FrameArgs::hit_box of its frame (4 words) and a pinned,
-  // mapped host copy (h_hit_box_dev: its device address, box_out_kernel)
-  int32_t *d_hit_box = nullptr;
-  int32_t *h_hit_box = nullptr;
-  int32_t *h_hit_box_dev = nullptr;
-  // the pageable zero-copy path: FrameArgs::row_span (2 words per row) and its
-  // pinned, mapped host copy, for span_cap rows
-  int32_t *d_row_span = nullptr;
-  int32_t *h_row_span = nullptr;
-  int32_t *h_row_span_dev = nullptr;
-  int32_t span_cap = 0;
-  // rt_render's staging frame for a cleared frame on pageable buffers: pinned
-  // host memory the kernel stores its hits into (zero-copy), kept cleared
-  rtdma::HostStage stage{hipHostMallocDefault};
-  // cost-ordered block schedule (see launch_render), double-buffered: frame k
-  // of the scene's one-frame kernel records its tiles' costs into d_cost[k & 1]
-  // and dispatches in the order d_order[k & 1] that frame k - 2's costs gave;
-  // frame k's own order is computed by order_kernel on the side stream
-  // sched_os as soon as frame k is done (frame_ev), beside frame k + 1, and
-  // ord_ev[k & 1] marks it done. sched_key[b] = the grid (gx << 16 | gy) whose
-  // order d_order[b] holds (0: none). sched_on = false renders in plain
-  // blockIdx order
-  uint32_t *d_cost[2] = {nullptr, nullptr};
-  uint32_t *d_order[2] = {nullptr, nullptr};
-  uint32_t sched_key[2] = {0, 0};
-  bool ord_rec[2] = {false, false};
-  int sched_par = 0;
-  uint32_t sched_cap = 0;
-  bool sched_on = true;
-  bool coop = true;  // mesh primary rays: cooperative tail (rtx_set_coop)
-  hipStream_t last_stream = nullptr;   // stream of the previous frame (scheduled or not)
-  hipStream_t sched_os = nullptr;      // side stream of the order kernels
-  hipEvent_t ord_ev[2] = {nullptr, nullptr};
-  hipEvent_t frame_ev = nullptr;
-  bool pump_on = false;  // primary-ray batches on the ray pump (rtx_set_pump)
-};
-
-namespace {
-
-// bricked sample count of a grid (rt_scenes.h GridDev)
-uint64_t grid_bricked_samples(const uint32_t size[3]) {
-  return (uint64_t)grid_bricks(size[0]) * grid_bricks(size[1]) * grid_bricks(size[2]) * 64u;
-}
-
-// device samples of a grid scene (s->grid_bricked picks the layout)
-uint64_t grid_samples(const rt_scene *s) {
-  return s->grid_bricked ? grid_bricked_samples(s->size) : (uint64_t)s->size[0] * s->size[1] * s->size[2];
-}
-
-// diagnostic (rtx_set_grid_force): bit 0 = grids created from now on take the
-// bricked layout whatever their size, bit 1 = every grid launch takes the 64-bit
-// address path (no buffer loads); tests reach each grid_mode branch with it
-int g_grid_force = 0;
-
-GridDev grid_dev(const rt_scene *s) {
-  const uint64_t n = grid_samples(s);
-  // buffer loads: 32-bit byte offsets and num_records, so only grids below
-  // 4 GiB (a grid of exactly 2^32 bytes would put its last sample past a
-  // saturated num_records) -- larger ones take the 64-bit address path
-  const uint32_t bytes = 4 * n < (1ull << 32) ? (uint32_t)(4 * n) : 0u;
-  if (!s->grid_bricked) return GridDev{s->d_vals, s->size[0], s->size[1], s->size[2], s->size[2],
-                                       s->size[1] * s->size[2], bytes};
-  const uint32_t ys = grid_bricks(s->size[2]) * 64u;
-  return GridDev{s->d_vals, s->size[0], s->size[1], s->size[2], ys, grid_bricks(s->size[1]) * ys, bytes};
-}
-
-int grid_mode(const rt_scene *s, const GridDev &gd) {
-  // buffer mode: 32-bit byte offsets and 24-bit stride multiplies (grid_mul)
-  const bool buf = gd.bytes != 0 && gd.xs < (1u << 24) && gd.ys < (1u << 24) && !(g_grid_force & 2);
-  return (buf ? kGridBuf : 0) | (s->grid_bricked ? kGridBricked : 0);
-}
-
-// reference x-major values -> 4x4x4 bricks; one thread per bricked sample
-// (padding samples get 0 and are never read)
-__global__ __launch_bounds__(256) void brick_kernel(const float *__restrict__ src, float *__restrict__ dst,
-                                                    uint32_t sx, uint32_t sy, uint32_t sz, uint64_t n) {
-  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  const uint32_t nby = grid_bricks(sy), nbz = grid_bricks(sz);
-  const uint32_t l = (uint32_t)(i & 63u);
-  const uint64_t b = i >> 6;
-  const uint32_t bz = (uint32_t)(b % nbz), by = (uint32_t)((b / nbz) % nby), bx = (uint32_t)(b / nbz / nby);
-  const uint32_t x = bx * 4 + (l >> 4), y = by * 4 + ((l >> 2) & 3u), z = bz * 4 + (l & 3u);
-  dst[i] = (x < sx && y < sy && z < sz) ? src[((uint64_t)x * sy + y) * sz + z] : 0.0f;
-}
-
-MeshDev mesh_dev(const rt_scene *s) {
-  MeshDev m{s->d_nodes, s->d_tris, s->root, {}, s->coop, s->dmax2};
-  for (int k = 0; k < 6; ++k) m.rbox[k] = s->root_box[k];
-  return m;
-}
-
-// LDS frame slots per lane for a tree with `depth` inner levels: the top frame
-// lives in registers, so depth-1 slots. Sized to the tree (not a worst case)
-// so the stack does not cap occupancy: 4 slots x 12 B x 256 lanes = 12 KiB.
-int pick_maxd(int depth, int32_t &maxd) {
-  const int need = depth > 1 ? depth - 1 : 1;
-  const int options[] = {4, 7, 15, 31};
-  for (int m : options)
-    if (need <= m) { maxd = m; return RT_OK; }
-  return set_err(RT_E_INVALID, "tree deeper than 32 levels");
-}
+namespace rti {
 
 int ensure_events(rt_scene *s) {
   if (!s->ev0) HIP_TRY(hipEventCreate(&s->ev0));
   if (!s->ev1) HIP_TRY(hipEventCreate(&s->ev1));
   if (!s->ev_host) HIP_TRY(hipEventCreateWithFlags(&s->ev_host, hipEventDisableTiming));
-  return RT_OK;
-}
-
-// rt_render's two copy/render streams (non-blocking: no implicit sync with
-// the null stream) and the event that orders the uploads before the kernel
-int ensure_copy_streams(rt_scene *s) {
-  for (int k = 0; k < 2; ++k)
-    if (!s->xs[k]) {
-      HIP_TRY(hipStreamCreateWithFlags(&s->xs[k], hipStreamNonBlocking));
-      char label[64];
-      std::snprintf(label, sizeof label, "scene %p stream %s", (void *)s, k ? "t" : "render/colour");
-      rterr::stream_add(s->xs[k], s->device, label);
-    }
-  if (!s->xev) HIP_TRY(hipEventCreateWithFlags(&s->xev, hipEventDisableTiming));
-  if (!s->d_hit_box) HIP_TRY(hipMalloc(&s->d_hit_box, 4 * sizeof(int32_t)));
-  if (!s->h_hit_box_dev) {  // (guarded on the device address: a failed lookup is retried next call)
-    if (!s->h_hit_box) HIP_TRY(hipHostMalloc(&s->h_hit_box, 4 * sizeof(int32_t), hipHostMallocMapped));
-    HIP_TRY(hipHostGetDevicePointer((void **)&s->h_hit_box_dev, s->h_hit_box, 0));
-  }
   return RT_OK;
 }
 
@@ -1653,6 +996,10 @@ int ensure_fb(rt_scene *s, size_t px) {
   s->fb_cap = px;
   return RT_OK;
 }
+
+}  // namespace rti
+
+namespace {
 
 template <class S, int MAXD>
 void launch_render_t(const S &sc, const PlaneDev &pl, const FrameArgs &fa, bool general,
@@ -1675,18 +1022,6 @@ void launch_render_t(const S &sc, const PlaneDev &pl, const FrameArgs &fa, bool 
     else
       render_kernel<S, MAXD, false, 0><<<fgrid, kFBlock, 0, stream>>>(sc, pl, fa, nullptr);
   }
-}
-
-// The scene's staging frame (rtdma::HostStage) for px pixels, used by
-// rt_render on pageable caller buffers (host copies on one side, DMA on the
-// other). Its streams are synchronised before a smaller frame is replaced.
-int ensure_stage(rt_scene *s, size_t px) {
-  if (px <= s->stage.cap) return RT_OK;
-  if (s->xs[0]) HIP_TRY(hipStreamSynchronize(s->xs[0]));  // (the previous frame's work on the old frame)
-  if (s->xs[1]) HIP_TRY(hipStreamSynchronize(s->xs[1]));
-  if (const hipError_t e = s->stage.ensure(px))
-    return set_err(RT_E_DEVICE, std::string("staging frame: ") + hipGetErrorString(e));
-  return RT_OK;
 }
 
 // Cost-ordered schedule state for a frame of grid gx x gy blocks on `stream`.
@@ -1775,8 +1110,12 @@ int schedule_end(rt_scene *s, const FrameArgs &fa, uint32_t gx, uint32_t gy, hip
   return RT_OK;
 }
 
-int launch_render(rt_scene *s, const FrameArgs &fa_in, hipStream_t stream,
-                  unsigned long long *counters = nullptr, int diag = 0, bool sched = true) {
+}  // namespace
+
+namespace rti {
+
+int launch_render(rt_scene *s, const FrameArgs &fa_in, hipStream_t stream, unsigned long long *counters, int diag,
+                  bool sched) {
   FrameArgs fa = fa_in;
   const bool general = s->plane.on || fa.P.shading_mode != RT_SHADING_NORMAL;
   const uint32_t gx = (fa.W + kFTile - 1) / kFTile, gy = (fa.rows_local + kFTile - 1) / kFTile;
@@ -1786,38 +1125,19 @@ int launch_render(rt_scene *s, const FrameArgs &fa_in, hipStream_t stream,
     const int rc = schedule_begin(s, fa, gx, gy, stream);
     if (rc) return rc;
   }
-  if (s->kind == RT_SCENE_MESH) {
-    const MeshDev md = mesh_dev(s);
-    switch (s->maxd) {
-      case 4: launch_render_t<MeshS, 4>(MeshS{md}, s->plane, fa, general, stream, counters, diag); break;
-      case 7: launch_render_t<MeshS, 7>(MeshS{md}, s->plane, fa, general, stream, counters, diag); break;
-      case 15: launch_render_t<MeshS, 15>(MeshS{md}, s->plane, fa, general, stream, counters, diag); break;
-      default: launch_render_t<MeshS, 31>(MeshS{md}, s->plane, fa, general, stream, counters, diag); break;
-    }
-  } else if (s->kind == RT_SCENE_GRID) {
-    const GridDev gd = grid_dev(s);
-    switch (grid_mode(s, gd)) {
-      case kGridBuf | kGridBricked:
-        launch_render_t<GridS<kGridBuf | kGridBricked>, 1>({gd}, s->plane, fa, general, stream, counters, diag);
-        break;
-      case kGridBricked: launch_render_t<GridS<kGridBricked>, 1>({gd}, s->plane, fa, general, stream, counters, diag); break;
-      default: launch_render_t<GridS<kGridBuf>, 1>({gd}, s->plane, fa, general, stream, counters, diag); break;
-    }
-  } else if (s->kind == RT_SCENE_OCTREE) {
-    const OctDev od{s->d_child, s->d_ovals};
-    switch (s->maxd) {
-      case 4: launch_render_t<OctS<true>, 4>(OctS<true>{od}, s->plane, fa, general, stream, counters, diag); break;
-      case 7: launch_render_t<OctS<true>, 7>(OctS<true>{od}, s->plane, fa, general, stream, counters, diag); break;
-      case 15: launch_render_t<OctS<false>, 15>(OctS<false>{od}, s->plane, fa, general, stream, counters, diag); break;
-      default: launch_render_t<OctS<false>, 31>(OctS<false>{od}, s->plane, fa, general, stream, counters, diag); break;
-    }
-  } else {
+  if (!dispatch_scene(s, [&](const auto &sc, auto slots) {
+        launch_render_t<std::decay_t<decltype(sc)>, decltype(slots)::value>(sc, s->plane, fa, general, stream,
+                                                                            counters, diag);
+      }))
     return set_err(RT_E_STATE, "scene has no geometry");
-  }
   HIP_TRY(hipGetLastError());
   if (diag == 0 && sched) return schedule_end(s, fa, gx, gy, stream);
   return RT_OK;
 }
+
+}  // namespace rti
+
+namespace {
 
 // Work-queue heads of render_persist_kernel, one set per (device, stream):
 // launches on one stream run in order, and each launch's last wave resets its
@@ -2102,6 +1422,10 @@ int launch_batch_t(rt_scene *s, const S &sc, const PlaneDev &pl, const FrameBatc
   return RT_OK;
 }
 
+}  // namespace
+
+namespace rti {
+
 // One launch for n <= kMaxBatch frames of equal size / tile (blockIdx order).
 int launch_batch(rt_scene *s, FrameBatch &fb, int n, hipStream_t stream) {
   const bool general = s->plane.on || fb.f[0].P.shading_mode != RT_SHADING_NORMAL;
@@ -2112,39 +1436,19 @@ int launch_batch(rt_scene *s, FrameBatch &fb, int n, hipStream_t stream) {
     fb.f[i].cost = nullptr;
   }
   int rc = RT_OK;
-  if (s->kind == RT_SCENE_MESH) {
-    const MeshDev md = mesh_dev(s);
-    switch (s->maxd) {
-      case 4: rc = launch_batch_t<MeshS, 4>(s, MeshS{md}, s->plane, fb, n, general, stream); break;
-      case 7: rc = launch_batch_t<MeshS, 7>(s, MeshS{md}, s->plane, fb, n, general, stream); break;
-      case 15: rc = launch_batch_t<MeshS, 15>(s, MeshS{md}, s->plane, fb, n, general, stream); break;
-      default: rc = launch_batch_t<MeshS, 31>(s, MeshS{md}, s->plane, fb, n, general, stream); break;
-    }
-  } else if (s->kind == RT_SCENE_GRID) {
-    const GridDev gd = grid_dev(s);
-    const int mode = grid_mode(s, gd);
-    switch (mode) {
-      case kGridBuf | kGridBricked:
-        rc = launch_batch_t<GridS<kGridBuf | kGridBricked>, 1>(s, {gd}, s->plane, fb, n, general, stream);
-        break;
-      case kGridBricked: rc = launch_batch_t<GridS<kGridBricked>, 1>(s, {gd}, s->plane, fb, n, general, stream); break;
-      default: rc = launch_batch_t<GridS<kGridBuf>, 1>(s, {gd}, s->plane, fb, n, general, stream); break;
-    }
-  } else if (s->kind == RT_SCENE_OCTREE) {
-    const OctDev od{s->d_child, s->d_ovals};
-    switch (s->maxd) {
-      case 4: rc = launch_batch_t<OctS<true>, 4>(s, OctS<true>{od}, s->plane, fb, n, general, stream); break;
-      case 7: rc = launch_batch_t<OctS<true>, 7>(s, OctS<true>{od}, s->plane, fb, n, general, stream); break;
-      case 15: rc = launch_batch_t<OctS<false>, 15>(s, OctS<false>{od}, s->plane, fb, n, general, stream); break;
-      default: rc = launch_batch_t<OctS<false>, 31>(s, OctS<false>{od}, s->plane, fb, n, general, stream); break;
-    }
-  } else {
+  if (!dispatch_scene(s, [&](const auto &sc, auto slots) {
+        rc = launch_batch_t<std::decay_t<decltype(sc)>, decltype(slots)::value>(s, sc, s->plane, fb, n, general,
+                                                                                stream);
+      }))
     return set_err(RT_E_STATE, "scene has no geometry");
-  }
   if (rc) return rc;
   HIP_TRY(hipGetLastError());
   return RT_OK;
 }
+
+}  // namespace rti
+
+namespace {
 
 // Whether eye_ray_fast gives eye_ray's bits for every pixel of a W x H frame
 // with this inverse projection: the operand ranges rtm::div_mk needs, bounded
@@ -2346,6 +1650,10 @@ bool cull_rect(const rt_render_params *p, int32_t W, int32_t H, const float box[
   return true;
 }
 
+}  // namespace
+
+namespace rti {
+
 int fill_frame(FrameArgs &fa, const rt_scene *s, const rt_render_params *p, uint32_t *c, float *t, int32_t W,
                int32_t H, uint32_t flags, const rt_tile *tile) {
   fa.P = *p;
@@ -2390,715 +1698,9 @@ int fill_frame(FrameArgs &fa, const rt_scene *s, const rt_render_params *p, uint
   return RT_OK;
 }
 
-template <class S, int MAXD>
-void launch_rays_t(const S &sc, const PlaneDev &pl, const float *o, const float *d, int64_t n,
-                   float tn, float tf, int32_t *hit, float *t, float *nrm, int64_t *prim) {
-  const int64_t blocks = (n + kBlock - 1) / kBlock;
-  rays_kernel<S, MAXD><<<(unsigned)blocks, kBlock>>>(sc, pl, o, d, n, tn, tf, hit, t, nrm, prim);
-}
-
-template <class S, int MAXD>
-void launch_trace_t(const S &sc, const PlaneDev &pl, const rt_ray_batch &b, int mode, hipStream_t stream) {
-  const unsigned blocks = (unsigned)((b.n + kRBlock - 1) / kRBlock);
-  switch (mode) {
-    case kRaysAny: trace_rays_kernel<S, MAXD, kRaysAny><<<blocks, kRBlock, 0, stream>>>(sc, pl, b); break;
-    case kRaysClosest: trace_rays_kernel<S, MAXD, kRaysClosest><<<blocks, kRBlock, 0, stream>>>(sc, pl, b); break;
-    default: trace_rays_kernel<S, MAXD, kRaysNormal><<<blocks, kRBlock, 0, stream>>>(sc, pl, b); break;
-  }
-}
-
-// the scene-kind / grid-mode / stack-slot dispatch of rt_intersect_rays
-int launch_trace(rt_scene *s, const rt_ray_batch &b, int mode, hipStream_t stream) {
-  if (s->kind == RT_SCENE_MESH) {
-    const MeshDev md = mesh_dev(s);
-    switch (s->maxd) {
-      case 4: launch_trace_t<MeshS, 4>(MeshS{md}, s->plane, b, mode, stream); break;
-      case 7: launch_trace_t<MeshS, 7>(MeshS{md}, s->plane, b, mode, stream); break;
-      case 15: launch_trace_t<MeshS, 15>(MeshS{md}, s->plane, b, mode, stream); break;
-      default: launch_trace_t<MeshS, 31>(MeshS{md}, s->plane, b, mode, stream); break;
-    }
-  } else if (s->kind == RT_SCENE_GRID) {
-    const GridDev gd = grid_dev(s);
-    switch (grid_mode(s, gd)) {
-      case kGridBuf | kGridBricked:
-        launch_trace_t<GridS<kGridBuf | kGridBricked>, 1>({gd}, s->plane, b, mode, stream);
-        break;
-      case kGridBricked: launch_trace_t<GridS<kGridBricked>, 1>({gd}, s->plane, b, mode, stream); break;
-      default: launch_trace_t<GridS<kGridBuf>, 1>({gd}, s->plane, b, mode, stream); break;
-    }
-  } else if (s->kind == RT_SCENE_OCTREE) {
-    const OctDev od{s->d_child, s->d_ovals};
-    switch (s->maxd) {
-      case 4: launch_trace_t<OctS<true>, 4>(OctS<true>{od}, s->plane, b, mode, stream); break;
-      case 7: launch_trace_t<OctS<true>, 7>(OctS<true>{od}, s->plane, b, mode, stream); break;
-      case 15: launch_trace_t<OctS<false>, 15>(OctS<false>{od}, s->plane, b, mode, stream); break;
-      default: launch_trace_t<OctS<false>, 31>(OctS<false>{od}, s->plane, b, mode, stream); break;
-    }
-  } else if (s->kind == RT_SCENE_INSTANCED) {
-    // a bottom-level scene refitted since its table entry was written: the
-    // entry is rewritten in stream order ahead of the trace, no host wait
-    for (size_t j = 0; j < s->blas.size(); ++j) {
-      if (s->blas[j]->version == s->blas_seen[j]) continue;
-      if (int rc = rti::blas_entry_launch(s->d_blas + j, mesh_dev(s->blas[j]), stream)) return rc;
-      s->blas_seen[j] = s->blas[j]->version;
-    }
-    return rti::trace_instances_launch(rti::InstArgs{s->d_inst, s->d_blas, s->ninst, s->maxd}, s->plane, b, mode,
-                                       stream);
-  } else {
-    return set_err(RT_E_STATE, "scene has no geometry");
-  }
-  HIP_TRY(hipGetLastError());
-  return RT_OK;
-}
-
-// the entries that render frames or copy a scene take no instanced scene
-int no_instanced(const rt_scene *s, const char *who) {
-  if (s && s->kind == RT_SCENE_INSTANCED)
-    return set_err(RT_E_STATE, std::string(who) + ": not available for an instanced scene");
-  return RT_OK;
-}
-
-}  // namespace
-
-namespace {
-// BVH8 builder selection (rt_set_bvh_builder): both builders give the same tree
-int g_bvh_mode = RT_BVH_AUTO;
-constexpr int64_t kBvhDeviceMinTris = 32768;  // auto: the device builder from this many triangles
-
-// which builder produced this thread's last tree (rtx_bvh_last_builder):
-// 1 host, 2 device, 3 host after a failed device build (AUTO)
-thread_local int t_bvh_last = 0;
-
-int build_bvh(const float *vpos4, int64_t nverts, const uint32_t *idx, int64_t nidx, rth::BVHGpu &b,
-              unsigned want) {
-  std::string err;
-  int ndev = 0;
-  const bool dev = g_bvh_mode == RT_BVH_DEVICE ||
-                   (g_bvh_mode == RT_BVH_AUTO && nidx / 3 >= kBvhDeviceMinTris &&
-                    hipGetDeviceCount(&ndev) == hipSuccess && ndev > 0);
-  bool fell_back = false;
-  if (dev) {
-    if (rth::build_bvh8_gpu(vpos4, nverts, idx, nidx, b, err, want)) {
-      t_bvh_last = 2;
-      return RT_OK;
-    }
-    if (err.rfind("GPU BVH builder bound", 0) == 0) return set_err(RT_E_DEVICE, err);
-    const bool device_failure = err.rfind("GPU BVH build:", 0) == 0;
-    if (!device_failure) return set_err(RT_E_INVALID, err);
-    if (g_bvh_mode == RT_BVH_DEVICE) return set_err(RT_E_DEVICE, err);
-    // AUTO: the host builder gives the identical tree, unless
-    // the device is left in a sticky fault state: then every later call on it
-    // fails too, so the failure is reported here instead of at the upload
-    if (const hipError_t e = hipDeviceSynchronize(); e != hipSuccess)
-      return set_err(RT_E_DEVICE, err + "; device unusable afterwards: " + hipGetErrorString(e));
-    (void)hipGetLastError();  // the builder's failure was reported above: clear it
-    std::fprintf(stderr, "rtamd: %s; building the BVH on the host instead\n", err.c_str());
-    fell_back = true;
-    err.clear();
-  }
-  if (!rth::build_bvh8(vpos4, nverts, idx, nidx, b, err, want)) return set_err(RT_E_INVALID, err);
-  t_bvh_last = fell_back ? 3 : 1;
-  return RT_OK;
-}
-
-int new_scene(rt_scene **out) {
-  if (!out) return set_err(RT_E_INVALID, "out is NULL");
-  int dev = 0;
-  HIP_TRY(hipGetDevice(&dev));
-  rt_scene *s = new rt_scene();
-  s->device = dev;
-  s->plane.on = 0;
-  s->plane.n = f3{0.0f, 1.0f, 0.0f};
-  *out = s;
-  return RT_OK;
-}
-
-// upload + `pad` zeroed trailing elements (kernels may read past the end).
-template <class T>
-int upload_padded(T **dst, const T *src, size_t n, size_t pad, int64_t &bytes) {
-  HIP_TRY(hipMalloc(dst, (n + pad) * sizeof(T)));
-  HIP_TRY(hipMemset(*dst, 0, (n + pad) * sizeof(T)));
-  if (n) HIP_TRY(rtdma::h2d(*dst, src, n * sizeof(T), nullptr));
-  bytes += (int64_t)((n + pad) * sizeof(T));
-  return RT_OK;
-}
-
-template <class T>
-int upload(T **dst, const T *src, size_t n, int64_t &bytes) {
-  if (n == 0) n = 1;  // keep a valid pointer
-  HIP_TRY(hipMalloc(dst, n * sizeof(T)));
-  if (src) HIP_TRY(rtdma::h2d(*dst, src, n * sizeof(T), nullptr));
-  bytes += (int64_t)(n * sizeof(T));
-  return RT_OK;
-}
-
-// the pinned host words a dynamic mesh's update reads its constants into
-int dynamic_host_words(rt_scene *s) {
-  HIP_TRY(hipHostMalloc((void **)&s->h_refit, 64 * sizeof(uint32_t), hipHostMallocDefault));
-  return RT_OK;
-}
-
-}  // namespace
+}  // namespace rti
 
 extern "C" {
-
-int rt_set_bvh_builder(int mode) {
-  if (mode < RT_BVH_AUTO || mode > RT_BVH_DEVICE) return set_err(RT_E_INVALID, "bad BVH builder mode");
-  g_bvh_mode = mode;
-  return RT_OK;
-}
-
-int rt_bvh_export(const float *vpos4, int64_t nverts, const uint32_t *idx, int64_t nidx,
-                  uint32_t *canon, int64_t *nnodes, uint32_t *perm_tri, int32_t *max_depth) {
-  if (!vpos4 || !idx || !nnodes || nverts <= 0 || nidx <= 0) return set_err(RT_E_INVALID, "bad mesh");
-  rth::BVHGpu b;
-  const unsigned want = (canon ? rth::kBvhCanon : 0u) | (perm_tri ? rth::kBvhPerm : 0u);
-  if (int rc = build_bvh(vpos4, nverts, idx, nidx, b, want)) return rc;
-  const int64_t n = canon ? (int64_t)b.canon.size() / 52 : b.host_nodes;
-  if (canon) {
-    if (*nnodes < n) return set_err(RT_E_INVALID, "buffer too small");
-    std::memcpy(canon, b.canon.data(), b.canon.size() * 4);
-  }
-  if (perm_tri) std::memcpy(perm_tri, b.perm_tri.data(), b.perm_tri.size() * 4);
-  if (max_depth) *max_depth = b.max_depth;
-  *nnodes = n;
-  return RT_OK;
-}
-
-// max over triangle slots of |e1| |e2| (float bits: the values are >= 0, so
-// their bit patterns order like them; NaN counts as +inf)
-__global__ void tri_edge_bound_kernel(const rtl::GTri *__restrict__ tris, uint32_t n, uint32_t *out) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  float m = 0.0f;
-  if (i < n) {
-    const float4 *q = reinterpret_cast<const float4 *>(tris + i);
-    const float4 b = q[1], c = q[2];
-    const float v = __builtin_sqrtf(b.x * b.x + b.y * b.y + b.z * b.z) *
-                    __builtin_sqrtf(c.x * c.x + c.y * c.y + c.z * c.z);
-    m = __builtin_isnan(v) ? kInf : v;
-  }
-  for (int off = 32; off > 0; off >>= 1) m = __builtin_fmaxf(m, __shfl_xor(m, off, 64));
-  if ((threadIdx.x & 63) == 0 && m > 0.0f) atomicMax(out, __float_as_uint(m));
-}
-
-// MeshDev::dmax2 of a mesh scene: (2^124 / (2 M))^2, M = max |e1| |e2| over its
-// triangles. A ray with dot(d, d) <= dmax2 has |d| <= 2^124 / (2 M) (up to a
-// few ulps), and tri_t's float det = e1 . (d x e2) is at most sqrt(2) |e1|
-// |e2| |d| (1 + 2^-24)^5 < 1.5 M |d| <= 0.75 x 2^124 in magnitude: inside the
-// range where rtm::rcp_rn is the division. M = 0 (no triangle with both edges)
-// leaves every direction; M = inf or NaN leaves none.
-float dmax2_of(uint32_t edge_bits) {
-  float M;
-  std::memcpy(&M, &edge_bits, 4);
-  if (M == 0.0f) return std::numeric_limits<float>::max();
-  if (!std::isfinite(M)) return 0.0f;
-  const double r = std::ldexp(1.0, 124) / (2.0 * (double)M * (1.0 + 1e-6));
-  const double r2 = r * r;
-  return r2 >= (double)std::numeric_limits<float>::max() ? std::numeric_limits<float>::max()
-                                                          : std::nextafter((float)r2, 0.0f);
-}
-int mesh_dmax2(rt_scene *s, uint32_t n_tris) {
-  s->dmax2 = 0.0f;
-  if (n_tris == 0) return RT_OK;
-  uint32_t *d = nullptr, h = 0;
-  HIP_TRY(hipMalloc(&d, 4));
-  hipError_t e = hipMemset(d, 0, 4);
-  if (e == hipSuccess) {
-    tri_edge_bound_kernel<<<(n_tris + 255) / 256, 256>>>(s->d_tris, n_tris, d);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipMemcpy(&h, d, 4, hipMemcpyDeviceToHost);
-  HIP_NOTE(hipFree(d));
-  if (e != hipSuccess) return set_err(RT_E_DEVICE, std::string("triangle edge bound: ") + hipGetErrorString(e));
-  s->dmax2 = dmax2_of(h);
-  return RT_OK;
-}
-
-int rt_scene_create_mesh(const float *vpos4, int64_t nverts, const uint32_t *idx, int64_t nidx,
-                         rt_scene **out) {
-  return rt_scene_create_mesh_ex(vpos4, nverts, idx, nidx, 0u, out);
-}
-
-int rt_scene_create_mesh_ex(const float *vpos4, int64_t nverts, const uint32_t *idx, int64_t nidx,
-                            uint32_t flags, rt_scene **out) {
-  if (!vpos4 || !idx || nverts <= 0 || nidx <= 0) return set_err(RT_E_INVALID, "empty mesh");
-  if (flags & ~RT_MESH_DYNAMIC) return set_err(RT_E_INVALID, "rt_scene_create_mesh_ex: unknown flags");
-  rth::BVHGpu b;
-  if (int rc = build_bvh(vpos4, nverts, idx, nidx, b, rth::kBvhTris | rth::kBvhDeviceTris)) return rc;
-  int32_t maxd = 8;
-  int rc = pick_maxd(b.max_depth, maxd);
-  if (rc) return rc;
-  rt_scene *s;
-  if ((rc = new_scene(&s))) return rc;
-  s->kind = RT_SCENE_MESH;
-  s->maxd = maxd;
-  s->root = b.root_word;
-  std::memcpy(s->root_box, b.root_box, sizeof(s->root_box));
-  if (!(b.root_word & rtl::kLeafBit) && b.root_word < b.nodes.size())
-    std::memcpy(s->root_child, b.nodes[b.root_word].box, sizeof(s->root_child));
-  s->host_nodes = b.host_nodes;
-  s->host_inner = b.host_inner;
-  s->bvh_depth = b.max_depth;
-  s->n_inner = (uint32_t)b.nodes.size();
-  if (b.dev_tris.p) {  // the device builder left the triangles on the device (with the zero pad)
-    s->dev_bytes += (int64_t)b.dev_tris.bytes;
-    s->d_tris = static_cast<rtl::GTri *>(b.dev_tris.take());
-  }
-  if ((rc = upload(&s->d_nodes, b.nodes.data(), b.nodes.size(), s->dev_bytes)) ||
-      (!s->d_tris && (rc = upload_padded(&s->d_tris, b.tris.data(), b.tris.size(), 8, s->dev_bytes))) ||
-      (rc = mesh_dmax2(s, b.n_tris))) {
-    rt_scene_destroy(s);
-    return rc;
-  }
-  s->n_tris = b.n_tris;
-  if (!b.nodes.empty())
-    for (uint32_t w : b.nodes[0].child) s->root_nchild += w != rtl::kInvalidChild;
-  if (flags & RT_MESH_DYNAMIC) {
-    const int64_t before = s->dev_bytes;
-    s->nverts = nverts;
-    s->level_first = rth::bvh_level_first(b.nodes);
-    if ((rc = upload(&s->d_idx, idx, (size_t)nidx, s->dev_bytes)) ||
-        (rc = upload(&s->d_vstage, (const float *)nullptr, 4 * (size_t)nverts, s->dev_bytes)) ||
-        (rc = upload(&s->d_edge, (const uint32_t *)nullptr, 1, s->dev_bytes)) || (rc = dynamic_host_words(s))) {
-      rt_scene_destroy(s);
-      return rc;
-    }
-    s->dyn_bytes = s->dev_bytes - before;
-    s->dynamic = true;
-  }
-  *out = s;
-  return RT_OK;
-}
-
-// The refit behind both update entries: d_vpos4 (device, on the scene's
-// device) is read in stream order on `stream`; returns after the constants
-// are back on the host.
-static int update_vertices_device(rt_scene *s, const float *d_vpos4, hipStream_t st) {
-  const rti::RefitArgs a{s->d_nodes, s->d_tris, s->root, d_vpos4, s->d_idx, s->level_first.data(),
-                         s->level_first.empty() ? 0 : (int32_t)s->level_first.size() - 1};
-  if (int rc = rti::refit_launch(a, st)) return rc;
-  // the constants the host keeps: the triangles' edge bound (dmax2) and, for
-  // an inner root, its eight child boxes (root_child, root_box)
-  const bool inner = a.levels > 0;
-  HIP_TRY(hipMemsetAsync(s->d_edge, 0, 4, st));
-  if (s->n_tris) {
-    tri_edge_bound_kernel<<<(s->n_tris + 255) / 256, 256, 0, st>>>(s->d_tris, s->n_tris, s->d_edge);
-    HIP_TRY(hipGetLastError());
-  }
-  if (inner) HIP_TRY(hipMemcpyAsync(s->h_refit, s->d_nodes[0].box, 192, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(s->h_refit + 48, s->d_edge, 4, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  if (inner) {
-    std::memcpy(s->root_child, s->h_refit, 192);
-    const float inf = std::numeric_limits<float>::infinity();
-    float mn[3] = {inf, inf, inf}, mx[3] = {-inf, -inf, -inf};
-    for (uint32_t c = 0; c < s->root_nchild; ++c) {  // bvh_layout's root box: the union over c = 0 .. nchild-1
-      for (int k = 0; k < 3; ++k) {
-        mn[k] = std::min(mn[k], s->root_child[6 * c + 2 * k]);
-        mx[k] = std::max(mx[k], s->root_child[6 * c + 2 * k + 1]);
-      }
-    }
-    for (int k = 0; k < 3; ++k) { s->root_box[k] = mn[k]; s->root_box[3 + k] = mx[k]; }
-  }
-  s->dmax2 = s->n_tris ? dmax2_of(s->h_refit[48]) : 0.0f;
-  ++s->version;
-  return RT_OK;
-}
-
-int rt_scene_create_grid(const uint32_t size[3], const float *values, rt_scene **out) {
-  if (!size || !values) return set_err(RT_E_INVALID, "NULL argument");
-  const uint64_t n = (uint64_t)size[0] * size[1] * size[2];
-  if (size[0] < 1 || size[1] < 1 || size[2] < 1 || n > (1ull << 32))
-    return set_err(RT_E_INVALID, "bad grid size");
-  rt_scene *s;
-  int rc = new_scene(&s);
-  if (rc) return rc;
-  s->kind = RT_SCENE_GRID;
-  s->size[0] = size[0]; s->size[1] = size[1]; s->size[2] = size[2];
-  if ((uint64_t)n * 4 <= kGridLinearMaxBytes && !(g_grid_force & 1)) {  // fits one XCD's L2: the reference layout
-    if ((rc = upload(&s->d_vals, values, (size_t)n, s->dev_bytes))) {
-      rt_scene_destroy(s);
-      return rc;
-    }
-    *out = s;
-    return RT_OK;
-  }
-  const uint64_t nb = grid_bricked_samples(size);
-  if (nb >= (1ull << 32)) {
-    rt_scene_destroy(s);
-    return set_err(RT_E_INVALID, "bad grid size");
-  }
-  s->grid_bricked = true;
-  float *d_ref = nullptr;  // the reference array, staged for the device-side bricking
-  if ((rc = upload(&d_ref, values, (size_t)n, s->dev_bytes)) ||
-      (rc = upload(&s->d_vals, (const float *)nullptr, (size_t)nb, s->dev_bytes))) {
-    if (d_ref) HIP_NOTE(hipFree(d_ref));
-    rt_scene_destroy(s);
-    return rc;
-  }
-  s->dev_bytes -= (int64_t)(n * sizeof(float));
-  brick_kernel<<<(unsigned)((nb + 255) / 256), 256>>>(d_ref, s->d_vals, size[0], size[1], size[2], nb);
-  const hipError_t e1 = hipGetLastError(), e2 = hipDeviceSynchronize(), e3 = hipFree(d_ref);
-  if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess) {
-    rt_scene_destroy(s);
-    return set_err(RT_E_DEVICE, std::string("grid bricking: ") +
-                                    hipGetErrorString(e1 != hipSuccess ? e1 : e2 != hipSuccess ? e2 : e3));
-  }
-  *out = s;
-  return RT_OK;
-}
-
-int rt_scene_create_octree(const void *nodes36, int64_t count, rt_scene **out) {
-  if (!nodes36 || count <= 0) return set_err(RT_E_INVALID, "empty octree");
-  rth::OctGpu g;
-  std::string err;
-  if (!rth::flatten_octree((const uint8_t *)nodes36, count, g, err)) return set_err(RT_E_INVALID, err);
-  int32_t maxd = 8;
-  int rc = pick_maxd(g.max_depth, maxd);
-  if (rc) return rc;
-  rt_scene *s;
-  if ((rc = new_scene(&s))) return rc;
-  s->kind = RT_SCENE_OCTREE;
-  s->maxd = maxd;
-  s->oct_depth = g.max_depth;
-  if ((rc = upload(&s->d_child, g.child.data(), g.child.size(), s->dev_bytes)) ||
-      (rc = upload(&s->d_ovals, g.vals.data(), g.vals.size(), s->dev_bytes))) {
-    rt_scene_destroy(s);
-    return rc;
-  }
-  *out = s;
-  return RT_OK;
-}
-
-int rt_scene_replicate(const rt_scene *src, int device, rt_scene **out) {
-  if (!src || !out) return set_err(RT_E_INVALID, "bad arguments");
-  if (int rc = no_instanced(src, "rt_scene_replicate")) return rc;
-  *out = nullptr;
-  int ndev = 0;
-  HIP_TRY(hipGetDeviceCount(&ndev));
-  if (device < 0 || device >= ndev) return set_err(RT_E_INVALID, "rt_scene_replicate: no such device");
-  int prev = 0;
-  HIP_TRY(hipGetDevice(&prev));
-  HIP_TRY(hipSetDevice(device));
-  rt_scene *s = new rt_scene();
-  // the scene's description (kind, tree shape, plane, kernel instantiation)
-  s->kind = src->kind;
-  s->device = device;
-  s->maxd = src->maxd;
-  s->root = src->root;
-  std::memcpy(s->root_box, src->root_box, sizeof s->root_box);
-  std::memcpy(s->root_child, src->root_child, sizeof s->root_child);
-  s->host_nodes = src->host_nodes;
-  s->host_inner = src->host_inner;
-  s->n_inner = src->n_inner;
-  s->dmax2 = src->dmax2;
-  s->bvh_depth = src->bvh_depth;
-  std::memcpy(s->size, src->size, sizeof s->size);
-  s->grid_bricked = src->grid_bricked;
-  s->oct_depth = src->oct_depth;
-  s->plane = src->plane;
-  s->n_tris = src->n_tris;
-  s->root_nchild = src->root_nchild;
-  s->version = src->version;
-  s->dev_bytes = src->dev_bytes - src->dyn_bytes;  // (a plain snapshot: not dynamic)
-  s->sched_on = src->sched_on;
-  s->coop = src->coop;
-  s->pump_on = src->pump_on;
-  // the device arrays, copied device to device (over xGMI between GPUs)
-  void *const from[] = {src->d_nodes, src->d_tris, src->d_vals, src->d_child, src->d_ovals};
-  void **to[] = {(void **)&s->d_nodes, (void **)&s->d_tris, (void **)&s->d_vals, (void **)&s->d_child,
-                 (void **)&s->d_ovals};
-  hipError_t e = hipSuccess;
-  const char *step = "";
-  for (int i = 0; i < 5 && e == hipSuccess; ++i) {
-    if (!from[i]) continue;
-    size_t bytes = 0;
-    if ((e = hipMemPtrGetInfo(from[i], &bytes)) != hipSuccess) { step = "hipMemPtrGetInfo"; break; }
-    if ((e = hipMalloc(to[i], bytes)) != hipSuccess) { step = "hipMalloc"; break; }
-    if ((e = hipMemcpyPeer(*to[i], device, from[i], src->device, bytes)) != hipSuccess) step = "hipMemcpyPeer";
-  }
-  HIP_NOTE(hipSetDevice(prev));
-  if (e != hipSuccess) {
-    rt_scene_destroy(s);
-    return set_err(RT_E_DEVICE, std::string("rt_scene_replicate: ") + step + ": " + hipGetErrorString(e));
-  }
-  *out = s;
-  return RT_OK;
-}
-
-int rt_scene_device(const rt_scene *s) { return s ? s->device : RT_E_INVALID; }
-
-static int check_update(const rt_scene *s, const float *vpos4, int64_t nverts, const char *who) {
-  if (!s) return set_err(RT_E_INVALID, std::string(who) + ": scene is NULL");
-  if (!vpos4) return set_err(RT_E_INVALID, std::string(who) + ": vertex pointer is NULL");
-  if (nverts <= 0) return set_err(RT_E_INVALID, std::string(who) + ": nverts must be positive");
-  if (s->kind != RT_SCENE_MESH) return set_err(RT_E_STATE, std::string(who) + ": not a mesh scene");
-  if (!s->dynamic)
-    return set_err(RT_E_STATE, std::string(who) + ": the mesh was not created with RT_MESH_DYNAMIC");
-  if (nverts != s->nverts)
-    return set_err(RT_E_INVALID, std::string(who) + ": nverts is " + std::to_string(nverts) + ", the mesh was created with " +
-                                     std::to_string(s->nverts));
-  return RT_OK;
-}
-
-// ---- instanced scenes (include/rtamd.h; kernels in rt_instances.hip) -------
-namespace {
-// one rt_instance -> its device record; `who` names the entry in the message
-int instance_record(const rt_instance &in, int32_t nblas, int64_t index, const char *who, rti::InstRec &r) {
-  const std::string at = std::string(who) + ": instance " + std::to_string(index);
-  if (in.blas < 0 || in.blas >= nblas) return set_err(RT_E_INVALID, at + ": blas index out of range");
-  if (in.flags & ~RT_INSTANCE_DISABLED) return set_err(RT_E_INVALID, at + ": unknown flag bits");
-  if (!rti::affine_inverse(in.xform, r.m))
-    return set_err(RT_E_INVALID, at + ": the matrix is singular or has a non-finite entry");
-  r.blas = in.blas;
-  r.flags = in.flags;
-  r.skipped = 0;
-  r.pad = 0;
-  return RT_OK;
-}
-
-int instance_range(const rt_scene *s, int32_t first, int32_t count, const char *who) {
-  if (!s) return set_err(RT_E_INVALID, std::string(who) + ": scene is NULL");
-  if (s->kind != RT_SCENE_INSTANCED) return set_err(RT_E_STATE, std::string(who) + ": not an instanced scene");
-  if (first < 0 || count < 0 || (int64_t)first + count > s->ninst)
-    return set_err(RT_E_INVALID, std::string(who) + ": range outside the scene's " + std::to_string(s->ninst) +
-                                     " instances");
-  return RT_OK;
-}
-}  // namespace
-
-int rt_scene_create_instanced(rt_scene *const *blas, int32_t nblas, const rt_instance *inst, int32_t ninst,
-                              rt_scene **out) {
-  const char *who = "rt_scene_create_instanced";
-  if (!blas || !inst || !out) return set_err(RT_E_INVALID, std::string(who) + ": NULL argument");
-  *out = nullptr;
-  if (nblas < 1 || ninst < 1) return set_err(RT_E_INVALID, std::string(who) + ": nblas and ninst must be at least 1");
-  int dev = 0;
-  HIP_TRY(hipGetDevice(&dev));
-  int32_t maxd = 1;
-  for (int32_t j = 0; j < nblas; ++j) {
-    if (!blas[j]) return set_err(RT_E_INVALID, std::string(who) + ": BLAS " + std::to_string(j) + " is NULL");
-    if (blas[j]->kind != RT_SCENE_MESH)
-      return set_err(RT_E_STATE, std::string(who) + ": BLAS " + std::to_string(j) + " is not a mesh scene");
-    if (blas[j]->device != dev)
-      return set_err(RT_E_INVALID, std::string(who) + ": BLAS " + std::to_string(j) + " lives on device " +
-                                       std::to_string(blas[j]->device) + ", the current device is " + std::to_string(dev));
-    maxd = std::max(maxd, blas[j]->maxd);
-  }
-  std::vector<rti::InstRec> recs((size_t)ninst);
-  for (int32_t i = 0; i < ninst; ++i)
-    if (int rc = instance_record(inst[i], nblas, i, who, recs[(size_t)i])) return rc;
-  std::vector<MeshDev> tab;
-  for (int32_t j = 0; j < nblas; ++j) tab.push_back(mesh_dev(blas[j]));
-  rt_scene *s = nullptr;
-  if (int rc = new_scene(&s)) return rc;
-  s->kind = RT_SCENE_INSTANCED;
-  s->maxd = maxd;  // the LDS stack of the deepest bottom-level tree
-  s->ninst = ninst;
-  s->blas.assign(blas, blas + nblas);
-  for (int32_t j = 0; j < nblas; ++j) s->blas_seen.push_back(blas[j]->version);
-  int rc = upload(&s->d_inst, recs.data(), recs.size(), s->dev_bytes);
-  if (!rc) rc = upload(&s->d_blas, tab.data(), tab.size(), s->dev_bytes);
-  if (rc) {
-    rt_scene_destroy(s);
-    return rc;
-  }
-  *out = s;
-  return RT_OK;
-}
-
-int rt_scene_update_instances(rt_scene *s, int32_t first, int32_t count, const rt_instance *inst) {
-  const char *who = "rt_scene_update_instances";
-  if (int rc = instance_range(s, first, count, who)) return rc;
-  if (!inst) return set_err(RT_E_INVALID, std::string(who) + ": instance pointer is NULL");
-  if (count == 0) return RT_OK;
-  std::vector<rti::InstRec> recs((size_t)count);
-  for (int32_t i = 0; i < count; ++i)
-    if (int rc = instance_record(inst[i], (int32_t)s->blas.size(), (int64_t)first + i, who, recs[(size_t)i])) return rc;
-  int prev = 0;
-  HIP_TRY(hipGetDevice(&prev));
-  HIP_TRY(hipSetDevice(s->device));
-  const hipError_t e = rtdma::h2d(s->d_inst + first, recs.data(), recs.size() * sizeof(rti::InstRec), nullptr);
-  HIP_NOTE(hipSetDevice(prev));
-  if (e != hipSuccess) return set_err(RT_E_DEVICE, rterr::hip_fail("rt_scene_update_instances: upload", e));
-  return RT_OK;
-}
-
-int rt_scene_update_instances_device(rt_scene *s, int32_t first, int32_t count, const float *d_xform12,
-                                     void *stream) {
-  const char *who = "rt_scene_update_instances_device";
-  if (int rc = instance_range(s, first, count, who)) return rc;
-  if (!d_xform12) return set_err(RT_E_INVALID, std::string(who) + ": matrix pointer is NULL");
-  if (count == 0) return RT_OK;
-  return rti::pose_launch(s->d_inst, first, count, d_xform12, (hipStream_t)stream);
-}
-
-int rt_scene_get_instances(const rt_scene *s, int32_t first, int32_t count, rt_instance *inst, float *inv12,
-                           uint32_t *skipped) {
-  if (int rc = instance_range(s, first, count, "rt_scene_get_instances")) return rc;
-  if (count == 0) return RT_OK;
-  std::vector<rti::InstRec> recs((size_t)count);
-  int prev = 0;
-  HIP_TRY(hipGetDevice(&prev));
-  HIP_TRY(hipSetDevice(s->device));
-  hipError_t e = hipDeviceSynchronize();  // pose updates queued on any stream
-  if (e == hipSuccess) e = rtdma::d2h(recs.data(), s->d_inst + first, recs.size() * sizeof(rti::InstRec), nullptr);
-  HIP_NOTE(hipSetDevice(prev));
-  if (e != hipSuccess) return set_err(RT_E_DEVICE, rterr::hip_fail("rt_scene_get_instances", e));
-  for (int32_t i = 0; i < count; ++i) {
-    const rti::InstRec &r = recs[(size_t)i];
-    if (inst) {
-      inst[i].blas = r.blas;
-      inst[i].flags = r.flags;
-      for (float &x : inst[i].xform) x = 0.0f;
-      if (!r.skipped) (void)rti::affine_inverse(r.m, inst[i].xform);
-    }
-    if (inv12) std::memcpy(inv12 + 12 * (size_t)i, r.m, sizeof r.m);
-    if (skipped) skipped[i] = r.skipped;
-  }
-  return RT_OK;
-}
-
-int rt_scene_update_vertices_device(rt_scene *s, const float *d_vpos4, int64_t nverts, void *stream) {
-  if (int rc = check_update(s, d_vpos4, nverts, "rt_scene_update_vertices_device")) return rc;
-  return update_vertices_device(s, d_vpos4, (hipStream_t)stream);
-}
-
-int rt_scene_update_vertices(rt_scene *s, const float *vpos4, int64_t nverts) {
-  if (int rc = check_update(s, vpos4, nverts, "rt_scene_update_vertices")) return rc;
-  int prev = 0;
-  HIP_TRY(hipGetDevice(&prev));
-  HIP_TRY(hipSetDevice(s->device));
-  int rc = RT_OK;
-  if (const hipError_t e = rtdma::h2d(s->d_vstage, vpos4, 16 * (size_t)nverts, nullptr))
-    rc = set_err(RT_E_DEVICE, rterr::hip_fail("rt_scene_update_vertices: vertex upload", e));
-  if (!rc) rc = update_vertices_device(s, s->d_vstage, nullptr);
-  HIP_NOTE(hipSetDevice(prev));
-  return rc;
-}
-
-// Diagnostic (not part of include/rtamd.h): a mesh scene's device tree, as it
-// is now: n_inner GNode records (224 bytes each) and n_tris GTri records (48
-// bytes each). Two-call protocol: with nodes224 = tris48 = NULL only the counts
-// are returned; else *n_inner / *n_tris are the buffers' capacities.
-int rtx_scene_mesh_download(rt_scene *s, void *nodes224, int64_t *n_inner, void *tris48, int64_t *n_tris) {
-  if (!s || !n_inner || !n_tris) return set_err(RT_E_INVALID, "rtx_scene_mesh_download: NULL argument");
-  if (s->kind != RT_SCENE_MESH) return set_err(RT_E_STATE, "rtx_scene_mesh_download: not a mesh scene");
-  if (nodes224 || tris48) {
-    if (!nodes224 || !tris48 || *n_inner < (int64_t)s->n_inner || *n_tris < (int64_t)s->n_tris)
-      return set_err(RT_E_INVALID, "rtx_scene_mesh_download: buffers too small");
-    int prev = 0;
-    HIP_TRY(hipGetDevice(&prev));
-    HIP_TRY(hipSetDevice(s->device));
-    hipError_t e = hipDeviceSynchronize();
-    if (e == hipSuccess) e = rtdma::d2h(nodes224, s->d_nodes, (size_t)s->n_inner * sizeof(rtl::GNode), nullptr);
-    if (e == hipSuccess) e = rtdma::d2h(tris48, s->d_tris, (size_t)s->n_tris * sizeof(rtl::GTri), nullptr);
-    HIP_NOTE(hipSetDevice(prev));
-    if (e != hipSuccess) return set_err(RT_E_DEVICE, rterr::hip_fail("rtx_scene_mesh_download", e));
-  }
-  *n_inner = s->n_inner;
-  *n_tris = s->n_tris;
-  return RT_OK;
-}
-
-// Diagnostic (not part of include/rtamd.h): the constants the host keeps of a
-// mesh scene: root_box[6], the root's child boxes root_child[48], dmax2.
-int rtx_scene_mesh_constants(const rt_scene *s, float root_box[6], float root_child[48], float *dmax2) {
-  if (!s) return set_err(RT_E_INVALID, "rtx_scene_mesh_constants: scene is NULL");
-  if (s->kind != RT_SCENE_MESH) return set_err(RT_E_STATE, "rtx_scene_mesh_constants: not a mesh scene");
-  if (root_box) std::memcpy(root_box, s->root_box, sizeof s->root_box);
-  if (root_child) std::memcpy(root_child, s->root_child, sizeof s->root_child);
-  if (dmax2) *dmax2 = s->dmax2;
-  return RT_OK;
-}
-
-int rt_scene_get_plane(const rt_scene *s, int *enabled, float normal[3], float *offset) {
-  if (!s) return set_err(RT_E_INVALID, "scene is NULL");
-  if (enabled) *enabled = s->plane.on;
-  if (normal) { normal[0] = s->plane.n.x; normal[1] = s->plane.n.y; normal[2] = s->plane.n.z; }
-  if (offset) *offset = s->plane.off;
-  return RT_OK;
-}
-
-int rt_scene_set_plane(rt_scene *s, int enabled, const float normal[3], float offset) {
-  if (!s) return set_err(RT_E_INVALID, "scene is NULL");
-  PlaneDev &p = s->plane;
-  p.on = enabled ? 1 : 0;
-  if (!enabled) return RT_OK;
-  if (!normal) return set_err(RT_E_INVALID, "normal is NULL");
-  // Plane(normal, offset) + recalcBasis (raytracing.hpp:121-124, 169-179)
-  const float n[3] = {normal[0], normal[1], normal[2]};
-  const float a[3] = {std::fabs(n[0]), std::fabs(n[1]), std::fabs(n[2])};
-  float b1[3];
-  if (a[0] > a[1] && a[0] > a[2]) { b1[0] = n[1]; b1[1] = -n[0]; b1[2] = 0; }
-  else { b1[0] = 0; b1[1] = n[2]; b1[2] = -n[1]; }
-  auto nrm = [](float v[3]) {
-    const float l = std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
-    v[0] = v[0] / l; v[1] = v[1] / l; v[2] = v[2] / l;
-  };
-  nrm(b1);
-  float b2[3] = {b1[1] * n[2] - b1[2] * n[1], b1[2] * n[0] - b1[0] * n[2], b1[0] * n[1] - b1[1] * n[0]};
-  nrm(b2);
-  p.n = f3{n[0], n[1], n[2]};
-  p.off = offset;
-  p.b1 = f3{b1[0], b1[1], b1[2]};
-  p.b2 = f3{b2[0], b2[1], b2[2]};
-  return RT_OK;
-}
-
-int rt_scene_kind(const rt_scene *s) { return s ? s->kind : RT_E_INVALID; }
-int64_t rt_scene_device_bytes(const rt_scene *s) { return s ? s->dev_bytes : 0; }
-
-int rt_scene_bvh_stats(const rt_scene *s, int64_t *nodes, int64_t *inner, int32_t *max_depth) {
-  if (!s) return set_err(RT_E_INVALID, "scene is NULL");
-  if (s->kind != RT_SCENE_MESH && s->kind != RT_SCENE_OCTREE) return set_err(RT_E_STATE, "not a tree scene");
-  if (nodes) *nodes = s->host_nodes;
-  if (inner) *inner = s->host_inner;
-  if (max_depth) *max_depth = s->kind == RT_SCENE_MESH ? s->bvh_depth : s->oct_depth;
-  return RT_OK;
-}
-
-int rt_scene_destroy(rt_scene *s) {
-  if (!s) return RT_OK;
-  int prev = 0;
-  HIP_NOTE(hipGetDevice(&prev));
-  HIP_NOTE(hipSetDevice(s->device));
-  // the scene's own copy/render streams drain before anything they may still
-  // read or write is freed (rt_render returns only after both, but a failed
-  // call or a caller-stream launch may not have)
-  for (hipStream_t x : s->xs)
-    if (x) HIP_NOTE(hipStreamSynchronize(x));
-  if (s->sched_os) HIP_NOTE(hipStreamSynchronize(s->sched_os));
-  void *ptrs[] = {s->d_nodes, s->d_tris, s->d_vals, s->d_child, s->d_ovals, s->d_color, s->d_t,
-                  s->d_cost[0], s->d_order[0], s->d_cost[1], s->d_order[1], s->d_idx, s->d_vstage, s->d_edge, s->d_inst, s->d_blas};
-  for (void *p : ptrs)
-    if (p) HIP_NOTE(hipFree(p));
-  if (s->h_refit) HIP_NOTE(hipHostFree(s->h_refit));
-  for (hipEvent_t e : s->ord_ev)
-    if (e) HIP_NOTE(hipEventDestroy(e));
-  if (s->frame_ev) HIP_NOTE(hipEventDestroy(s->frame_ev));
-  if (s->sched_os) {
-    rterr::stream_remove(s->sched_os);
-    HIP_NOTE(hipStreamDestroy(s->sched_os));
-  }
-  if (s->ev0) HIP_NOTE(hipEventDestroy(s->ev0));
-  if (s->ev1) HIP_NOTE(hipEventDestroy(s->ev1));
-  if (s->ev_host) HIP_NOTE(hipEventDestroy(s->ev_host));
-  if (s->xev) HIP_NOTE(hipEventDestroy(s->xev));
-  if (s->d_hit_box) HIP_NOTE(hipFree(s->d_hit_box));
-  if (s->h_hit_box) HIP_NOTE(hipHostFree(s->h_hit_box));
-  if (s->d_row_span) HIP_NOTE(hipFree(s->d_row_span));
-  if (s->h_row_span) HIP_NOTE(hipHostFree(s->h_row_span));
-  s->stage.release();
-  for (hipStream_t x : s->xs)
-    if (x) {
-      rterr::stream_remove(x);
-      HIP_NOTE(hipStreamDestroy(x));
-    }
-  HIP_NOTE(hipSetDevice(prev));
-  delete s;
-  return RT_OK;
-}
 
 int rt_render_device(rt_scene *s, const rt_render_params *p, uint32_t *d_color, float *d_t, int32_t W,
                      int32_t H, uint32_t flags, const rt_tile *tile, void *stream) {
@@ -3170,372 +1772,6 @@ int rt_stream_release(void *stream) {
   }
   HIP_TRY(hipFreeAsync(p, (hipStream_t)stream));
   return RT_OK;
-}
-
-// rt_render's failure injection (rtx_render_inject_failure): the next n calls
-// fail after their uploads were issued; g_render_drains counts the returns that
-// waited for both copy streams (rtx_render_drain_count)
-std::atomic<int> g_render_fault{0};
-std::atomic<int64_t> g_render_drains{0};
-
-namespace {
-
-using rtdma::pinned_device_ptr;
-
-// RTAMD_DROPIN_ZC=0: rt_render's cleared frames take the device frame + boxed
-// download instead of the zero-copy path (A/B switch)
-bool dropin_zero_copy() {
-  static const bool on = !ab_off("RTAMD_DROPIN_ZC");
-  return on;
-}
-
-bool dropin_trace() {
-  static const bool on = ab_on("RTAMD_DROPIN_TRACE");
-  return on;
-}
-
-// The pageable drop-in's staging spans reset by the host threads that copy
-// them; RTAMD_HOST_CLEAR=0: by clear_spans_kernel instead (A/B switch).
-bool host_clears_stage() {
-  static const bool on = !ab_off("RTAMD_HOST_CLEAR");
-  return on;
-}
-
-// System-scope stores into host frames (kFlagHostFrame); RTAMD_HOST_STORES=agent
-// turns them off (A/B switch).
-bool host_sys_stores() {
-  static const bool on = [] {
-    const char *e = ab_env("RTAMD_HOST_STORES");
-    return !(e && std::strcmp(e, "agent") == 0);
-  }();
-  return on;
-}
-
-// rt_render of a cleared frame (RT_FLAG_CLEAR | RT_FLAG_HITS_ONLY: the app's
-// frameBuf.clear() + draw, src/main.cpp:197,203): only hit pixels differ from
-// the caller's buffers (raytracing.cpp:91-94), and the kernel stores exactly
-// those -- into HOST memory (zero-copy), so no download follows the kernel:
-//  * buffers pinned by rt_host_pin: the hits go straight into them;
-//  * pageable buffers: into the scene's pinned staging frame, which is kept
-//    cleared. The kernel records, per row, the span of the pixels it stored
-//    (kFlagRowSpan); box_out_kernel moves the spans to mapped host memory, the
-//    host copies just those spans to the caller's buffers (OpenMP rows) and
-//    resets them in the staging frame as it goes (RTAMD_HOST_CLEAR=0: the
-//    GPU does, clear_spans_kernel, in stream order before the next frame).
-int render_cleared_zero_copy(rt_scene *s, FrameArgs fa, uint32_t *color, float *t, int32_t W, int32_t H,
-                             float *ms) {
-  const size_t px = (size_t)W * H;
-  hipStream_t a = s->xs[0];
-  rterr::stream_mark(a, "rt_render (zero-copy cleared frame)");
-  // every return waits for stream a while it may still touch the caller's
-  // buffers; the span-word reset (below) is the library's own and
-  // is left running when the call returns
-  struct Drain {
-    hipStream_t a;
-    bool on = true;
-    ~Drain() {
-      if (on && hipStreamSynchronize(a) == hipSuccess) g_render_drains.fetch_add(1);
-    }
-  } drain{a};
-  void *dc = pinned_device_ptr(color, px * 4), *dt = pinned_device_ptr(t, px * 4);
-  fa.flags |= RT_FLAG_HITS_ONLY | (host_sys_stores() ? kFlagHostFrame : 0u);
-  fa.hit_box = nullptr;
-  if (dc && dt) {
-    fa.color = (uint32_t *)dc;
-    fa.t = (float *)dt;
-    if (g_render_fault.load() > 0) {
-      g_render_fault.fetch_sub(1);
-      return set_err(RT_E_DEVICE, "injected rt_render failure (rtx_render_inject_failure)");
-    }
-    HIP_TRY(hipEventRecord(s->ev0, a));
-    // (the frame's tile-order kernel runs on the schedule's side stream: not waited for)
-    if (int rc = launch_render(s, fa, a)) return rc;
-    HIP_TRY(hipEventRecord(s->ev1, a));
-    HIP_TRY(hipEventSynchronize(s->ev1));
-    drain.on = false;
-    if (ms) HIP_TRY(hipEventElapsedTime(ms, s->ev0, s->ev1));
-    return RT_OK;
-  }
-  if (int rc = ensure_stage(s, px)) return rc;
-  void *sc = nullptr, *st = nullptr;
-  HIP_TRY(hipHostGetDevicePointer(&sc, s->stage.c, 0));
-  HIP_TRY(hipHostGetDevicePointer(&st, s->stage.t, 0));
-  if (H > s->span_cap) {
-    HIP_TRY(hipStreamSynchronize(a));  // (the previous frame's span clear reads d_row_span)
-    if (s->d_row_span) HIP_NOTE(hipFree(s->d_row_span));
-    if (s->h_row_span) HIP_NOTE(hipHostFree(s->h_row_span));
-    s->d_row_span = s->h_row_span = s->h_row_span_dev = nullptr;
-    s->span_cap = 0;
-    HIP_TRY(hipMalloc(&s->d_row_span, (size_t)H * 2 * sizeof(int32_t)));
-    HIP_TRY(hipHostMalloc(&s->h_row_span, (size_t)H * 2 * sizeof(int32_t), hipHostMallocMapped));
-    HIP_TRY(hipHostGetDevicePointer((void **)&s->h_row_span_dev, s->h_row_span, 0));
-    s->span_cap = H;
-    s->stage.mark_dirty();  // (the spans of the frame in the staging frame are gone)
-  }
-  // (otherwise the previous frame's span reset left both the staging
-  // frame and the span words reset)
-  if (s->stage.clear_for(W, H)) {
-    s->stage.mark_dirty();  // (a failed reset of the span words leaves the next frame to redo both)
-    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)s->d_row_span, 0x7FFFFFFF, (size_t)H * 2, a));
-    s->stage.mark_clean();
-  }
-  fa.color = (uint32_t *)sc;
-  fa.t = (float *)st;
-  fa.hit_box = s->d_row_span;
-  fa.flags |= kFlagRowSpan;
-  if (g_render_fault.load() > 0) {
-    g_render_fault.fetch_sub(1);
-    return set_err(RT_E_DEVICE, "injected rt_render failure (rtx_render_inject_failure)");
-  }
-  const auto h0 = std::chrono::steady_clock::now();
-  HIP_TRY(hipEventRecord(s->ev0, a));
-  s->stage.mark_dirty();  // until its spans are cleared again below
-  if (int rc = launch_render(s, fa, a)) return rc;
-  HIP_TRY(hipEventRecord(s->ev1, a));
-  box_out_kernel<<<(unsigned)((2 * H + 255) / 256), 256, 0, a>>>(s->d_row_span, s->h_row_span_dev, 2 * H);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(s->ev_host, a));
-  const auto h1 = std::chrono::steady_clock::now();
-  HIP_TRY(hipEventSynchronize(s->ev_host));
-  const auto h2 = std::chrono::steady_clock::now();
-  if (ms) HIP_TRY(hipEventElapsedTime(ms, s->ev0, s->ev1));
-  // the stored spans to the caller (host threads; every other pixel of the
-  // caller's cleared frame already holds the staging frame's 0 / +inf); the
-  // host resets the same spans of the staging frame as it goes (the GPU only
-  // stores into it, from the next call on), and the span words are reset in
-  // stream order before the next frame's kernel; the call does not wait for that
-  const bool host_clear = host_clears_stage();
-  rth::copy_spans(color, t, s->stage.c, s->stage.t, W, H, s->h_row_span, 0, host_clear);
-  const auto h3 = std::chrono::steady_clock::now();
-  drain.on = false;
-  if (host_clear) {
-    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)s->d_row_span, 0x7FFFFFFF, (size_t)H * 2, a));
-  } else {
-    clear_spans_kernel<<<(unsigned)H, 256, 0, a>>>((uint32_t *)sc, (float *)st, s->d_row_span, W);
-    HIP_TRY(hipGetLastError());
-  }
-  s->stage.mark_clean();
-  if (dropin_trace()) {  // RTAMD_DROPIN_TRACE=1: host-side phases of this call (dev switch)
-    const auto h4 = std::chrono::steady_clock::now();
-    auto us = [](auto x, auto y) { return std::chrono::duration<double, std::micro>(y - x).count(); };
-    int64_t pxs = 0;
-    for (int32_t y = 0; y < H; ++y)
-      if (s->h_row_span[2 * y] <= -s->h_row_span[2 * y + 1]) pxs += -s->h_row_span[2 * y + 1] - s->h_row_span[2 * y] + 1;
-    std::fprintf(stderr, "dropin: issue %.1f, wait %.1f, copy %.1f (%lld px), clear issue %.1f us; kernel %.1f us\n",
-                 us(h0, h1), us(h1, h2), us(h2, h3), (long long)pxs, us(h3, h4), ms ? *ms * 1e3 : -1.0);
-  }
-  return RT_OK;
-}
-
-}  // namespace
-
-int rt_render(rt_scene *s, const rt_render_params *p, uint32_t *color, float *t, int32_t W, int32_t H,
-              uint32_t flags, float *ms) {
-  if (!s) return set_err(RT_E_INVALID, "scene is NULL");
-  int rc = no_instanced(s, "rt_render");
-  if (rc) return rc;
-  if ((rc = check_params(p, W, H))) return rc;
-  if (!color || !t) return set_err(RT_E_INVALID, "NULL framebuffer");
-  if (flags & RT_FLAG_TILE_NATURAL) return set_err(RT_E_INVALID, "rt_render renders whole frames (no tile)");
-  // every argument is checked before the first copy is queued
-  FrameArgs fa;
-  if ((rc = fill_frame(fa, s, p, nullptr, nullptr, W, H, flags & ~RT_FLAG_HITS_ONLY, nullptr))) return rc;
-  const size_t px = (size_t)W * H;
-  if (flags == (RT_FLAG_CLEAR | RT_FLAG_HITS_ONLY) && dropin_zero_copy()) {
-    if ((rc = ensure_events(s)) || (rc = ensure_copy_streams(s))) return rc;
-    return render_cleared_zero_copy(s, fa, color, t, W, H, ms);
-  }
-  if ((rc = ensure_fb(s, px)) || (rc = ensure_events(s)) || (rc = ensure_copy_streams(s))) return rc;
-  fa.color = s->d_color;
-  fa.t = s->d_t;
-  // The DMA engines only ever see pinned memory (rtdma):
-  // buffers pinned by rt_host_pin are copied directly; pageable ones go through
-  // the scene's staging frame, host threads copying between it and the caller's
-  // buffers on the host side of each DMA (hc / ht: where the DMAs read / write).
-  const bool direct = rtdma::pinned(color, px * 4) && rtdma::pinned(t, px * 4);
-  if (!direct && (rc = ensure_stage(s, px))) return rc;
-  uint32_t *hc = direct ? color : s->stage.c;
-  float *ht = direct ? t : s->stage.t;
-  // colour and t move on two streams (two DMA engines, concurrent). Once a copy
-  // is queued, every return -- an error included -- first waits for both
-  // streams, so the caller may unpin or free its buffers as soon as the call
-  // returns.
-  hipStream_t a = s->xs[0], b = s->xs[1];
-  rterr::stream_mark(a, "rt_render (render + colour copies)");
-  rterr::stream_mark(b, "rt_render (t copies)");
-  struct Drain {
-    hipStream_t a, b;
-    ~Drain() {
-      const hipError_t ea = hipStreamSynchronize(a), eb = hipStreamSynchronize(b);
-      if (ea == hipSuccess && eb == hipSuccess) g_render_drains.fetch_add(1);
-    }
-  } drain{a, b};
-  // Which pixels can differ from the caller's buffers after the frame:
-  //  * RT_FLAG_CLEAR: every pixel (misses become 0 / +inf), so all are copied back;
-  //  * RT_FLAG_CLEAR | RT_FLAG_HITS_ONLY: the caller's buffers already hold a
-  //    cleared frame (the app's frameBuf.clear() + draw, src/main.cpp:197,203),
-  //    so only stored hits differ (raytracing.cpp:91-94);
-  //  * no flag (tPrev frame): colour and t are written only on hit, so again
-  //    only stored hits differ.
-  // In the last two cases the kernel records the bounding box of its stored
-  // pixels and only that box is copied back. The device frame is always
-  // written whole (a cleared frame) or uploaded whole (tPrev), so the box
-  // holds exactly the caller's values outside the hits.
-  const bool boxed = !(flags & RT_FLAG_CLEAR) || (flags & RT_FLAG_HITS_ONLY);
-  if (!direct) s->stage.mark_dirty();  // (the zero-copy path's cleared staging frame is overwritten)
-  if (!(flags & RT_FLAG_CLEAR)) {
-    if (!direct) rth::copy_rect(hc, ht, color, t, W, 0, W - 1, 0, H - 1, 0);
-    HIP_TRY(hipMemcpyAsync(s->d_color, hc, px * 4, hipMemcpyHostToDevice, a));
-    HIP_TRY(hipMemcpyAsync(s->d_t, ht, px * 4, hipMemcpyHostToDevice, b));
-    HIP_TRY(hipEventRecord(s->xev, b));
-    HIP_TRY(hipStreamWaitEvent(a, s->xev, 0));
-  }
-  if (g_render_fault.load() > 0) {
-    g_render_fault.fetch_sub(1);
-    return set_err(RT_E_DEVICE, "injected rt_render failure (rtx_render_inject_failure)");
-  }
-  if (boxed) {
-    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)s->d_hit_box, 0x7FFFFFFF, 4, a));
-    fa.hit_box = s->d_hit_box;
-  }
-  HIP_TRY(hipEventRecord(s->ev0, a));
-  if ((rc = launch_render(s, fa, a))) return rc;
-  HIP_TRY(hipEventRecord(s->ev1, a));
-  int32_t x0 = 0, x1 = W - 1, y0 = 0, y1 = H - 1;  // the region copied back
-  if (!boxed) {
-    HIP_TRY(hipStreamWaitEvent(b, s->ev1, 0));
-    HIP_TRY(hipMemcpyAsync(ht, s->d_t, px * 4, hipMemcpyDeviceToHost, b));
-    HIP_TRY(hipMemcpyAsync(hc, s->d_color, px * 4, hipMemcpyDeviceToHost, a));
-  } else {
-    box_out_kernel<<<1, 64, 0, a>>>(s->d_hit_box, s->h_hit_box_dev, 4);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(a));
-    x0 = s->h_hit_box[0], x1 = -s->h_hit_box[1], y0 = s->h_hit_box[2], y1 = -s->h_hit_box[3];
-    if (x0 <= x1 && y0 <= y1) {  // else: no hit, nothing changed
-      HIP_TRY(hipStreamWaitEvent(b, s->ev1, 0));
-      const size_t off = (size_t)y0 * W + x0, rows = (size_t)(y1 - y0 + 1), w = (size_t)(x1 - x0 + 1);
-      if (w * 2 > (size_t)W) {  // wide box: whole rows, one contiguous copy per buffer
-        x0 = 0;
-        x1 = W - 1;
-        HIP_TRY(hipMemcpyAsync(ht + (size_t)y0 * W, s->d_t + (size_t)y0 * W, rows * W * 4, hipMemcpyDeviceToHost, b));
-        HIP_TRY(hipMemcpyAsync(hc + (size_t)y0 * W, s->d_color + (size_t)y0 * W, rows * W * 4,
-                               hipMemcpyDeviceToHost, a));
-      } else {
-        HIP_TRY(hipMemcpy2DAsync(ht + off, (size_t)W * 4, s->d_t + off, (size_t)W * 4, w * 4, rows,
-                                 hipMemcpyDeviceToHost, b));
-        HIP_TRY(hipMemcpy2DAsync(hc + off, (size_t)W * 4, s->d_color + off, (size_t)W * 4, w * 4, rows,
-                                 hipMemcpyDeviceToHost, a));
-      }
-    }
-  }
-  HIP_TRY(hipStreamSynchronize(a));
-  HIP_TRY(hipStreamSynchronize(b));
-  if (!direct && x0 <= x1 && y0 <= y1) rth::copy_rect(color, t, hc, ht, W, x0, x1, y0, y1, 0);
-  if (ms) HIP_TRY(hipEventElapsedTime(ms, s->ev0, s->ev1));
-  return RT_OK;
-}
-
-// test hooks: fail the next n rt_render calls after their uploads; how many
-// rt_render returns have waited for both copy streams
-int rtx_render_inject_failure(int32_t n) {
-  g_render_fault.store(n);
-  return RT_OK;
-}
-int64_t rtx_render_drain_count(void) { return g_render_drains.load(); }
-
-int rt_untile_device(const uint32_t *d_packed_color, const float *d_packed_t, int64_t per_rank_pixels,
-                     uint32_t *d_color, float *d_t, int32_t W, int32_t H, const rt_tile *tile,
-                     void *stream) {
-  if (!tile || tile->num_ranks < 1 || tile->band_rows <= 0 || W <= 0 || H <= 0)
-    return set_err(RT_E_INVALID, "bad tile");
-  const int64_t n = (int64_t)W * H;
-  untile_kernel<<<(unsigned)((n + 255) / 256), 256, 0, (hipStream_t)stream>>>(
-      d_packed_color, d_packed_t, per_rank_pixels, d_color, d_t, W, H, tile->band_rows, tile->num_ranks);
-  HIP_TRY(hipGetLastError());
-  return RT_OK;
-}
-
-int rt_intersect_rays(rt_scene *s, const float *o, const float *d, int64_t n, float tnear, float tfar,
-                      int32_t *hit, float *t, float *normal, int64_t *prim) {
-  if (!s || !o || !d || !hit || !t || !normal || !prim) return set_err(RT_E_INVALID, "NULL argument");
-  if (n <= 0) return RT_OK;
-  float *dO = nullptr, *dD = nullptr, *dT = nullptr, *dN = nullptr;
-  int32_t *dH = nullptr;
-  int64_t *dP = nullptr;
-  auto cleanup = [&]() {
-    void *ps[] = {dO, dD, dT, dN, dH, dP};
-    for (void *q : ps)
-      if (q) HIP_NOTE(hipFree(q));
-  };
-  hipError_t e = hipSuccess;
-  do {
-    if ((e = hipMalloc(&dO, n * 12)) || (e = hipMalloc(&dD, n * 12)) || (e = hipMalloc(&dT, n * 4)) ||
-        (e = hipMalloc(&dN, n * 12)) || (e = hipMalloc(&dH, n * 4)) || (e = hipMalloc(&dP, n * 8)))
-      break;
-    if ((e = rtdma::h2d(dO, o, n * 12, nullptr)) || (e = rtdma::h2d(dD, d, n * 12, nullptr))) break;
-    if (s->kind == RT_SCENE_MESH) {
-      const MeshDev md = mesh_dev(s);
-      switch (s->maxd) {
-        case 4: launch_rays_t<MeshS, 4>(MeshS{md}, s->plane, dO, dD, n, tnear, tfar, dH, dT, dN, dP); break;
-        case 7: launch_rays_t<MeshS, 7>(MeshS{md}, s->plane, dO, dD, n, tnear, tfar, dH, dT, dN, dP); break;
-        case 15: launch_rays_t<MeshS, 15>(MeshS{md}, s->plane, dO, dD, n, tnear, tfar, dH, dT, dN, dP); break;
-        default: launch_rays_t<MeshS, 31>(MeshS{md}, s->plane, dO, dD, n, tnear, tfar, dH, dT, dN, dP); break;
-      }
-    } else if (s->kind == RT_SCENE_GRID) {
-      const GridDev gd = grid_dev(s);
-      switch (grid_mode(s, gd)) {
-        case kGridBuf | kGridBricked:
-          launch_rays_t<GridS<kGridBuf | kGridBricked>, 1>({gd}, s->plane, dO, dD, n, tnear, tfar, dH, dT, dN, dP);
-          break;
-        case kGridBricked:
-          launch_rays_t<GridS<kGridBricked>, 1>({gd}, s->plane, dO, dD, n, tnear, tfar, dH, dT, dN, dP);
-          break;
-        default: launch_rays_t<GridS<kGridBuf>, 1>({gd}, s->plane, dO, dD, n, tnear, tfar, dH, dT, dN, dP); break;
-      }
-    } else if (s->kind == RT_SCENE_INSTANCED) {
-      // the device entry's kernel on the staged buffers (the same values)
-      const rt_ray_batch b{n, dO, dD, nullptr, nullptr, tnear, tfar, dH, dT, dN, dP};
-      if (const int rc = launch_trace(s, b, kRaysNormal, nullptr)) {
-        cleanup();
-        return rc;
-      }
-    } else if (s->kind != RT_SCENE_OCTREE) {
-      cleanup();
-      return set_err(RT_E_STATE, "rt_intersect_rays: scene has no geometry");
-    } else {
-      const OctDev od{s->d_child, s->d_ovals};
-      switch (s->maxd) {
-        case 4: launch_rays_t<OctS<true>, 4>(OctS<true>{od}, s->plane, dO, dD, n, tnear, tfar, dH, dT, dN, dP); break;
-        case 7: launch_rays_t<OctS<true>, 7>(OctS<true>{od}, s->plane, dO, dD, n, tnear, tfar, dH, dT, dN, dP); break;
-        case 15: launch_rays_t<OctS<false>, 15>(OctS<false>{od}, s->plane, dO, dD, n, tnear, tfar, dH, dT, dN, dP); break;
-        default: launch_rays_t<OctS<false>, 31>(OctS<false>{od}, s->plane, dO, dD, n, tnear, tfar, dH, dT, dN, dP); break;
-      }
-    }
-    if ((e = hipGetLastError())) break;
-    if ((e = rtdma::d2h(hit, dH, n * 4, nullptr)) || (e = rtdma::d2h(t, dT, n * 4, nullptr)) ||
-        (e = rtdma::d2h(normal, dN, n * 12, nullptr)) || (e = rtdma::d2h(prim, dP, n * 8, nullptr)))
-      break;
-  } while (0);
-  cleanup();
-  if (e != hipSuccess) return set_err(RT_E_DEVICE, std::string("rt_intersect_rays: ") + hipGetErrorString(e));
-  return RT_OK;
-}
-
-int rt_trace_rays_device(rt_scene *s, const rt_ray_batch *b, uint32_t flags, void *stream) {
-  if (!s) return set_err(RT_E_INVALID, "scene is NULL");
-  if (!b) return set_err(RT_E_INVALID, "ray batch is NULL");
-  if (flags & ~RT_RAYS_ANY_HIT) return set_err(RT_E_INVALID, "unknown ray flag");
-  if (b->n < 0) return set_err(RT_E_INVALID, "negative ray count");
-  if (!b->d_origin || !b->d_dir) return set_err(RT_E_INVALID, "NULL ray origins or directions");
-  if (!b->d_hit && !b->d_t && !b->d_normal && !b->d_prim) return set_err(RT_E_INVALID, "no output buffer");
-  const bool any = (flags & RT_RAYS_ANY_HIT) != 0;
-  if (any && (!b->d_hit || b->d_t || b->d_normal || b->d_prim))
-    return set_err(RT_E_INVALID, "RT_RAYS_ANY_HIT writes d_hit only: d_t, d_normal and d_prim must be NULL");
-  if (b->n / kRBlock + (b->n % kRBlock != 0) > kMaxRayBlocks)
-    return set_err(RT_E_INVALID, "ray count exceeds one launch (" + std::to_string(kMaxRayBlocks * kRBlock) +
-                                     " rays): split the batch");
-  if (b->n == 0) return RT_OK;
-  return launch_trace(s, *b, any ? kRaysAny : b->d_normal ? kRaysNormal : kRaysClosest, (hipStream_t)stream);
 }
 
 // the counting kernel over `frames` frames: all C_ALL counters
@@ -3674,24 +1910,12 @@ int rtx_set_band_order(int on) {
   return RT_OK;
 }
 
-// Builder of this thread's last BVH: 1 host, 2 device, 3 host after a failed
-// device build (AUTO mode falls back; see rtx_bvh_inject_failure)
-int rtx_bvh_last_builder(void) { return t_bvh_last; }
-
 // Diagnostic: persistent launches from now on write per-wave stamps (see
 // PersistQ::stamps) into the device buffer d_buf of cap_waves x 8 u64
 // (d_buf = NULL turns it off). Not part of include/rtamd.h.
 int rtx_set_persist_stamps(void *d_buf, int64_t cap_waves) {
   g_persist_stamps = (unsigned long long *)d_buf;
   g_persist_stamps_cap = d_buf ? cap_waves : 0;
-  return RT_OK;
-}
-
-// Diagnostic: force grid layouts / address paths (g_grid_force bits). Not part
-// of include/rtamd.h.
-int rtx_set_grid_force(int flags) {
-  if (flags < 0 || flags > 3) return set_err(RT_E_INVALID, "grid force flags must be 0..3");
-  g_grid_force = flags;
   return RT_OK;
 }
 
@@ -3754,47 +1978,260 @@ int rt_bench_frames(rt_scene *s, const rt_render_params *params, int32_t frames,
 
 }  // extern "C"
 
-// ------------------------------------------------ rt_multi_render internals --
-namespace rti {
-// One slot of rt_multi_render's zero-copy cleared frame (RT_FLAG_CLEAR |
-// RT_FLAG_HITS_ONLY over a cleared host frame): the slot's bands of `tile` go
-// through the one-frame kernel on `stream`, storing only their hits, at their
-// own rows of the W x H host frame whose device addresses (on the scene's
-// device) are dc / dt (kFlagNatural: one frame shared by every slot). With
-// d_span != NULL the kernel records per LOCAL row (tile->rank's rows in
-// increasing order) the span of the pixels it stored (kFlagRowSpan, 2 words per
-// row, pre-set to INT32_MAX by the caller).
-int render_band_host(rt_scene *s, const rt_render_params *p, uint32_t *dc, float *dt, int32_t W, int32_t H,
-                     const rt_tile *tile, int32_t *d_span, hipStream_t stream) {
-  if (!s) return set_err(RT_E_INVALID, "scene is NULL");
-  if (int rc = check_params(p, W, H)) return rc;
-  FrameArgs fa;
-  if (int rc = fill_frame(fa, s, p, dc, dt, W, H, RT_FLAG_CLEAR | RT_FLAG_HITS_ONLY, tile)) return rc;
-  if (fa.rows_local <= 0) return RT_OK;
-  fa.flags |= kFlagHostFrame | kFlagNatural | (d_span ? kFlagRowSpan : 0u);
-  fa.hit_box = d_span;
-  return launch_render(s, fa, stream);
+// ============================================================ ray queries ==
+// rays_kernel behind rt_intersect_rays (host buffers; the shading path's
+// per-lane S::intersect on arbitrary rays) and trace_rays_kernel behind
+// rt_trace_rays_device (device buffers, closest and any hit, on a stream). An
+// instanced scene's rays go on to rt_instances.hip. They are compiled in this
+// unit, beside the render kernels whose traversal instantiations they share:
+// in a unit of their own, the render kernels come out with other code
+// (profiles/r17/README.md).
+namespace {
+
+template <class S, int SLOTS>
+__global__ __launch_bounds__(kBlock) void rays_kernel(S sc, PlaneDev pl, const float *o3,
+                                                       const float *d3, int64_t n, float tn,
+                                                       float tf, int32_t *hit, float *t,
+                                                       float *nrm, int64_t *prim) {
+  __shared__ uint32_t stk[stack_words<S, SLOTS>() * kBlock];
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  StackOf<S, kBlock> st{stk + threadIdx.x};
+  const f3 o{o3[3 * i], o3[3 * i + 1], o3[3 * i + 2]};
+  const f3 d{d3[3 * i], d3[3 * i + 1], d3[3 * i + 2]};
+  NoCnt cnt;
+  const SurfHit sh = union_intersect<S, kBlock>(sc, pl, o, d, tn, tf, st, cnt);
+  hit[i] = sh.h.hit ? 1 : 0;
+  t[i] = sh.h.t;
+  nrm[3 * i] = sh.h.n.x;
+  nrm[3 * i + 1] = sh.h.n.y;
+  nrm[3 * i + 2] = sh.h.n.z;
+  prim[i] = sh.h.hit ? sh.h.prim : -1;
 }
 
-uint64_t scene_version(const rt_scene *s) { return s ? s->version : 0; }
+// ---- rt_trace_rays_device: IScene::intersect on device buffers -------------
+// One ray per lane, like rays_kernel, with the work chosen at compile time:
+// kRaysAny (S::occluded, one word per ray), kRaysClosest (no normal is
+// computed: no tri_normal triangle reload, no grid_normal, oct_trace without
+// NEED_NORMAL) and kRaysNormal. The outputs the caller left NULL and the
+// per-ray tNear / tFar arrays are wave-uniform branches on kernel arguments.
+// The mesh's closest hit is mesh_primary_wave (a wave's last rays finish in
+// 8-lane groups), the other traversals are per lane (DESIGN.md section 4;
+// what was measured against them is in section 8).
+// Workgroup of trace_rays_kernel: one wave. A ray batch has no tile that needs
+// four waves together, and a workgroup keeps its LDS stacks until its slowest
+// wave ends.
+constexpr int kRBlock = 64;
+// a launch's global size is a 32-bit count of work-items
+constexpr int64_t kMaxRayBlocks = (int64_t)(0xFFFFFFFFu / (uint32_t)kRBlock);
 
-// A replica (rt_scene_replicate) of mesh scene `src` brought up to src's last
-// update: nodes and triangles copied device to device (the sizes never
-// change), the three host constants taken over. Blocking; the caller has
-// drained the streams that use the replica.
-int scene_refresh_replica(rt_scene *rep, const rt_scene *src) {
-  if (!rep || !src || rep->kind != src->kind) return set_err(RT_E_INVALID, "scene_refresh_replica: bad arguments");
-  if (rep->version == src->version || src->kind != RT_SCENE_MESH) return RT_OK;
-  if (rep->n_inner != src->n_inner || rep->n_tris != src->n_tris)
-    return set_err(RT_E_STATE, "scene_refresh_replica: the replica is not of this scene");
-  if (src->n_inner)
-    HIP_TRY(hipMemcpyPeer(rep->d_nodes, rep->device, src->d_nodes, src->device, (size_t)src->n_inner * sizeof(rtl::GNode)));
-  if (src->n_tris)
-    HIP_TRY(hipMemcpyPeer(rep->d_tris, rep->device, src->d_tris, src->device, (size_t)src->n_tris * sizeof(rtl::GTri)));
-  std::memcpy(rep->root_box, src->root_box, sizeof rep->root_box);
-  std::memcpy(rep->root_child, src->root_child, sizeof rep->root_child);
-  rep->dmax2 = src->dmax2;
-  rep->version = src->version;
+// S::intersect with the normal (and the primitive id's load) optional
+template <int B, bool NORMAL, class CT>
+__device__ __forceinline__ Hit rays_closest(const MeshS &sc, f3 o, f3 d, float tn, float tf,
+                                            LdsStack<B, MeshS::kFields> st, bool want_prim, CT &cnt) {
+  float t;
+  uint32_t k;
+  Hit h = miss_hit();
+  if (mesh_trace<B, false>(sc.d, o, d, tn, tf, st, t, k, cnt)) {
+    h.hit = true;
+    h.t = t;
+    if constexpr (NORMAL) h.n = tri_normal(sc.d.tris, k);
+    if (want_prim) h.prim = (int64_t)sc.d.tris[k].orig_id;
+  }
+  return h;
+}
+template <int B, bool NORMAL, int kMode, class CT>
+__device__ __forceinline__ Hit rays_closest(const GridS<kMode> &sc, f3 o, f3 d, float tn, float tf,
+                                            LdsStack<B, GridS<kMode>::kFields>, bool, CT &cnt) {
+  Hit h = miss_hit();
+  f3 p;
+  uint32_t cell;
+  if (grid_march<kMode>(sc.d, o, d, tn, tf, h.t, p, cell, cnt)) {
+    h.hit = true;
+    if constexpr (NORMAL) h.n = grid_normal<kMode>(sc.d, p, cnt);
+    h.prim = (int64_t)cell;
+  } else {
+    h.t = kInf;
+  }
+  return h;
+}
+template <int B, bool NORMAL, bool PACK, class CT>
+__device__ __forceinline__ Hit rays_closest(const OctS<PACK> &sc, f3 o, f3 d, float tn, float tf,
+                                            LdsStack<B, kOctFields> st, bool, CT &cnt) {
+  Hit h = miss_hit();
+  uint32_t node;
+  if (oct_trace<B, NORMAL, PACK>(sc.d, o, d, tn, tf, st, h.t, h.n, node, cnt)) {
+    h.hit = true;
+    h.prim = (int64_t)node;
+  } else {
+    h.t = kInf;
+  }
+  return h;
+}
+
+// Occupancy floor of the mesh's closest-hit query at 4 and 7 slots: the
+// primary kernels' 5 waves per SIMD. Left to itself the compiler took 94 VGPRs
+// there before the shared node fetch and 118 (4 waves) with it.
+template <class S, int SLOTS, int MODE>
+constexpr int trace_min_waves() {
+  return (S::kCoop && SLOTS <= 7 && MODE != kRaysAny) ? S::kMinWaves : 1;
+}
+template <class S, int SLOTS, int MODE>
+__global__ __launch_bounds__(kRBlock) __attribute__((amdgpu_waves_per_eu(trace_min_waves<S, SLOTS, MODE>())))
+void trace_rays_kernel(S sc, PlaneDev pl, rt_ray_batch b) {
+  __shared__ uint32_t stk[stack_words<S, SLOTS>() * kRBlock];
+  const int64_t i = (int64_t)blockIdx.x * kRBlock + threadIdx.x;
+  // a partial last wave keeps its lanes without a ray: mesh_primary_wave needs
+  // the whole wave, so they carry active = false and touch no memory
+  const bool active = i < b.n;
+  StackOf<S, kRBlock> st{stk + threadIdx.x};
+  f3 o{0.0f, 0.0f, 0.0f}, d{0.0f, 0.0f, 1.0f};
+  float tn = b.tnear, tf = b.tfar;
+  if (active) {
+    o = f3{b.d_origin[3 * i], b.d_origin[3 * i + 1], b.d_origin[3 * i + 2]};
+    d = f3{b.d_dir[3 * i], b.d_dir[3 * i + 1], b.d_dir[3 * i + 2]};
+    if (b.d_tnear) tn = b.d_tnear[i];
+    if (b.d_tfar) tf = b.d_tfar[i];
+  }
+  NoCnt cnt;
+  if constexpr (MODE == kRaysAny) {
+    if (active) b.d_hit[i] = union_occluded<S, kRBlock>(sc, pl, o, d, tn, tf, st, cnt) ? 1 : 0;
+  } else {
+    Hit h = miss_hit();
+    bool traced = false;
+    if constexpr (std::is_same_v<S, MeshS>) {
+      // mesh_primary_wave takes one tNear for the wave (tFar is per ray):
+      // batches with a d_tnear array take the per-lane traversal below
+      if (!b.d_tnear) {
+        float t;
+        uint32_t k;
+        if (mesh_primary_wave<kRBlock, MeshS::kFields>(sc.d, o, d, tn, tf, active, stk, t, k) && active) {
+          h.hit = true;
+          h.t = t;
+          if constexpr (MODE == kRaysNormal) h.n = tri_normal(sc.d.tris, k);
+          if (b.d_prim) h.prim = (int64_t)sc.d.tris[k].orig_id;
+        }
+        traced = true;
+      }
+    }
+    if (!active) return;
+    if (!traced) h = rays_closest<kRBlock, MODE == kRaysNormal>(sc, o, d, tn, tf, st, b.d_prim != nullptr, cnt);
+    if (pl.on) {  // SceneUnion::intersect, as union_intersect
+      float tp = kInf, ap = 1.0f;
+      const bool ph = plane_hit(pl, o, d, tn, tf, tp, ap);
+      if (!(h.t < (ph ? tp : kInf))) h = ph ? Hit{true, tp, pl.n, -2} : miss_hit();
+    }
+    if (b.d_hit) b.d_hit[i] = h.hit ? 1 : 0;
+    if (b.d_t) b.d_t[i] = h.t;
+    if constexpr (MODE == kRaysNormal) {
+      b.d_normal[3 * i] = h.n.x;
+      b.d_normal[3 * i + 1] = h.n.y;
+      b.d_normal[3 * i + 2] = h.n.z;
+    }
+    if (b.d_prim) b.d_prim[i] = h.hit ? h.prim : -1;
+  }
+}
+
+template <class S, int MAXD>
+void launch_rays_t(const S &sc, const PlaneDev &pl, const float *o, const float *d, int64_t n,
+                   float tn, float tf, int32_t *hit, float *t, float *nrm, int64_t *prim) {
+  const int64_t blocks = (n + kBlock - 1) / kBlock;
+  rays_kernel<S, MAXD><<<(unsigned)blocks, kBlock>>>(sc, pl, o, d, n, tn, tf, hit, t, nrm, prim);
+}
+
+template <class S, int MAXD>
+void launch_trace_t(const S &sc, const PlaneDev &pl, const rt_ray_batch &b, int mode, hipStream_t stream) {
+  const unsigned blocks = (unsigned)((b.n + kRBlock - 1) / kRBlock);
+  switch (mode) {
+    case kRaysAny: trace_rays_kernel<S, MAXD, kRaysAny><<<blocks, kRBlock, 0, stream>>>(sc, pl, b); break;
+    case kRaysClosest: trace_rays_kernel<S, MAXD, kRaysClosest><<<blocks, kRBlock, 0, stream>>>(sc, pl, b); break;
+    default: trace_rays_kernel<S, MAXD, kRaysNormal><<<blocks, kRBlock, 0, stream>>>(sc, pl, b); break;
+  }
+}
+
+// rt_trace_rays_device's launch: an instanced scene goes to rt_instances.hip,
+// every other one through the scene dispatch
+int launch_trace(rt_scene *s, const rt_ray_batch &b, int mode, hipStream_t stream) {
+  if (s->kind == RT_SCENE_INSTANCED) {
+    // a bottom-level scene refitted since its table entry was written: the
+    // entry is rewritten in stream order ahead of the trace, no host wait
+    for (size_t j = 0; j < s->blas.size(); ++j) {
+      if (s->blas[j]->version == s->blas_seen[j]) continue;
+      if (int rc = rti::blas_entry_launch(s->d_blas + j, mesh_dev(s->blas[j]), stream)) return rc;
+      s->blas_seen[j] = s->blas[j]->version;
+    }
+    return rti::trace_instances_launch(rti::InstArgs{s->d_inst, s->d_blas, s->ninst, s->maxd}, s->plane, b, mode,
+                                       stream);
+  }
+  if (!dispatch_scene(s, [&](const auto &sc, auto slots) {
+        launch_trace_t<std::decay_t<decltype(sc)>, decltype(slots)::value>(sc, s->plane, b, mode, stream);
+      }))
+    return set_err(RT_E_STATE, "scene has no geometry");
+  HIP_TRY(hipGetLastError());
   return RT_OK;
 }
-}  // namespace rti
+
+}  // namespace
+
+extern "C" {
+
+int rt_intersect_rays(rt_scene *s, const float *o, const float *d, int64_t n, float tnear, float tfar,
+                      int32_t *hit, float *t, float *normal, int64_t *prim) {
+  if (!s || !o || !d || !hit || !t || !normal || !prim) return set_err(RT_E_INVALID, "NULL argument");
+  if (n <= 0) return RT_OK;
+  float *dO = nullptr, *dD = nullptr, *dT = nullptr, *dN = nullptr;
+  int32_t *dH = nullptr;
+  int64_t *dP = nullptr;
+  auto cleanup = [&]() {
+    void *ps[] = {dO, dD, dT, dN, dH, dP};
+    for (void *q : ps)
+      if (q) HIP_NOTE(hipFree(q));
+  };
+  hipError_t e = hipSuccess;
+  do {
+    if ((e = hipMalloc(&dO, n * 12)) || (e = hipMalloc(&dD, n * 12)) || (e = hipMalloc(&dT, n * 4)) ||
+        (e = hipMalloc(&dN, n * 12)) || (e = hipMalloc(&dH, n * 4)) || (e = hipMalloc(&dP, n * 8)))
+      break;
+    if ((e = rtdma::h2d(dO, o, n * 12, nullptr)) || (e = rtdma::h2d(dD, d, n * 12, nullptr))) break;
+    if (s->kind == RT_SCENE_INSTANCED) {
+      // the device entry's kernel on the staged buffers (the same values)
+      const rt_ray_batch b{n, dO, dD, nullptr, nullptr, tnear, tfar, dH, dT, dN, dP};
+      if (const int rc = launch_trace(s, b, kRaysNormal, nullptr)) {
+        cleanup();
+        return rc;
+      }
+    } else if (!dispatch_scene(s, [&](const auto &sc, auto slots) {
+                 launch_rays_t<std::decay_t<decltype(sc)>, decltype(slots)::value>(sc, s->plane, dO, dD, n, tnear,
+                                                                                   tfar, dH, dT, dN, dP);
+               })) {
+      cleanup();
+      return set_err(RT_E_STATE, "rt_intersect_rays: scene has no geometry");
+    }
+    if ((e = hipGetLastError())) break;
+    if ((e = rtdma::d2h(hit, dH, n * 4, nullptr)) || (e = rtdma::d2h(t, dT, n * 4, nullptr)) ||
+        (e = rtdma::d2h(normal, dN, n * 12, nullptr)) || (e = rtdma::d2h(prim, dP, n * 8, nullptr)))
+      break;
+  } while (0);
+  cleanup();
+  if (e != hipSuccess) return set_err(RT_E_DEVICE, std::string("rt_intersect_rays: ") + hipGetErrorString(e));
+  return RT_OK;
+}
+
+int rt_trace_rays_device(rt_scene *s, const rt_ray_batch *b, uint32_t flags, void *stream) {
+  if (!s) return set_err(RT_E_INVALID, "scene is NULL");
+  if (!b) return set_err(RT_E_INVALID, "ray batch is NULL");
+  if (flags & ~RT_RAYS_ANY_HIT) return set_err(RT_E_INVALID, "unknown ray flag");
+  if (b->n < 0) return set_err(RT_E_INVALID, "negative ray count");
+  if (!b->d_origin || !b->d_dir) return set_err(RT_E_INVALID, "NULL ray origins or directions");
+  if (!b->d_hit && !b->d_t && !b->d_normal && !b->d_prim) return set_err(RT_E_INVALID, "no output buffer");
+  const bool any = (flags & RT_RAYS_ANY_HIT) != 0;
+  if (any && (!b->d_hit || b->d_t || b->d_normal || b->d_prim))
+    return set_err(RT_E_INVALID, "RT_RAYS_ANY_HIT writes d_hit only: d_t, d_normal and d_prim must be NULL");
+  if (b->n / kRBlock + (b->n % kRBlock != 0) > kMaxRayBlocks)
+    return set_err(RT_E_INVALID, "ray count exceeds one launch (" + std::to_string(kMaxRayBlocks * kRBlock) +
+                                     " rays): split the batch");
+  if (b->n == 0) return RT_OK;
+  return launch_trace(s, *b, any ? kRaysAny : b->d_normal ? kRaysNormal : kRaysClosest, (hipStream_t)stream);
+}
+
+}  // extern "C"

@@ -1,7 +1,7 @@
 // rt_instances.h -- instanced scenes (RT_SCENE_INSTANCED, include/rtamd.h):
 // the device records, the one function that defines an instance's
 // world-to-object matrix, and the launches of rt_instances.hip as rt_device.hip
-// queues them.
+// (traces) and rt_scene.hip (pose updates) queue them.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -61,8 +61,7 @@ struct InstArgs {
   int32_t ninst;
   int32_t maxd;
 };
-// mode: 0 any hit, 1 closest hit without the normal, 2 with it (rt_device.hip's
-// kRaysAny / kRaysClosest / kRaysNormal). Only launches.
+// mode: kRaysAny / kRaysClosest / kRaysNormal (rt_shade.h). Only launches.
 int trace_instances_launch(const InstArgs &a, const rtd::PlaneDev &pl, const rt_ray_batch &b, int mode,
                            hipStream_t st);
 // Writes one table entry in stream order (the entry travels as a kernel

@@ -4,7 +4,8 @@
 // bottom-level scenes. Semantics: include/rtamd.h and DESIGN.md section 4a.
 //
 // A translation unit of its own: the kernels of rt_device.hip compile exactly
-// as before whatever is instantiated here.
+// as before whatever is instantiated here. The stack slot switch is
+// rt_dispatch.h's, the mode enum rt_shade.h's.
 //
 // The instance loop is wave-uniform. An instance record (64 bytes) and the
 // MeshDev of its bottom-level scene are read through addresses every lane
@@ -16,6 +17,7 @@
 // inline assembly and no device-scope waiting.
 #include <hip/hip_runtime.h>
 
+#include "rt_dispatch.h"
 #include "rt_error.h"
 #include "rt_instances.h"
 #include "rt_layout.h"
@@ -27,8 +29,6 @@ using namespace rtd;
 namespace {
 
 constexpr int kIBlock = 64;  // one wave, as trace_rays_kernel (rt_device.hip)
-enum { kAny = 0, kClosest = 1, kNormal = 2 };
-constexpr int kF = 3;  // LDS words per stack slot of the mesh traversal (MeshS::kFields)
 
 // world -> object, with the operation order of include/rtamd.h (no fusing)
 __device__ __forceinline__ f3 xf_point(const float *m, f3 p) {
@@ -55,12 +55,12 @@ template <int SLOTS, int MODE>
 __global__ __launch_bounds__(kIBlock) void trace_instances_kernel(const rti::InstRec *__restrict__ inst,
                                                                   const MeshDev *__restrict__ tab, int32_t ninst,
                                                                   PlaneDev pl, rt_ray_batch b) {
-  __shared__ uint32_t stk[SLOTS * kF * kIBlock];
+  __shared__ uint32_t stk[SLOTS * MeshS::kFields * kIBlock];
   const int64_t i = (int64_t)blockIdx.x * kIBlock + threadIdx.x;
   // a partial last wave keeps its lanes without a ray (mesh_primary_wave needs
   // the whole wave): they carry active = false and touch no memory
   const bool active = i < b.n;
-  LdsStack<kIBlock, kF> st{stk + threadIdx.x};
+  LdsStack<kIBlock, MeshS::kFields> st{stk + threadIdx.x};
   f3 o{0.0f, 0.0f, 0.0f}, d{0.0f, 0.0f, 1.0f};
   float tn = b.tnear, tf = b.tfar;
   if (active) {
@@ -70,7 +70,7 @@ __global__ __launch_bounds__(kIBlock) void trace_instances_kernel(const rti::Ins
     if (b.d_tfar) tf = b.d_tfar[i];
   }
   NoCnt cnt;
-  if constexpr (MODE == kAny) {
+  if constexpr (MODE == kRaysAny) {
     // OR over the instances of the bottom-level any hit under the full tFar;
     // a lane that has its hit goes inactive, the wave stops when none is left
     bool live = active, occ = false;
@@ -113,7 +113,7 @@ __global__ __launch_bounds__(kIBlock) void trace_instances_kernel(const rti::Ins
       // mesh_primary_wave takes one tNear for the wave (tFar is per ray):
       // batches with a d_tnear array take the per-lane traversal
       if (!b.d_tnear)
-        h = mesh_primary_wave<kIBlock, kF>(md, oo, dd, tn, tfi, go, stk, t, tri) && go;
+        h = mesh_primary_wave<kIBlock, MeshS::kFields>(md, oo, dd, tn, tfi, go, stk, t, tri) && go;
       else
         h = go && mesh_trace<kIBlock, false>(md, oo, dd, tn, tfi, st, t, tri, cnt);
       if (h && t < best) {  // ties keep the lower index
@@ -130,7 +130,7 @@ __global__ __launch_bounds__(kIBlock) void trace_instances_kernel(const rti::Ins
       const rtl::GTri *tris = tab[inst[wi].blas].tris;
       h.hit = true;
       h.t = best;
-      if constexpr (MODE == kNormal) {
+      if constexpr (MODE == kRaysNormal) {
         const f3 n = tri_normal(tris, wk);  // object space
         // the inverse transpose of the object-to-world map: M^T n
         h.n = normalize(f3{(m[0] * n.x + m[4] * n.y) + m[8] * n.z, (m[1] * n.x + m[5] * n.y) + m[9] * n.z,
@@ -145,7 +145,7 @@ __global__ __launch_bounds__(kIBlock) void trace_instances_kernel(const rti::Ins
     }
     if (b.d_hit) b.d_hit[i] = h.hit ? 1 : 0;
     if (b.d_t) b.d_t[i] = h.t;
-    if constexpr (MODE == kNormal) {
+    if constexpr (MODE == kRaysNormal) {
       b.d_normal[3 * i] = h.n.x;
       b.d_normal[3 * i + 1] = h.n.y;
       b.d_normal[3 * i + 2] = h.n.z;
@@ -187,11 +187,15 @@ template <int SLOTS>
 void launch_t(const rti::InstArgs &a, const PlaneDev &pl, const rt_ray_batch &b, int mode, hipStream_t st) {
   const unsigned blocks = (unsigned)((b.n + kIBlock - 1) / kIBlock);
   switch (mode) {
-    case kAny: trace_instances_kernel<SLOTS, kAny><<<blocks, kIBlock, 0, st>>>(a.inst, a.blas, a.ninst, pl, b); break;
-    case kClosest:
-      trace_instances_kernel<SLOTS, kClosest><<<blocks, kIBlock, 0, st>>>(a.inst, a.blas, a.ninst, pl, b);
+    case kRaysAny:
+      trace_instances_kernel<SLOTS, kRaysAny><<<blocks, kIBlock, 0, st>>>(a.inst, a.blas, a.ninst, pl, b);
       break;
-    default: trace_instances_kernel<SLOTS, kNormal><<<blocks, kIBlock, 0, st>>>(a.inst, a.blas, a.ninst, pl, b); break;
+    case kRaysClosest:
+      trace_instances_kernel<SLOTS, kRaysClosest><<<blocks, kIBlock, 0, st>>>(a.inst, a.blas, a.ninst, pl, b);
+      break;
+    default:
+      trace_instances_kernel<SLOTS, kRaysNormal><<<blocks, kIBlock, 0, st>>>(a.inst, a.blas, a.ninst, pl, b);
+      break;
   }
 }
 
@@ -200,12 +204,7 @@ void launch_t(const rti::InstArgs &a, const PlaneDev &pl, const rt_ray_batch &b,
 namespace rti {
 
 int trace_instances_launch(const InstArgs &a, const PlaneDev &pl, const rt_ray_batch &b, int mode, hipStream_t st) {
-  switch (a.maxd) {
-    case 4: launch_t<4>(a, pl, b, mode, st); break;
-    case 7: launch_t<7>(a, pl, b, mode, st); break;
-    case 15: launch_t<15>(a, pl, b, mode, st); break;
-    default: launch_t<31>(a, pl, b, mode, st); break;
-  }
+  with_slots(a.maxd, [&](auto slots) { launch_t<decltype(slots)::value>(a, pl, b, mode, st); });
   HIP_TRY(hipGetLastError());
   return RT_OK;
 }

@@ -1,5 +1,5 @@
 // rt_refit.h -- the device refit of a mesh scene's BVH8 (rt_refit.hip), as
-// rt_scene_update_vertices_device (rt_device.hip) queues it.
+// rt_scene_update_vertices_device (rt_scene.hip) queues it.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -1,0 +1,816 @@
+// rt_scene.hip -- scenes: creation from meshes (with the BVH builder choice),
+// grids and octrees, replication to another device, vertex updates of dynamic
+// meshes, instanced scenes, destruction, the plane and the getters of
+// include/rtamd.h, and the device views of a scene that the kernel launchers
+// take (mesh_dev, grid_dev, grid_mode; rt_scene.h). Its kernels are the two
+// that prepare scene data (brick_kernel, tri_edge_bound_kernel).
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+#include <limits>
+#include <string>
+#include <vector>
+
+#include "../../include/rtamd.h"
+#include "rt_dispatch.h"
+#include "rt_error.h"
+#include "rt_host.h"
+#include "rt_refit.h"
+#include "rt_scene.h"
+#include "rt_shade.h"
+
+using namespace rtd;
+using namespace rti;
+
+namespace {
+
+// bricked sample count of a grid (rt_scenes.h GridDev)
+uint64_t grid_bricked_samples(const uint32_t size[3]) {
+  return (uint64_t)grid_bricks(size[0]) * grid_bricks(size[1]) * grid_bricks(size[2]) * 64u;
+}
+
+// device samples of a grid scene (s->grid_bricked picks the layout)
+uint64_t grid_samples(const rt_scene *s) {
+  return s->grid_bricked ? grid_bricked_samples(s->size) : (uint64_t)s->size[0] * s->size[1] * s->size[2];
+}
+
+// diagnostic (rtx_set_grid_force): bit 0 = grids created from now on take the
+// bricked layout whatever their size, bit 1 = every grid launch takes the 64-bit
+// address path (no buffer loads); tests reach each grid_mode branch with it
+int g_grid_force = 0;
+
+}  // namespace
+
+namespace rti {
+
+GridDev grid_dev(const rt_scene *s) {
+  const uint64_t n = grid_samples(s);
+  // buffer loads: 32-bit byte offsets and num_records, so only grids below
+  // 4 GiB (a grid of exactly 2^32 bytes would put its last sample past a
+  // saturated num_records) -- larger ones take the 64-bit address path
+  const uint32_t bytes = 4 * n < (1ull << 32) ? (uint32_t)(4 * n) : 0u;
+  if (!s->grid_bricked) return GridDev{s->d_vals, s->size[0], s->size[1], s->size[2], s->size[2],
+                                       s->size[1] * s->size[2], bytes};
+  const uint32_t ys = grid_bricks(s->size[2]) * 64u;
+  return GridDev{s->d_vals, s->size[0], s->size[1], s->size[2], ys, grid_bricks(s->size[1]) * ys, bytes};
+}
+
+int grid_mode(const rt_scene *s, const GridDev &gd) {
+  // buffer mode: 32-bit byte offsets and 24-bit stride multiplies (grid_mul)
+  const bool buf = gd.bytes != 0 && gd.xs < (1u << 24) && gd.ys < (1u << 24) && !(g_grid_force & 2);
+  return (buf ? kGridBuf : 0) | (s->grid_bricked ? kGridBricked : 0);
+}
+
+}  // namespace rti
+
+namespace {
+
+// reference x-major values -> 4x4x4 bricks; one thread per bricked sample
+// (padding samples get 0 and are never read)
+__global__ __launch_bounds__(256) void brick_kernel(const float *__restrict__ src, float *__restrict__ dst,
+                                                    uint32_t sx, uint32_t sy, uint32_t sz, uint64_t n) {
+  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t nby = grid_bricks(sy), nbz = grid_bricks(sz);
+  const uint32_t l = (uint32_t)(i & 63u);
+  const uint64_t b = i >> 6;
+  const uint32_t bz = (uint32_t)(b % nbz), by = (uint32_t)((b / nbz) % nby), bx = (uint32_t)(b / nbz / nby);
+  const uint32_t x = bx * 4 + (l >> 4), y = by * 4 + ((l >> 2) & 3u), z = bz * 4 + (l & 3u);
+  dst[i] = (x < sx && y < sy && z < sz) ? src[((uint64_t)x * sy + y) * sz + z] : 0.0f;
+}
+
+}  // namespace
+
+namespace rti {
+
+MeshDev mesh_dev(const rt_scene *s) {
+  MeshDev m{s->d_nodes, s->d_tris, s->root, {}, s->coop, s->dmax2};
+  for (int k = 0; k < 6; ++k) m.rbox[k] = s->root_box[k];
+  return m;
+}
+
+// the entries that render frames or copy a scene take no instanced scene
+int no_instanced(const rt_scene *s, const char *who) {
+  if (s && s->kind == RT_SCENE_INSTANCED)
+    return set_err(RT_E_STATE, std::string(who) + ": not available for an instanced scene");
+  return RT_OK;
+}
+
+}  // namespace rti
+
+namespace {
+
+// LDS frame slots per lane for a tree with `depth` inner levels: the top frame
+// lives in registers, so depth-1 slots. Sized to the tree (not a worst case)
+// so the stack does not cap occupancy: 4 slots x 12 B x 256 lanes = 12 KiB.
+int pick_maxd(int depth, int32_t &maxd) {
+  const int need = depth > 1 ? depth - 1 : 1;
+  const int options[] = {4, 7, 15, 31};
+  for (int m : options)
+    if (need <= m) { maxd = m; return RT_OK; }
+  return set_err(RT_E_INVALID, "tree deeper than 32 levels");
+}
+
+}  // namespace
+
+namespace {
+// BVH8 builder selection (rt_set_bvh_builder): both builders give the same tree
+int g_bvh_mode = RT_BVH_AUTO;
+constexpr int64_t kBvhDeviceMinTris = 32768;  // auto: the device builder from this many triangles
+
+// which builder produced this thread's last tree (rtx_bvh_last_builder):
+// 1 host, 2 device, 3 host after a failed device build (AUTO)
+thread_local int t_bvh_last = 0;
+
+int build_bvh(const float *vpos4, int64_t nverts, const uint32_t *idx, int64_t nidx, rth::BVHGpu &b,
+              unsigned want) {
+  std::string err;
+  int ndev = 0;
+  const bool dev = g_bvh_mode == RT_BVH_DEVICE ||
+                   (g_bvh_mode == RT_BVH_AUTO && nidx / 3 >= kBvhDeviceMinTris &&
+                    hipGetDeviceCount(&ndev) == hipSuccess && ndev > 0);
+  bool fell_back = false;
+  if (dev) {
+    if (rth::build_bvh8_gpu(vpos4, nverts, idx, nidx, b, err, want)) {
+      t_bvh_last = 2;
+      return RT_OK;
+    }
+    if (err.rfind("GPU BVH builder bound", 0) == 0) return set_err(RT_E_DEVICE, err);
+    const bool device_failure = err.rfind("GPU BVH build:", 0) == 0;
+    if (!device_failure) return set_err(RT_E_INVALID, err);
+    if (g_bvh_mode == RT_BVH_DEVICE) return set_err(RT_E_DEVICE, err);
+    // AUTO: the host builder gives the identical tree, unless
+    // the device is left in a sticky fault state: then every later call on it
+    // fails too, so the failure is reported here instead of at the upload
+    if (const hipError_t e = hipDeviceSynchronize(); e != hipSuccess)
+      return set_err(RT_E_DEVICE, err + "; device unusable afterwards: " + hipGetErrorString(e));
+    (void)hipGetLastError();  // the builder's failure was reported above: clear it
+    std::fprintf(stderr, "rtamd: %s; building the BVH on the host instead\n", err.c_str());
+    fell_back = true;
+    err.clear();
+  }
+  if (!rth::build_bvh8(vpos4, nverts, idx, nidx, b, err, want)) return set_err(RT_E_INVALID, err);
+  t_bvh_last = fell_back ? 3 : 1;
+  return RT_OK;
+}
+
+int new_scene(rt_scene **out) {
+  if (!out) return set_err(RT_E_INVALID, "out is NULL");
+  int dev = 0;
+  HIP_TRY(hipGetDevice(&dev));
+  rt_scene *s = new rt_scene();
+  s->device = dev;
+  s->plane.on = 0;
+  s->plane.n = f3{0.0f, 1.0f, 0.0f};
+  *out = s;
+  return RT_OK;
+}
+
+// upload + `pad` zeroed trailing elements (kernels may read past the end).
+template <class T>
+int upload_padded(T **dst, const T *src, size_t n, size_t pad, int64_t &bytes) {
+  HIP_TRY(hipMalloc(dst, (n + pad) * sizeof(T)));
+  HIP_TRY(hipMemset(*dst, 0, (n + pad) * sizeof(T)));
+  if (n) HIP_TRY(rtdma::h2d(*dst, src, n * sizeof(T), nullptr));
+  bytes += (int64_t)((n + pad) * sizeof(T));
+  return RT_OK;
+}
+
+template <class T>
+int upload(T **dst, const T *src, size_t n, int64_t &bytes) {
+  if (n == 0) n = 1;  // keep a valid pointer
+  HIP_TRY(hipMalloc(dst, n * sizeof(T)));
+  if (src) HIP_TRY(rtdma::h2d(*dst, src, n * sizeof(T), nullptr));
+  bytes += (int64_t)(n * sizeof(T));
+  return RT_OK;
+}
+
+// the pinned host words a dynamic mesh's update reads its constants into
+int dynamic_host_words(rt_scene *s) {
+  HIP_TRY(hipHostMalloc((void **)&s->h_refit, 64 * sizeof(uint32_t), hipHostMallocDefault));
+  return RT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rt_set_bvh_builder(int mode) {
+  if (mode < RT_BVH_AUTO || mode > RT_BVH_DEVICE) return set_err(RT_E_INVALID, "bad BVH builder mode");
+  g_bvh_mode = mode;
+  return RT_OK;
+}
+
+int rt_bvh_export(const float *vpos4, int64_t nverts, const uint32_t *idx, int64_t nidx,
+                  uint32_t *canon, int64_t *nnodes, uint32_t *perm_tri, int32_t *max_depth) {
+  if (!vpos4 || !idx || !nnodes || nverts <= 0 || nidx <= 0) return set_err(RT_E_INVALID, "bad mesh");
+  rth::BVHGpu b;
+  const unsigned want = (canon ? rth::kBvhCanon : 0u) | (perm_tri ? rth::kBvhPerm : 0u);
+  if (int rc = build_bvh(vpos4, nverts, idx, nidx, b, want)) return rc;
+  const int64_t n = canon ? (int64_t)b.canon.size() / 52 : b.host_nodes;
+  if (canon) {
+    if (*nnodes < n) return set_err(RT_E_INVALID, "buffer too small");
+    std::memcpy(canon, b.canon.data(), b.canon.size() * 4);
+  }
+  if (perm_tri) std::memcpy(perm_tri, b.perm_tri.data(), b.perm_tri.size() * 4);
+  if (max_depth) *max_depth = b.max_depth;
+  *nnodes = n;
+  return RT_OK;
+}
+
+// max over triangle slots of |e1| |e2| (float bits: the values are >= 0, so
+// their bit patterns order like them; NaN counts as +inf)
+__global__ void tri_edge_bound_kernel(const rtl::GTri *__restrict__ tris, uint32_t n, uint32_t *out) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  float m = 0.0f;
+  if (i < n) {
+    const float4 *q = reinterpret_cast<const float4 *>(tris + i);
+    const float4 b = q[1], c = q[2];
+    const float v = __builtin_sqrtf(b.x * b.x + b.y * b.y + b.z * b.z) *
+                    __builtin_sqrtf(c.x * c.x + c.y * c.y + c.z * c.z);
+    m = __builtin_isnan(v) ? kInf : v;
+  }
+  for (int off = 32; off > 0; off >>= 1) m = __builtin_fmaxf(m, __shfl_xor(m, off, 64));
+  if ((threadIdx.x & 63) == 0 && m > 0.0f) atomicMax(out, __float_as_uint(m));
+}
+
+// MeshDev::dmax2 of a mesh scene: (2^124 / (2 M))^2, M = max |e1| |e2| over its
+// triangles. A ray with dot(d, d) <= dmax2 has |d| <= 2^124 / (2 M) (up to a
+// few ulps), and tri_t's float det = e1 . (d x e2) is at most sqrt(2) |e1|
+// |e2| |d| (1 + 2^-24)^5 < 1.5 M |d| <= 0.75 x 2^124 in magnitude: inside the
+// range where rtm::rcp_rn is the division. M = 0 (no triangle with both edges)
+// leaves every direction; M = inf or NaN leaves none.
+float dmax2_of(uint32_t edge_bits) {
+  float M;
+  std::memcpy(&M, &edge_bits, 4);
+  if (M == 0.0f) return std::numeric_limits<float>::max();
+  if (!std::isfinite(M)) return 0.0f;
+  const double r = std::ldexp(1.0, 124) / (2.0 * (double)M * (1.0 + 1e-6));
+  const double r2 = r * r;
+  return r2 >= (double)std::numeric_limits<float>::max() ? std::numeric_limits<float>::max()
+                                                          : std::nextafter((float)r2, 0.0f);
+}
+int mesh_dmax2(rt_scene *s, uint32_t n_tris) {
+  s->dmax2 = 0.0f;
+  if (n_tris == 0) return RT_OK;
+  uint32_t *d = nullptr, h = 0;
+  HIP_TRY(hipMalloc(&d, 4));
+  hipError_t e = hipMemset(d, 0, 4);
+  if (e == hipSuccess) {
+    tri_edge_bound_kernel<<<(n_tris + 255) / 256, 256>>>(s->d_tris, n_tris, d);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpy(&h, d, 4, hipMemcpyDeviceToHost);
+  HIP_NOTE(hipFree(d));
+  if (e != hipSuccess) return set_err(RT_E_DEVICE, std::string("triangle edge bound: ") + hipGetErrorString(e));
+  s->dmax2 = dmax2_of(h);
+  return RT_OK;
+}
+
+int rt_scene_create_mesh(const float *vpos4, int64_t nverts, const uint32_t *idx, int64_t nidx,
+                         rt_scene **out) {
+  return rt_scene_create_mesh_ex(vpos4, nverts, idx, nidx, 0u, out);
+}
+
+int rt_scene_create_mesh_ex(const float *vpos4, int64_t nverts, const uint32_t *idx, int64_t nidx,
+                            uint32_t flags, rt_scene **out) {
+  if (!vpos4 || !idx || nverts <= 0 || nidx <= 0) return set_err(RT_E_INVALID, "empty mesh");
+  if (flags & ~RT_MESH_DYNAMIC) return set_err(RT_E_INVALID, "rt_scene_create_mesh_ex: unknown flags");
+  rth::BVHGpu b;
+  if (int rc = build_bvh(vpos4, nverts, idx, nidx, b, rth::kBvhTris | rth::kBvhDeviceTris)) return rc;
+  int32_t maxd = 8;
+  int rc = pick_maxd(b.max_depth, maxd);
+  if (rc) return rc;
+  rt_scene *s;
+  if ((rc = new_scene(&s))) return rc;
+  s->kind = RT_SCENE_MESH;
+  s->maxd = maxd;
+  s->root = b.root_word;
+  std::memcpy(s->root_box, b.root_box, sizeof(s->root_box));
+  if (!(b.root_word & rtl::kLeafBit) && b.root_word < b.nodes.size())
+    std::memcpy(s->root_child, b.nodes[b.root_word].box, sizeof(s->root_child));
+  s->host_nodes = b.host_nodes;
+  s->host_inner = b.host_inner;
+  s->bvh_depth = b.max_depth;
+  s->n_inner = (uint32_t)b.nodes.size();
+  if (b.dev_tris.p) {  // the device builder left the triangles on the device (with the zero pad)
+    s->dev_bytes += (int64_t)b.dev_tris.bytes;
+    s->d_tris = static_cast<rtl::GTri *>(b.dev_tris.take());
+  }
+  if ((rc = upload(&s->d_nodes, b.nodes.data(), b.nodes.size(), s->dev_bytes)) ||
+      (!s->d_tris && (rc = upload_padded(&s->d_tris, b.tris.data(), b.tris.size(), 8, s->dev_bytes))) ||
+      (rc = mesh_dmax2(s, b.n_tris))) {
+    rt_scene_destroy(s);
+    return rc;
+  }
+  s->n_tris = b.n_tris;
+  if (!b.nodes.empty())
+    for (uint32_t w : b.nodes[0].child) s->root_nchild += w != rtl::kInvalidChild;
+  if (flags & RT_MESH_DYNAMIC) {
+    const int64_t before = s->dev_bytes;
+    s->nverts = nverts;
+    s->level_first = rth::bvh_level_first(b.nodes);
+    if ((rc = upload(&s->d_idx, idx, (size_t)nidx, s->dev_bytes)) ||
+        (rc = upload(&s->d_vstage, (const float *)nullptr, 4 * (size_t)nverts, s->dev_bytes)) ||
+        (rc = upload(&s->d_edge, (const uint32_t *)nullptr, 1, s->dev_bytes)) || (rc = dynamic_host_words(s))) {
+      rt_scene_destroy(s);
+      return rc;
+    }
+    s->dyn_bytes = s->dev_bytes - before;
+    s->dynamic = true;
+  }
+  *out = s;
+  return RT_OK;
+}
+
+// The refit behind both update entries: d_vpos4 (device, on the scene's
+// device) is read in stream order on `stream`; returns after the constants
+// are back on the host.
+static int update_vertices_device(rt_scene *s, const float *d_vpos4, hipStream_t st) {
+  const rti::RefitArgs a{s->d_nodes, s->d_tris, s->root, d_vpos4, s->d_idx, s->level_first.data(),
+                         s->level_first.empty() ? 0 : (int32_t)s->level_first.size() - 1};
+  if (int rc = rti::refit_launch(a, st)) return rc;
+  // the constants the host keeps: the triangles' edge bound (dmax2) and, for
+  // an inner root, its eight child boxes (root_child, root_box)
+  const bool inner = a.levels > 0;
+  HIP_TRY(hipMemsetAsync(s->d_edge, 0, 4, st));
+  if (s->n_tris) {
+    tri_edge_bound_kernel<<<(s->n_tris + 255) / 256, 256, 0, st>>>(s->d_tris, s->n_tris, s->d_edge);
+    HIP_TRY(hipGetLastError());
+  }
+  if (inner) HIP_TRY(hipMemcpyAsync(s->h_refit, s->d_nodes[0].box, 192, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(s->h_refit + 48, s->d_edge, 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  if (inner) {
+    std::memcpy(s->root_child, s->h_refit, 192);
+    const float inf = std::numeric_limits<float>::infinity();
+    float mn[3] = {inf, inf, inf}, mx[3] = {-inf, -inf, -inf};
+    for (uint32_t c = 0; c < s->root_nchild; ++c) {  // bvh_layout's root box: the union over c = 0 .. nchild-1
+      for (int k = 0; k < 3; ++k) {
+        mn[k] = std::min(mn[k], s->root_child[6 * c + 2 * k]);
+        mx[k] = std::max(mx[k], s->root_child[6 * c + 2 * k + 1]);
+      }
+    }
+    for (int k = 0; k < 3; ++k) { s->root_box[k] = mn[k]; s->root_box[3 + k] = mx[k]; }
+  }
+  s->dmax2 = s->n_tris ? dmax2_of(s->h_refit[48]) : 0.0f;
+  ++s->version;
+  return RT_OK;
+}
+
+int rt_scene_create_grid(const uint32_t size[3], const float *values, rt_scene **out) {
+  if (!size || !values) return set_err(RT_E_INVALID, "NULL argument");
+  const uint64_t n = (uint64_t)size[0] * size[1] * size[2];
+  if (size[0] < 1 || size[1] < 1 || size[2] < 1 || n > (1ull << 32))
+    return set_err(RT_E_INVALID, "bad grid size");
+  rt_scene *s;
+  int rc = new_scene(&s);
+  if (rc) return rc;
+  s->kind = RT_SCENE_GRID;
+  s->size[0] = size[0]; s->size[1] = size[1]; s->size[2] = size[2];
+  if ((uint64_t)n * 4 <= kGridLinearMaxBytes && !(g_grid_force & 1)) {  // fits one XCD's L2: the reference layout
+    if ((rc = upload(&s->d_vals, values, (size_t)n, s->dev_bytes))) {
+      rt_scene_destroy(s);
+      return rc;
+    }
+    *out = s;
+    return RT_OK;
+  }
+  const uint64_t nb = grid_bricked_samples(size);
+  if (nb >= (1ull << 32)) {
+    rt_scene_destroy(s);
+    return set_err(RT_E_INVALID, "bad grid size");
+  }
+  s->grid_bricked = true;
+  float *d_ref = nullptr;  // the reference array, staged for the device-side bricking
+  if ((rc = upload(&d_ref, values, (size_t)n, s->dev_bytes)) ||
+      (rc = upload(&s->d_vals, (const float *)nullptr, (size_t)nb, s->dev_bytes))) {
+    if (d_ref) HIP_NOTE(hipFree(d_ref));
+    rt_scene_destroy(s);
+    return rc;
+  }
+  s->dev_bytes -= (int64_t)(n * sizeof(float));
+  brick_kernel<<<(unsigned)((nb + 255) / 256), 256>>>(d_ref, s->d_vals, size[0], size[1], size[2], nb);
+  const hipError_t e1 = hipGetLastError(), e2 = hipDeviceSynchronize(), e3 = hipFree(d_ref);
+  if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess) {
+    rt_scene_destroy(s);
+    return set_err(RT_E_DEVICE, std::string("grid bricking: ") +
+                                    hipGetErrorString(e1 != hipSuccess ? e1 : e2 != hipSuccess ? e2 : e3));
+  }
+  *out = s;
+  return RT_OK;
+}
+
+int rt_scene_create_octree(const void *nodes36, int64_t count, rt_scene **out) {
+  if (!nodes36 || count <= 0) return set_err(RT_E_INVALID, "empty octree");
+  rth::OctGpu g;
+  std::string err;
+  if (!rth::flatten_octree((const uint8_t *)nodes36, count, g, err)) return set_err(RT_E_INVALID, err);
+  int32_t maxd = 8;
+  int rc = pick_maxd(g.max_depth, maxd);
+  if (rc) return rc;
+  rt_scene *s;
+  if ((rc = new_scene(&s))) return rc;
+  s->kind = RT_SCENE_OCTREE;
+  s->maxd = maxd;
+  s->oct_depth = g.max_depth;
+  if ((rc = upload(&s->d_child, g.child.data(), g.child.size(), s->dev_bytes)) ||
+      (rc = upload(&s->d_ovals, g.vals.data(), g.vals.size(), s->dev_bytes))) {
+    rt_scene_destroy(s);
+    return rc;
+  }
+  *out = s;
+  return RT_OK;
+}
+
+int rt_scene_replicate(const rt_scene *src, int device, rt_scene **out) {
+  if (!src || !out) return set_err(RT_E_INVALID, "bad arguments");
+  if (int rc = no_instanced(src, "rt_scene_replicate")) return rc;
+  *out = nullptr;
+  int ndev = 0;
+  HIP_TRY(hipGetDeviceCount(&ndev));
+  if (device < 0 || device >= ndev) return set_err(RT_E_INVALID, "rt_scene_replicate: no such device");
+  int prev = 0;
+  HIP_TRY(hipGetDevice(&prev));
+  HIP_TRY(hipSetDevice(device));
+  rt_scene *s = new rt_scene();
+  // the scene's description (kind, tree shape, plane, kernel instantiation)
+  s->kind = src->kind;
+  s->device = device;
+  s->maxd = src->maxd;
+  s->root = src->root;
+  std::memcpy(s->root_box, src->root_box, sizeof s->root_box);
+  std::memcpy(s->root_child, src->root_child, sizeof s->root_child);
+  s->host_nodes = src->host_nodes;
+  s->host_inner = src->host_inner;
+  s->n_inner = src->n_inner;
+  s->dmax2 = src->dmax2;
+  s->bvh_depth = src->bvh_depth;
+  std::memcpy(s->size, src->size, sizeof s->size);
+  s->grid_bricked = src->grid_bricked;
+  s->oct_depth = src->oct_depth;
+  s->plane = src->plane;
+  s->n_tris = src->n_tris;
+  s->root_nchild = src->root_nchild;
+  s->version = src->version;
+  s->dev_bytes = src->dev_bytes - src->dyn_bytes;  // (a plain snapshot: not dynamic)
+  s->sched_on = src->sched_on;
+  s->coop = src->coop;
+  s->pump_on = src->pump_on;
+  // the device arrays, copied device to device (over xGMI between GPUs)
+  void *const from[] = {src->d_nodes, src->d_tris, src->d_vals, src->d_child, src->d_ovals};
+  void **to[] = {(void **)&s->d_nodes, (void **)&s->d_tris, (void **)&s->d_vals, (void **)&s->d_child,
+                 (void **)&s->d_ovals};
+  hipError_t e = hipSuccess;
+  const char *step = "";
+  for (int i = 0; i < 5 && e == hipSuccess; ++i) {
+    if (!from[i]) continue;
+    size_t bytes = 0;
+    if ((e = hipMemPtrGetInfo(from[i], &bytes)) != hipSuccess) { step = "hipMemPtrGetInfo"; break; }
+    if ((e = hipMalloc(to[i], bytes)) != hipSuccess) { step = "hipMalloc"; break; }
+    if ((e = hipMemcpyPeer(*to[i], device, from[i], src->device, bytes)) != hipSuccess) step = "hipMemcpyPeer";
+  }
+  HIP_NOTE(hipSetDevice(prev));
+  if (e != hipSuccess) {
+    rt_scene_destroy(s);
+    return set_err(RT_E_DEVICE, std::string("rt_scene_replicate: ") + step + ": " + hipGetErrorString(e));
+  }
+  *out = s;
+  return RT_OK;
+}
+
+int rt_scene_device(const rt_scene *s) { return s ? s->device : RT_E_INVALID; }
+
+static int check_update(const rt_scene *s, const float *vpos4, int64_t nverts, const char *who) {
+  if (!s) return set_err(RT_E_INVALID, std::string(who) + ": scene is NULL");
+  if (!vpos4) return set_err(RT_E_INVALID, std::string(who) + ": vertex pointer is NULL");
+  if (nverts <= 0) return set_err(RT_E_INVALID, std::string(who) + ": nverts must be positive");
+  if (s->kind != RT_SCENE_MESH) return set_err(RT_E_STATE, std::string(who) + ": not a mesh scene");
+  if (!s->dynamic)
+    return set_err(RT_E_STATE, std::string(who) + ": the mesh was not created with RT_MESH_DYNAMIC");
+  if (nverts != s->nverts)
+    return set_err(RT_E_INVALID, std::string(who) + ": nverts is " + std::to_string(nverts) + ", the mesh was created with " +
+                                     std::to_string(s->nverts));
+  return RT_OK;
+}
+
+// ---- instanced scenes (include/rtamd.h; kernels in rt_instances.hip) -------
+namespace {
+// one rt_instance -> its device record; `who` names the entry in the message
+int instance_record(const rt_instance &in, int32_t nblas, int64_t index, const char *who, rti::InstRec &r) {
+  const std::string at = std::string(who) + ": instance " + std::to_string(index);
+  if (in.blas < 0 || in.blas >= nblas) return set_err(RT_E_INVALID, at + ": blas index out of range");
+  if (in.flags & ~RT_INSTANCE_DISABLED) return set_err(RT_E_INVALID, at + ": unknown flag bits");
+  if (!rti::affine_inverse(in.xform, r.m))
+    return set_err(RT_E_INVALID, at + ": the matrix is singular or has a non-finite entry");
+  r.blas = in.blas;
+  r.flags = in.flags;
+  r.skipped = 0;
+  r.pad = 0;
+  return RT_OK;
+}
+
+int instance_range(const rt_scene *s, int32_t first, int32_t count, const char *who) {
+  if (!s) return set_err(RT_E_INVALID, std::string(who) + ": scene is NULL");
+  if (s->kind != RT_SCENE_INSTANCED) return set_err(RT_E_STATE, std::string(who) + ": not an instanced scene");
+  if (first < 0 || count < 0 || (int64_t)first + count > s->ninst)
+    return set_err(RT_E_INVALID, std::string(who) + ": range outside the scene's " + std::to_string(s->ninst) +
+                                     " instances");
+  return RT_OK;
+}
+}  // namespace
+
+int rt_scene_create_instanced(rt_scene *const *blas, int32_t nblas, const rt_instance *inst, int32_t ninst,
+                              rt_scene **out) {
+  const char *who = "rt_scene_create_instanced";
+  if (!blas || !inst || !out) return set_err(RT_E_INVALID, std::string(who) + ": NULL argument");
+  *out = nullptr;
+  if (nblas < 1 || ninst < 1) return set_err(RT_E_INVALID, std::string(who) + ": nblas and ninst must be at least 1");
+  int dev = 0;
+  HIP_TRY(hipGetDevice(&dev));
+  int32_t maxd = 1;
+  for (int32_t j = 0; j < nblas; ++j) {
+    if (!blas[j]) return set_err(RT_E_INVALID, std::string(who) + ": BLAS " + std::to_string(j) + " is NULL");
+    if (blas[j]->kind != RT_SCENE_MESH)
+      return set_err(RT_E_STATE, std::string(who) + ": BLAS " + std::to_string(j) + " is not a mesh scene");
+    if (blas[j]->device != dev)
+      return set_err(RT_E_INVALID, std::string(who) + ": BLAS " + std::to_string(j) + " lives on device " +
+                                       std::to_string(blas[j]->device) + ", the current device is " + std::to_string(dev));
+    maxd = std::max(maxd, blas[j]->maxd);
+  }
+  std::vector<rti::InstRec> recs((size_t)ninst);
+  for (int32_t i = 0; i < ninst; ++i)
+    if (int rc = instance_record(inst[i], nblas, i, who, recs[(size_t)i])) return rc;
+  std::vector<MeshDev> tab;
+  for (int32_t j = 0; j < nblas; ++j) tab.push_back(mesh_dev(blas[j]));
+  rt_scene *s = nullptr;
+  if (int rc = new_scene(&s)) return rc;
+  s->kind = RT_SCENE_INSTANCED;
+  s->maxd = maxd;  // the LDS stack of the deepest bottom-level tree
+  s->ninst = ninst;
+  s->blas.assign(blas, blas + nblas);
+  for (int32_t j = 0; j < nblas; ++j) s->blas_seen.push_back(blas[j]->version);
+  int rc = upload(&s->d_inst, recs.data(), recs.size(), s->dev_bytes);
+  if (!rc) rc = upload(&s->d_blas, tab.data(), tab.size(), s->dev_bytes);
+  if (rc) {
+    rt_scene_destroy(s);
+    return rc;
+  }
+  *out = s;
+  return RT_OK;
+}
+
+int rt_scene_update_instances(rt_scene *s, int32_t first, int32_t count, const rt_instance *inst) {
+  const char *who = "rt_scene_update_instances";
+  if (int rc = instance_range(s, first, count, who)) return rc;
+  if (!inst) return set_err(RT_E_INVALID, std::string(who) + ": instance pointer is NULL");
+  if (count == 0) return RT_OK;
+  std::vector<rti::InstRec> recs((size_t)count);
+  for (int32_t i = 0; i < count; ++i)
+    if (int rc = instance_record(inst[i], (int32_t)s->blas.size(), (int64_t)first + i, who, recs[(size_t)i])) return rc;
+  int prev = 0;
+  HIP_TRY(hipGetDevice(&prev));
+  HIP_TRY(hipSetDevice(s->device));
+  const hipError_t e = rtdma::h2d(s->d_inst + first, recs.data(), recs.size() * sizeof(rti::InstRec), nullptr);
+  HIP_NOTE(hipSetDevice(prev));
+  if (e != hipSuccess) return set_err(RT_E_DEVICE, rterr::hip_fail("rt_scene_update_instances: upload", e));
+  return RT_OK;
+}
+
+int rt_scene_update_instances_device(rt_scene *s, int32_t first, int32_t count, const float *d_xform12,
+                                     void *stream) {
+  const char *who = "rt_scene_update_instances_device";
+  if (int rc = instance_range(s, first, count, who)) return rc;
+  if (!d_xform12) return set_err(RT_E_INVALID, std::string(who) + ": matrix pointer is NULL");
+  if (count == 0) return RT_OK;
+  return rti::pose_launch(s->d_inst, first, count, d_xform12, (hipStream_t)stream);
+}
+
+int rt_scene_get_instances(const rt_scene *s, int32_t first, int32_t count, rt_instance *inst, float *inv12,
+                           uint32_t *skipped) {
+  if (int rc = instance_range(s, first, count, "rt_scene_get_instances")) return rc;
+  if (count == 0) return RT_OK;
+  std::vector<rti::InstRec> recs((size_t)count);
+  int prev = 0;
+  HIP_TRY(hipGetDevice(&prev));
+  HIP_TRY(hipSetDevice(s->device));
+  hipError_t e = hipDeviceSynchronize();  // pose updates queued on any stream
+  if (e == hipSuccess) e = rtdma::d2h(recs.data(), s->d_inst + first, recs.size() * sizeof(rti::InstRec), nullptr);
+  HIP_NOTE(hipSetDevice(prev));
+  if (e != hipSuccess) return set_err(RT_E_DEVICE, rterr::hip_fail("rt_scene_get_instances", e));
+  for (int32_t i = 0; i < count; ++i) {
+    const rti::InstRec &r = recs[(size_t)i];
+    if (inst) {
+      inst[i].blas = r.blas;
+      inst[i].flags = r.flags;
+      for (float &x : inst[i].xform) x = 0.0f;
+      if (!r.skipped) (void)rti::affine_inverse(r.m, inst[i].xform);
+    }
+    if (inv12) std::memcpy(inv12 + 12 * (size_t)i, r.m, sizeof r.m);
+    if (skipped) skipped[i] = r.skipped;
+  }
+  return RT_OK;
+}
+
+int rt_scene_update_vertices_device(rt_scene *s, const float *d_vpos4, int64_t nverts, void *stream) {
+  if (int rc = check_update(s, d_vpos4, nverts, "rt_scene_update_vertices_device")) return rc;
+  return update_vertices_device(s, d_vpos4, (hipStream_t)stream);
+}
+
+int rt_scene_update_vertices(rt_scene *s, const float *vpos4, int64_t nverts) {
+  if (int rc = check_update(s, vpos4, nverts, "rt_scene_update_vertices")) return rc;
+  int prev = 0;
+  HIP_TRY(hipGetDevice(&prev));
+  HIP_TRY(hipSetDevice(s->device));
+  int rc = RT_OK;
+  if (const hipError_t e = rtdma::h2d(s->d_vstage, vpos4, 16 * (size_t)nverts, nullptr))
+    rc = set_err(RT_E_DEVICE, rterr::hip_fail("rt_scene_update_vertices: vertex upload", e));
+  if (!rc) rc = update_vertices_device(s, s->d_vstage, nullptr);
+  HIP_NOTE(hipSetDevice(prev));
+  return rc;
+}
+
+// Diagnostic (not part of include/rtamd.h): a mesh scene's device tree, as it
+// is now: n_inner GNode records (224 bytes each) and n_tris GTri records (48
+// bytes each). Two-call protocol: with nodes224 = tris48 = NULL only the counts
+// are returned; else *n_inner / *n_tris are the buffers' capacities.
+int rtx_scene_mesh_download(rt_scene *s, void *nodes224, int64_t *n_inner, void *tris48, int64_t *n_tris) {
+  if (!s || !n_inner || !n_tris) return set_err(RT_E_INVALID, "rtx_scene_mesh_download: NULL argument");
+  if (s->kind != RT_SCENE_MESH) return set_err(RT_E_STATE, "rtx_scene_mesh_download: not a mesh scene");
+  if (nodes224 || tris48) {
+    if (!nodes224 || !tris48 || *n_inner < (int64_t)s->n_inner || *n_tris < (int64_t)s->n_tris)
+      return set_err(RT_E_INVALID, "rtx_scene_mesh_download: buffers too small");
+    int prev = 0;
+    HIP_TRY(hipGetDevice(&prev));
+    HIP_TRY(hipSetDevice(s->device));
+    hipError_t e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = rtdma::d2h(nodes224, s->d_nodes, (size_t)s->n_inner * sizeof(rtl::GNode), nullptr);
+    if (e == hipSuccess) e = rtdma::d2h(tris48, s->d_tris, (size_t)s->n_tris * sizeof(rtl::GTri), nullptr);
+    HIP_NOTE(hipSetDevice(prev));
+    if (e != hipSuccess) return set_err(RT_E_DEVICE, rterr::hip_fail("rtx_scene_mesh_download", e));
+  }
+  *n_inner = s->n_inner;
+  *n_tris = s->n_tris;
+  return RT_OK;
+}
+
+// Diagnostic (not part of include/rtamd.h): the constants the host keeps of a
+// mesh scene: root_box[6], the root's child boxes root_child[48], dmax2.
+int rtx_scene_mesh_constants(const rt_scene *s, float root_box[6], float root_child[48], float *dmax2) {
+  if (!s) return set_err(RT_E_INVALID, "rtx_scene_mesh_constants: scene is NULL");
+  if (s->kind != RT_SCENE_MESH) return set_err(RT_E_STATE, "rtx_scene_mesh_constants: not a mesh scene");
+  if (root_box) std::memcpy(root_box, s->root_box, sizeof s->root_box);
+  if (root_child) std::memcpy(root_child, s->root_child, sizeof s->root_child);
+  if (dmax2) *dmax2 = s->dmax2;
+  return RT_OK;
+}
+
+int rt_scene_get_plane(const rt_scene *s, int *enabled, float normal[3], float *offset) {
+  if (!s) return set_err(RT_E_INVALID, "scene is NULL");
+  if (enabled) *enabled = s->plane.on;
+  if (normal) { normal[0] = s->plane.n.x; normal[1] = s->plane.n.y; normal[2] = s->plane.n.z; }
+  if (offset) *offset = s->plane.off;
+  return RT_OK;
+}
+
+int rt_scene_set_plane(rt_scene *s, int enabled, const float normal[3], float offset) {
+  if (!s) return set_err(RT_E_INVALID, "scene is NULL");
+  PlaneDev &p = s->plane;
+  p.on = enabled ? 1 : 0;
+  if (!enabled) return RT_OK;
+  if (!normal) return set_err(RT_E_INVALID, "normal is NULL");
+  // Plane(normal, offset) + recalcBasis (raytracing.hpp:121-124, 169-179)
+  const float n[3] = {normal[0], normal[1], normal[2]};
+  const float a[3] = {std::fabs(n[0]), std::fabs(n[1]), std::fabs(n[2])};
+  float b1[3];
+  if (a[0] > a[1] && a[0] > a[2]) { b1[0] = n[1]; b1[1] = -n[0]; b1[2] = 0; }
+  else { b1[0] = 0; b1[1] = n[2]; b1[2] = -n[1]; }
+  auto nrm = [](float v[3]) {
+    const float l = std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
+    v[0] = v[0] / l; v[1] = v[1] / l; v[2] = v[2] / l;
+  };
+  nrm(b1);
+  float b2[3] = {b1[1] * n[2] - b1[2] * n[1], b1[2] * n[0] - b1[0] * n[2], b1[0] * n[1] - b1[1] * n[0]};
+  nrm(b2);
+  p.n = f3{n[0], n[1], n[2]};
+  p.off = offset;
+  p.b1 = f3{b1[0], b1[1], b1[2]};
+  p.b2 = f3{b2[0], b2[1], b2[2]};
+  return RT_OK;
+}
+
+int rt_scene_kind(const rt_scene *s) { return s ? s->kind : RT_E_INVALID; }
+int64_t rt_scene_device_bytes(const rt_scene *s) { return s ? s->dev_bytes : 0; }
+
+int rt_scene_bvh_stats(const rt_scene *s, int64_t *nodes, int64_t *inner, int32_t *max_depth) {
+  if (!s) return set_err(RT_E_INVALID, "scene is NULL");
+  if (s->kind != RT_SCENE_MESH && s->kind != RT_SCENE_OCTREE) return set_err(RT_E_STATE, "not a tree scene");
+  if (nodes) *nodes = s->host_nodes;
+  if (inner) *inner = s->host_inner;
+  if (max_depth) *max_depth = s->kind == RT_SCENE_MESH ? s->bvh_depth : s->oct_depth;
+  return RT_OK;
+}
+
+int rt_scene_destroy(rt_scene *s) {
+  if (!s) return RT_OK;
+  int prev = 0;
+  HIP_NOTE(hipGetDevice(&prev));
+  HIP_NOTE(hipSetDevice(s->device));
+  // the scene's own copy/render streams drain before anything they may still
+  // read or write is freed (rt_render returns only after both, but a failed
+  // call or a caller-stream launch may not have)
+  for (hipStream_t x : s->xs)
+    if (x) HIP_NOTE(hipStreamSynchronize(x));
+  if (s->sched_os) HIP_NOTE(hipStreamSynchronize(s->sched_os));
+  void *ptrs[] = {s->d_nodes, s->d_tris, s->d_vals, s->d_child, s->d_ovals, s->d_color, s->d_t,
+                  s->d_cost[0], s->d_order[0], s->d_cost[1], s->d_order[1], s->d_idx, s->d_vstage, s->d_edge, s->d_inst, s->d_blas};
+  for (void *p : ptrs)
+    if (p) HIP_NOTE(hipFree(p));
+  if (s->h_refit) HIP_NOTE(hipHostFree(s->h_refit));
+  for (hipEvent_t e : s->ord_ev)
+    if (e) HIP_NOTE(hipEventDestroy(e));
+  if (s->frame_ev) HIP_NOTE(hipEventDestroy(s->frame_ev));
+  if (s->sched_os) {
+    rterr::stream_remove(s->sched_os);
+    HIP_NOTE(hipStreamDestroy(s->sched_os));
+  }
+  if (s->ev0) HIP_NOTE(hipEventDestroy(s->ev0));
+  if (s->ev1) HIP_NOTE(hipEventDestroy(s->ev1));
+  if (s->ev_host) HIP_NOTE(hipEventDestroy(s->ev_host));
+  if (s->xev) HIP_NOTE(hipEventDestroy(s->xev));
+  if (s->d_hit_box) HIP_NOTE(hipFree(s->d_hit_box));
+  if (s->h_hit_box) HIP_NOTE(hipHostFree(s->h_hit_box));
+  if (s->d_row_span) HIP_NOTE(hipFree(s->d_row_span));
+  if (s->h_row_span) HIP_NOTE(hipHostFree(s->h_row_span));
+  s->stage.release();
+  for (hipStream_t x : s->xs)
+    if (x) {
+      rterr::stream_remove(x);
+      HIP_NOTE(hipStreamDestroy(x));
+    }
+  HIP_NOTE(hipSetDevice(prev));
+  delete s;
+  return RT_OK;
+}
+
+// Builder of this thread's last BVH: 1 host, 2 device, 3 host after a failed
+// device build (AUTO mode falls back; see rtx_bvh_inject_failure)
+int rtx_bvh_last_builder(void) { return t_bvh_last; }
+
+// Diagnostic: force grid layouts / address paths (g_grid_force bits). Not part
+// of include/rtamd.h.
+int rtx_set_grid_force(int flags) {
+  if (flags < 0 || flags > 3) return set_err(RT_E_INVALID, "grid force flags must be 0..3");
+  g_grid_force = flags;
+  return RT_OK;
+}
+
+// Diagnostic (not part of include/rtamd.h; host only, touches no device): the
+// kernel template arguments the scene dispatch (rt_dispatch.h) picks for a
+// scene of `kind` with `maxd` stack slots and, for a grid, the launch mode
+// `gmode`: out[0] = the adapter's scene kind, out[1] = the slot count N,
+// out[2] = the adapter's variant (GridS: kMode, OctS: PACK, MeshS: 0).
+// RT_E_STATE for a kind without an adapter (an unknown one, or an instanced
+// scene, whose entries branch off ahead of the dispatch).
+int rtx_dispatch_probe(int kind, int maxd, int gmode, int out[3]) {
+  if (!out) return set_err(RT_E_INVALID, "rtx_dispatch_probe: out is NULL");
+  if (!dispatch_types(kind, maxd, gmode, [&](auto adapter, auto slots) {
+        using A = typename decltype(adapter)::type;
+        out[0] = AdapterInfo<A>::kKind;
+        out[1] = decltype(slots)::value;
+        out[2] = AdapterInfo<A>::kVariant;
+      }))
+    return set_err(RT_E_STATE, "rtx_dispatch_probe: no scene adapter for this scene kind");
+  return RT_OK;
+}
+
+}  // extern "C"
+
+namespace rti {
+
+uint64_t scene_version(const rt_scene *s) { return s ? s->version : 0; }
+
+// A replica (rt_scene_replicate) of mesh scene `src` brought up to src's last
+// update: nodes and triangles copied device to device (the sizes never
+// change), the three host constants taken over. Blocking; the caller has
+// drained the streams that use the replica.
+int scene_refresh_replica(rt_scene *rep, const rt_scene *src) {
+  if (!rep || !src || rep->kind != src->kind) return set_err(RT_E_INVALID, "scene_refresh_replica: bad arguments");
+  if (rep->version == src->version || src->kind != RT_SCENE_MESH) return RT_OK;
+  if (rep->n_inner != src->n_inner || rep->n_tris != src->n_tris)
+    return set_err(RT_E_STATE, "scene_refresh_replica: the replica is not of this scene");
+  if (src->n_inner)
+    HIP_TRY(hipMemcpyPeer(rep->d_nodes, rep->device, src->d_nodes, src->device, (size_t)src->n_inner * sizeof(rtl::GNode)));
+  if (src->n_tris)
+    HIP_TRY(hipMemcpyPeer(rep->d_tris, rep->device, src->d_tris, src->device, (size_t)src->n_tris * sizeof(rtl::GTri)));
+  std::memcpy(rep->root_box, src->root_box, sizeof rep->root_box);
+  std::memcpy(rep->root_child, src->root_child, sizeof rep->root_child);
+  rep->dmax2 = src->dmax2;
+  rep->version = src->version;
+  return RT_OK;
+}
+
+}  // namespace rti

@@ -181,6 +181,9 @@ _XSIGS = {
     # (shared node fetches, expansions of either form)
     "rtx_count_share": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_uint32,
                                   C.c_void_p]),
+    # the scene dispatch's mapping (scene kind, stack slots, grid mode) ->
+    # kernel template arguments, host only
+    "rtx_dispatch_probe": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p]),
 }
 
 
