@@ -237,9 +237,12 @@ int rt_scene_get_plane(const rt_scene *s, int *enabled, float normal[3], float *
  * (rt_scene_set_plane, world space) takes part exactly as for the other kinds.
  * RT_RAYS_ANY_HIT is the OR over the instances of the BLAS any hit on
  * (o', d', tNear, tFar), stopping at the first hit; it equals the closest-hit
- * query's flag. There is no top-level tree: every ray
- * visits every instance, and skips one only by the traversal's own root-box
- * test on the transformed ray, which cannot change an answer.
+ * query's flag. A scene created by this entry is a flat
+ * list: every ray visits every instance, and skips one only by the traversal's
+ * own root-box test on the transformed ray, which cannot change an answer.
+ * Hundreds of instances want the top-level tree of RT_INSTANCED_TLAS
+ * (rt_scene_create_instanced_ex below), whose world-box test is part of that
+ * mode's definition.
  *
  * rt_trace_rays_device and rt_intersect_rays accept the kind with all their
  * argument rules; rt_scene_kind, rt_scene_device, rt_scene_device_bytes (the
@@ -274,6 +277,61 @@ int rt_affine_inverse(const float xform[12], float inv[12]);
  * device, or a matrix rt_affine_inverse refuses. */
 int rt_scene_create_instanced(rt_scene *const *blas, int32_t nblas, const rt_instance *inst, int32_t ninst,
                               rt_scene **out);
+/* ---- RT_INSTANCED_TLAS: a top-level tree over the instances' world boxes ---
+ * rt_scene_create_instanced_ex with flags = 0 is rt_scene_create_instanced;
+ * unknown flag bits return RT_E_INVALID. For a scene created with
+ * RT_INSTANCED_TLAS the loop above gains ONE line and nothing else changes:
+ *     for i = 0 .. K-1 in index order, skipping disabled (and skipped) instances:
+ *         tf_i = best < tFar ? best : tFar
+ *         if not box_pass(wbox_i, o, d, tNear, tf_i): continue      (on the WORLD ray)
+ *         ... transform, BLAS intersect under tf_i, ties keep the lower index: as above
+ * RT_RAYS_ANY_HIT is the OR over the instances with box_pass(wbox_i, o, d,
+ * tNear, tFar) of the BLAS any hit; box_pass is monotone in tFar, so it still
+ * equals the closest-hit flag. The test is part of the
+ * definition, not an approximation of the flat list's answer: the oracle of the
+ * tests runs the same test. Both functions are plain float operations in the
+ * written order, never fused, the same code on the host and on the device:
+ *   box_pass(b = lo.xyz hi.xyz, o, d, tn, tf): false when b[0] > b[3] (the one
+ *     encoding of the empty box: lo = +inf, hi = -inf). Otherwise true when a
+ *     component of 1/d is not finite (a ray with a zero direction component
+ *     visits every non-empty instance, as in the flat list). Otherwise, with
+ *     t1 = (lo - o) * (1/d), t2 = (hi - o) * (1/d), mn(a, b) = a < b ? a : b,
+ *     mx(a, b) = a > b ? a : b:
+ *       tMin = mx(mx(mn(t1x, t2x), mx(mn(t1y, t2y), mn(t1z, t2z))), tn)
+ *       tMax = mn(mn(mx(t1x, t2x), mn(mx(t1y, t2y), mx(t1z, t2z))), tf)
+ *       pass = !(tMax < 0 || tMin > tMax)
+ *     (the BVH traversal's own root-box test, on a world box).
+ *   wbox_i = rt_instance_world_box(xform_i, the BLAS's root box): for corner
+ *     c = 0..7 (bit a of c picks hi on axis a) p[r] = ((x[4r]*c.x + x[4r+1]*c.y)
+ *     + x[4r+2]*c.z) + x[4r+3]; lo and hi folded in corner order by mn and mx;
+ *     then m = max_r mx(|lo_r|, |hi_r|) + max_r (hi_r - lo_r), e = 2^-16 * m and
+ *     wbox = (lo - e, hi + e). The pad is a definition, not a proof: 128 ulps of
+ *     the box's own scale, where the two tests' roundings are a few ulps. An
+ *     instance of a BLAS that is one leaf (no root box) has (-inf, +inf) on
+ *     every axis; a disabled or skipped instance and an instance of an empty
+ *     BLAS have the empty box.
+ * The tree is implicit: P = the smallest power of two >= K leaves in index
+ * order (leaf P + i = wbox_i, empty for i >= K), inner node n = the exact
+ * min / max of nodes 2n and 2n + 1, which the monotone test lets a ray skip
+ * exactly. Depth first, left to right, it yields a ray's candidates in index
+ * order. ITS QUALITY IS THE SPATIAL COHERENCE OF THE CALLER'S INDEX ORDER
+ * (INTEGRATION.md section 6c). The device holds the nodes (2P x 32 bytes) and
+ * the object-to-world matrices (K x 48 bytes) besides the two tables;
+ * rt_scene_device_bytes counts them. The boxes and the tree are recomputed on
+ * the device: at creation, by rt_scene_update_instances (done on return), by
+ * rt_scene_update_instances_device (queued on its stream behind the pose
+ * kernel: still no allocation, no copy, no host wait) and by a trace that
+ * finds a refitted BLAS (behind the rewritten table entry, on its stream). */
+#define RT_INSTANCED_TLAS 1u
+int rt_scene_create_instanced_ex(rt_scene *const *blas, int32_t nblas, const rt_instance *inst, int32_t ninst,
+                                 uint32_t flags, rt_scene **out);
+/* Host-only: the definition of an instance's world box (above). */
+int rt_instance_world_box(const float xform[12], const float obox[6], float wbox[6]);
+/* The tree as the device holds it, after one device synchronisation:
+ * leaf_boxes[6 i ..] = wbox_i for i < K, node_boxes[6 n ..] for n < 2P (node 0
+ * is not used: zeros), *leaves = P. Any output may be NULL. RT_E_STATE for a
+ * scene without a top-level tree. */
+int rt_scene_get_tlas(const rt_scene *s, float *leaf_boxes, float *node_boxes, int32_t *leaves);
 /* Replace instances first .. first + count - 1 from a host buffer (blas, flags
  * and pose); validated as at creation, and a refused call leaves the scene
  * unchanged. The records are copied to the device before the call returns. */

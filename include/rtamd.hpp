@@ -283,11 +283,15 @@ inline void loadSDFOctree(SDFOctree &o, const std::string &path) {  // octree_ra
 // BLAS scenes are not owned and must outlive this scene.
 class InstancedScene : public IScene {
  public:
-  void perform(const std::vector<const BVHBuilder *> &blas, const std::vector<rt_instance> &instances) {
+  // flags: 0, or RT_INSTANCED_TLAS for a top-level tree over the instances'
+  // world boxes (hundreds of instances; the index order should be spatial)
+  void perform(const std::vector<const BVHBuilder *> &blas, const std::vector<rt_instance> &instances,
+               uint32_t flags = 0) {
     std::vector<rt_scene *> h;
     for (const BVHBuilder *b : blas) h.push_back(b ? b->handle() : nullptr);
     rt_scene *s = nullptr;
-    check(rt_scene_create_instanced(h.data(), (int32_t)h.size(), instances.data(), (int32_t)instances.size(), &s));
+    check(rt_scene_create_instanced_ex(h.data(), (int32_t)h.size(), instances.data(), (int32_t)instances.size(), flags,
+                                       &s));
     reset(s);
     count_ = (int32_t)instances.size();
   }

@@ -2159,9 +2159,16 @@ int launch_trace(rt_scene *s, const rt_ray_batch &b, int mode, hipStream_t strea
       if (s->blas[j]->version == s->blas_seen[j]) continue;
       if (int rc = rti::blas_entry_launch(s->d_blas + j, mesh_dev(s->blas[j]), stream)) return rc;
       s->blas_seen[j] = s->blas[j]->version;
+      if (!s->d_tlas) continue;
+      // its root box moved: that BLAS's leaves of the top-level tree and the
+      // tree above them, behind the entry
+      const rti::TlasArgs t = rti::tlas_args(s);
+      if (int rc = rti::tlas_boxes_launch(t, 0, s->ninst, nullptr, (int32_t)j, stream)) return rc;
+      if (int rc = rti::tlas_refit_launch(t, stream)) return rc;
     }
-    return rti::trace_instances_launch(rti::InstArgs{s->d_inst, s->d_blas, s->ninst, s->maxd}, s->plane, b, mode,
-                                       stream);
+    const rti::InstArgs a{s->d_inst, s->d_blas, s->ninst, s->maxd, s->d_tlas, s->tlas_leaves};
+    return s->d_tlas ? rti::trace_tlas_launch(a, s->plane, b, mode, stream)
+                     : rti::trace_instances_launch(a, s->plane, b, mode, stream);
   }
   if (!dispatch_scene(s, [&](const auto &sc, auto slots) {
         launch_trace_t<std::decay_t<decltype(sc)>, decltype(slots)::value>(sc, s->plane, b, mode, stream);

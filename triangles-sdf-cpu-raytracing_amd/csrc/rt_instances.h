@@ -8,6 +8,7 @@
 
 #include "../../include/rtamd.h"
 #include "rt_scenes.h"
+#include "rt_tlas.h"
 
 namespace rti {
 
@@ -60,6 +61,10 @@ struct InstArgs {
   const rtd::MeshDev *blas;
   int32_t ninst;
   int32_t maxd;
+  // a scene created with RT_INSTANCED_TLAS: its tree (rt_tlas.h) and the
+  // tree's leaf count P; NULL / 0 for the flat list
+  const rtt::TNode *tlas = nullptr;
+  int32_t tlas_leaves = 0;
 };
 // mode: kRaysAny / kRaysClosest / kRaysNormal (rt_shade.h). Only launches.
 int trace_instances_launch(const InstArgs &a, const rtd::PlaneDev &pl, const rt_ray_batch &b, int mode,
@@ -70,5 +75,27 @@ int blas_entry_launch(rtd::MeshDev *entry, const rtd::MeshDev &md, hipStream_t s
 // inst[first + j].m = affine_inverse(d_xform12 + 12 j) for j < count, one
 // matrix per lane; blas and flags stay. Only launches.
 int pose_launch(InstRec *inst, int32_t first, int32_t count, const float *d_xform12, hipStream_t st);
+
+// ---- rt_tlas.hip: scenes created with RT_INSTANCED_TLAS ---------------------
+// the trace through the top-level tree (a.tlas set); as trace_instances_launch
+int trace_tlas_launch(const InstArgs &a, const rtd::PlaneDev &pl, const rt_ray_batch &b, int mode, hipStream_t st);
+// What maintains the tree: its nodes (2 * leaves records), the scene's
+// object-to-world matrices (12 floats per instance) and the two tables.
+struct TlasArgs {
+  rtt::TNode *nodes;
+  int32_t leaves;
+  int32_t ninst;
+  const InstRec *inst;
+  float *xform;
+  const rtd::MeshDev *blas;
+};
+// Leaves first .. first + count - 1 (first + count <= leaves) from the records
+// and the table as they are in stream order. d_xsrc (or NULL): count matrices
+// that are first taken over into t.xform. only_blas >= 0: only that BLAS's
+// instances. Only launches.
+int tlas_boxes_launch(const TlasArgs &t, int32_t first, int32_t count, const float *d_xsrc, int32_t only_blas,
+                      hipStream_t st);
+// every inner node from the leaves, bottom-up. Only launches.
+int tlas_refit_launch(const TlasArgs &t, hipStream_t st);
 
 }  // namespace rti

@@ -65,6 +65,13 @@ struct rt_scene {
   int32_t ninst = 0;
   std::vector<rt_scene *> blas;
   std::vector<uint64_t> blas_seen;
+  // created with RT_INSTANCED_TLAS: the top-level tree (2 * tlas_leaves nodes,
+  // rt_tlas.h) and the object-to-world matrices (12 floats per instance) its
+  // leaves are recomputed from when a BLAS's root box moves. Both live on the
+  // device only: the host keeps nothing that depends on a pose.
+  rtt::TNode *d_tlas = nullptr;
+  float *d_xform = nullptr;
+  int32_t tlas_leaves = 0;
   rtd::PlaneDev plane{};
   int64_t dev_bytes = 0;
   // cached buffers for host-buffer entry points
@@ -121,6 +128,8 @@ rtd::GridDev grid_dev(const rt_scene *s);
 int grid_mode(const rt_scene *s, const rtd::GridDev &gd);
 // the entries that render frames or copy a scene take no instanced scene
 int no_instanced(const rt_scene *s, const char *who);
+// what maintains the top-level tree of an instanced scene that has one
+rti::TlasArgs tlas_args(const rt_scene *s);
 
 // ---- rt_device.hip: the renderer --------------------------------------------
 // the scene's cached device frame for px pixels / its timing events

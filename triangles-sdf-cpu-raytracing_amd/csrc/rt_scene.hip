@@ -99,6 +99,10 @@ int no_instanced(const rt_scene *s, const char *who) {
   return RT_OK;
 }
 
+rti::TlasArgs tlas_args(const rt_scene *s) {
+  return rti::TlasArgs{s->d_tlas, s->tlas_leaves, s->ninst, s->d_inst, s->d_xform, s->d_blas};
+}
+
 }  // namespace rti
 
 namespace {
@@ -523,11 +527,21 @@ int instance_range(const rt_scene *s, int32_t first, int32_t count, const char *
 }
 }  // namespace
 
-int rt_scene_create_instanced(rt_scene *const *blas, int32_t nblas, const rt_instance *inst, int32_t ninst,
-                              rt_scene **out) {
-  const char *who = "rt_scene_create_instanced";
+// the tree of a scene created with RT_INSTANCED_TLAS, from the records, the
+// matrices and the table as the device holds them: leaves first .. first +
+// count - 1 (d_xsrc, only_blas: rti::tlas_boxes_launch), then every inner node
+static int tlas_update(const rt_scene *s, int32_t first, int32_t count, const float *d_xsrc, int32_t only_blas,
+                       hipStream_t st) {
+  const rti::TlasArgs t = rti::tlas_args(s);
+  if (int rc = rti::tlas_boxes_launch(t, first, count, d_xsrc, only_blas, st)) return rc;
+  return rti::tlas_refit_launch(t, st);
+}
+
+static int create_instanced(const char *who, rt_scene *const *blas, int32_t nblas, const rt_instance *inst,
+                            int32_t ninst, uint32_t flags, rt_scene **out) {
   if (!blas || !inst || !out) return set_err(RT_E_INVALID, std::string(who) + ": NULL argument");
   *out = nullptr;
+  if (flags & ~RT_INSTANCED_TLAS) return set_err(RT_E_INVALID, std::string(who) + ": unknown flag bits");
   if (nblas < 1 || ninst < 1) return set_err(RT_E_INVALID, std::string(who) + ": nblas and ninst must be at least 1");
   int dev = 0;
   HIP_TRY(hipGetDevice(&dev));
@@ -555,12 +569,38 @@ int rt_scene_create_instanced(rt_scene *const *blas, int32_t nblas, const rt_ins
   for (int32_t j = 0; j < nblas; ++j) s->blas_seen.push_back(blas[j]->version);
   int rc = upload(&s->d_inst, recs.data(), recs.size(), s->dev_bytes);
   if (!rc) rc = upload(&s->d_blas, tab.data(), tab.size(), s->dev_bytes);
+  if (!rc && (flags & RT_INSTANCED_TLAS)) {
+    // the matrices as given, the node array zeroed (node 0 and the pad words
+    // stay zero), every leaf (the empty ones past ninst too) and the inner
+    // nodes by the kernels that also serve the updates; done when this returns
+    std::vector<float> xf(12 * (size_t)ninst);
+    for (int32_t i = 0; i < ninst; ++i) std::memcpy(&xf[12 * (size_t)i], inst[i].xform, sizeof inst[i].xform);
+    s->tlas_leaves = rtt::leaf_count(ninst);
+    rc = upload(&s->d_xform, xf.data(), xf.size(), s->dev_bytes);
+    if (!rc) rc = upload(&s->d_tlas, (const rtt::TNode *)nullptr, 2 * (size_t)s->tlas_leaves, s->dev_bytes);
+    if (!rc) {
+      hipError_t e = hipMemset(s->d_tlas, 0, 2 * (size_t)s->tlas_leaves * sizeof(rtt::TNode));
+      if (e == hipSuccess) rc = tlas_update(s, 0, s->tlas_leaves, nullptr, -1, nullptr);
+      if (e == hipSuccess && !rc) e = hipStreamSynchronize(nullptr);
+      if (e != hipSuccess) rc = set_err(RT_E_DEVICE, rterr::hip_fail((std::string(who) + ": top-level tree").c_str(), e));
+    }
+  }
   if (rc) {
     rt_scene_destroy(s);
     return rc;
   }
   *out = s;
   return RT_OK;
+}
+
+int rt_scene_create_instanced(rt_scene *const *blas, int32_t nblas, const rt_instance *inst, int32_t ninst,
+                              rt_scene **out) {
+  return create_instanced("rt_scene_create_instanced", blas, nblas, inst, ninst, 0u, out);
+}
+
+int rt_scene_create_instanced_ex(rt_scene *const *blas, int32_t nblas, const rt_instance *inst, int32_t ninst,
+                                 uint32_t flags, rt_scene **out) {
+  return create_instanced("rt_scene_create_instanced_ex", blas, nblas, inst, ninst, flags, out);
 }
 
 int rt_scene_update_instances(rt_scene *s, int32_t first, int32_t count, const rt_instance *inst) {
@@ -574,10 +614,18 @@ int rt_scene_update_instances(rt_scene *s, int32_t first, int32_t count, const r
   int prev = 0;
   HIP_TRY(hipGetDevice(&prev));
   HIP_TRY(hipSetDevice(s->device));
-  const hipError_t e = rtdma::h2d(s->d_inst + first, recs.data(), recs.size() * sizeof(rti::InstRec), nullptr);
+  hipError_t e = rtdma::h2d(s->d_inst + first, recs.data(), recs.size() * sizeof(rti::InstRec), nullptr);
+  int rc = RT_OK;
+  if (e == hipSuccess && s->d_tlas) {  // the matrices as given, then the leaves and the tree; done on return
+    std::vector<float> xf(12 * (size_t)count);
+    for (int32_t i = 0; i < count; ++i) std::memcpy(&xf[12 * (size_t)i], inst[i].xform, sizeof inst[i].xform);
+    e = rtdma::h2d(s->d_xform + 12 * (size_t)first, xf.data(), xf.size() * sizeof(float), nullptr);
+    if (e == hipSuccess) rc = tlas_update(s, first, count, nullptr, -1, nullptr);
+    if (e == hipSuccess && !rc) e = hipStreamSynchronize(nullptr);
+  }
   HIP_NOTE(hipSetDevice(prev));
   if (e != hipSuccess) return set_err(RT_E_DEVICE, rterr::hip_fail("rt_scene_update_instances: upload", e));
-  return RT_OK;
+  return rc;
 }
 
 int rt_scene_update_instances_device(rt_scene *s, int32_t first, int32_t count, const float *d_xform12,
@@ -586,7 +634,33 @@ int rt_scene_update_instances_device(rt_scene *s, int32_t first, int32_t count, 
   if (int rc = instance_range(s, first, count, who)) return rc;
   if (!d_xform12) return set_err(RT_E_INVALID, std::string(who) + ": matrix pointer is NULL");
   if (count == 0) return RT_OK;
-  return rti::pose_launch(s->d_inst, first, count, d_xform12, (hipStream_t)stream);
+  if (int rc = rti::pose_launch(s->d_inst, first, count, d_xform12, (hipStream_t)stream)) return rc;
+  // a top-level tree: the box kernel takes the matrices over and redoes these
+  // leaves behind the pose kernel, then the refit; still only launches
+  return s->d_tlas ? tlas_update(s, first, count, d_xform12, -1, (hipStream_t)stream) : RT_OK;
+}
+
+int rt_scene_get_tlas(const rt_scene *s, float *leaf_boxes, float *node_boxes, int32_t *leaves) {
+  const char *who = "rt_scene_get_tlas";
+  if (!s) return set_err(RT_E_INVALID, std::string(who) + ": scene is NULL");
+  if (s->kind != RT_SCENE_INSTANCED || !s->d_tlas)
+    return set_err(RT_E_STATE, std::string(who) + ": not an instanced scene created with RT_INSTANCED_TLAS");
+  const int32_t P = s->tlas_leaves;
+  if (leaves) *leaves = P;
+  if (!leaf_boxes && !node_boxes) return RT_OK;
+  std::vector<rtt::TNode> nd(2 * (size_t)P);
+  int prev = 0;
+  HIP_TRY(hipGetDevice(&prev));
+  HIP_TRY(hipSetDevice(s->device));
+  hipError_t e = hipDeviceSynchronize();  // updates queued on any stream
+  if (e == hipSuccess) e = rtdma::d2h(nd.data(), s->d_tlas, nd.size() * sizeof(rtt::TNode), nullptr);
+  HIP_NOTE(hipSetDevice(prev));
+  if (e != hipSuccess) return set_err(RT_E_DEVICE, rterr::hip_fail(who, e));
+  if (leaf_boxes)
+    for (int32_t i = 0; i < s->ninst; ++i) std::memcpy(leaf_boxes + 6 * (size_t)i, nd[(size_t)P + i].b, 6 * sizeof(float));
+  if (node_boxes)
+    for (int32_t n = 0; n < 2 * P; ++n) std::memcpy(node_boxes + 6 * (size_t)n, nd[(size_t)n].b, 6 * sizeof(float));
+  return RT_OK;
 }
 
 int rt_scene_get_instances(const rt_scene *s, int32_t first, int32_t count, rt_instance *inst, float *inv12,
@@ -726,7 +800,7 @@ int rt_scene_destroy(rt_scene *s) {
     if (x) HIP_NOTE(hipStreamSynchronize(x));
   if (s->sched_os) HIP_NOTE(hipStreamSynchronize(s->sched_os));
   void *ptrs[] = {s->d_nodes, s->d_tris, s->d_vals, s->d_child, s->d_ovals, s->d_color, s->d_t,
-                  s->d_cost[0], s->d_order[0], s->d_cost[1], s->d_order[1], s->d_idx, s->d_vstage, s->d_edge, s->d_inst, s->d_blas};
+                  s->d_cost[0], s->d_order[0], s->d_cost[1], s->d_order[1], s->d_idx, s->d_vstage, s->d_edge, s->d_inst, s->d_blas, s->d_tlas, s->d_xform};
   for (void *p : ptrs)
     if (p) HIP_NOTE(hipFree(p));
   if (s->h_refit) HIP_NOTE(hipHostFree(s->h_refit));

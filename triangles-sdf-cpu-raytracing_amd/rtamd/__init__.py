@@ -7,6 +7,7 @@ package only marshals arguments.
 from ._lib import EXPORTED, LIB_PATH, RT_FLAG_CLEAR, RenderParams, RtError, Tile, build, lib
 from .api import (BVHBuilder, Camera, FrameBuffer, HitInfo, InstancedScene, IScene, MultiRenderer, Plane, Renderer, SceneUnion,
                   SDFGrid, SDFMesh, SDFOctree, ShadingMode, SimpleMesh, affine_inverse, camera_matrices, device_count,
+                  instance_world_box, morton_order,
                   load_mesh_from_obj, load_sdf_grid, load_sdf_octree, render_params, save_mesh_to_obj,
                   subdivide_mesh)
 from . import data, tiles, workloads
@@ -15,6 +16,7 @@ __all__ = [
     "EXPORTED", "LIB_PATH", "RT_FLAG_CLEAR", "RenderParams", "RtError", "Tile", "build", "lib",
     "BVHBuilder", "Camera", "FrameBuffer", "HitInfo", "InstancedScene", "IScene", "MultiRenderer", "Plane", "Renderer", "SceneUnion",
     "SDFGrid", "SDFMesh", "SDFOctree", "ShadingMode", "SimpleMesh", "affine_inverse", "camera_matrices", "device_count",
+    "instance_world_box", "morton_order",
     "load_mesh_from_obj", "load_sdf_grid", "load_sdf_octree", "render_params", "save_mesh_to_obj",
     "subdivide_mesh",
     "data",

@@ -22,6 +22,7 @@ RT_MESH_DYNAMIC = 1
 RT_IPC_HANDLE_BYTES = 64
 RT_SCENE_MESH, RT_SCENE_GRID, RT_SCENE_OCTREE, RT_SCENE_INSTANCED = 1, 2, 3, 4
 RT_INSTANCE_DISABLED = 1
+RT_INSTANCED_TLAS = 1
 
 _lib = None
 
@@ -93,6 +94,10 @@ _SIGS = {
     "rt_affine_inverse": (C.c_int, [C.c_void_p, C.c_void_p]),
     "rt_scene_create_instanced": (C.c_int, [C.POINTER(C.c_void_p), C.c_int32, C.POINTER(Instance), C.c_int32,
                                             C.POINTER(C.c_void_p)]),
+    "rt_scene_create_instanced_ex": (C.c_int, [C.POINTER(C.c_void_p), C.c_int32, C.POINTER(Instance), C.c_int32,
+                                               C.c_uint32, C.POINTER(C.c_void_p)]),
+    "rt_instance_world_box": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_scene_get_tlas": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]),
     "rt_scene_update_instances": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(Instance)]),
     "rt_scene_update_instances_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "rt_scene_get_instances": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(Instance), C.c_void_p,
@@ -184,6 +189,15 @@ _XSIGS = {
     # the scene dispatch's mapping (scene kind, stack slots, grid mode) ->
     # kernel template arguments, host only
     "rtx_dispatch_probe": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    # the top-level tree of RT_INSTANCED_TLAS scenes: the shared path's lane
+    # threshold, the per-ray traversal counter, and the host restatements of
+    # the box test, the tree and the kernel's cursor walk (no GPU)
+    "rtx_set_tlas_uniform_min": (C.c_int, [C.c_int]),
+    "rtx_set_tlas_count": (C.c_int, [C.c_void_p]),
+    "rtx_tlas_box_pass": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float]),
+    "rtx_tlas_build_host": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
+    "rtx_tlas_candidates": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_int32,
+                                      C.c_void_p, C.c_int32]),
 }
 
 

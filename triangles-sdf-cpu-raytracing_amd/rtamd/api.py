@@ -23,12 +23,12 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from ._lib import (RT_FLAG_CLEAR, RT_FLAG_HITS_ONLY, RT_INSTANCE_DISABLED, RT_MESH_DYNAMIC, RT_RAYS_ANY_HIT,
+from ._lib import (RT_FLAG_CLEAR, RT_FLAG_HITS_ONLY, RT_INSTANCE_DISABLED, RT_INSTANCED_TLAS, RT_MESH_DYNAMIC, RT_RAYS_ANY_HIT,
                    CameraState, Instance, RayBatch, RenderParams, RtError, Tile, check, lib)
 
 __all__ = [
     "ShadingMode", "SimpleMesh", "FrameBuffer", "Camera", "Renderer", "HitInfo", "IScene",
-    "BVHBuilder", "SDFGrid", "SDFOctree", "InstancedScene", "InstanceTable", "affine_inverse", "Plane", "SceneUnion", "load_mesh_from_obj",
+    "BVHBuilder", "SDFGrid", "SDFOctree", "InstancedScene", "InstanceTable", "affine_inverse", "instance_world_box", "morton_order", "Plane", "SceneUnion", "load_mesh_from_obj",
     "load_sdf_grid", "load_sdf_octree", "camera_matrices", "render_params", "RtError",
     "RT_FLAG_CLEAR", "Tile", "device_count", "SDFMesh", "subdivide_mesh", "save_mesh_to_obj",
     "MultiRenderer",
@@ -448,6 +448,35 @@ def affine_inverse(xform) -> np.ndarray:
     return inv.reshape(3, 4)
 
 
+def instance_world_box(xform, obox) -> np.ndarray:
+    """rt_instance_world_box: the world box (lo.xyz, hi.xyz, float32 [6]) an
+    RT_INSTANCED_TLAS scene gives an instance with object-to-world map `xform`
+    of a BLAS whose root box is `obox` (lo.xyz, hi.xyz)."""
+    x = np.ascontiguousarray(xform, np.float32).reshape(12)
+    b = np.ascontiguousarray(obox, np.float32).reshape(6)
+    w = np.zeros(6, np.float32)
+    check(lib().rt_instance_world_box(_p(x), _p(b), _p(w)))
+    return w
+
+
+def morton_order(centres) -> np.ndarray:
+    """A permutation of instance indices along the 30-bit Morton curve of
+    their centres ([K, 3], any float type): 10 bits per axis over the centres'
+    own bounding box, ties in the given order. The top-level tree of
+    InstancedScene(..., tlas=True) is a complete binary tree over the
+    instances IN INDEX ORDER, so its quality is the spatial coherence of that
+    order; pass instances[morton_order(centres)] when the order is free.
+    (prim then reports the permuted index.)"""
+    c = np.asarray(centres, np.float64).reshape(-1, 3)
+    lo, ext = c.min(0), np.maximum(c.max(0) - c.min(0), 1e-300)
+    q = np.minimum((c - lo) / ext * 1024.0, 1023.0).astype(np.uint64)
+    code = np.zeros(len(c), np.uint64)
+    for bit in range(10):
+        for a in range(3):
+            code |= ((q[:, a] >> np.uint64(bit)) & np.uint64(1)) << np.uint64(3 * bit + 2 - a)
+    return np.argsort(code, kind="stable")
+
+
 @dataclass
 class InstanceTable:
     """What the device holds of an InstancedScene (rt_scene_get_instances)."""
@@ -477,11 +506,14 @@ class InstancedScene(IScene):
     device; instances: (blas index, xform) or (blas index, xform, flags)
     tuples, xform the object-to-world map as 12 floats (row-major 3x4). Ray
     queries only (intersect, trace_device, torch_rays.trace): prim is
-    (instance << 32) | triangle id. Keeps its BLAS objects alive."""
+    (instance << 32) | triangle id. Keeps its BLAS objects alive.
+    tlas=True (RT_INSTANCED_TLAS): a top-level tree over the instances' world
+    boxes, for hundreds of instances; its quality is the spatial coherence of
+    the index order (morton_order)."""
 
     DISABLED = RT_INSTANCE_DISABLED
 
-    def __init__(self, blas_list, instances):
+    def __init__(self, blas_list, instances, tlas: bool = False):
         self._blas_objs = list(blas_list)
         inst = [tuple(t) for t in instances]
         self._blas_idx = np.asarray([t[0] for t in inst], np.int32)
@@ -490,8 +522,10 @@ class InstancedScene(IScene):
         xforms = np.asarray([np.asarray(t[1], np.float32).reshape(12) for t in inst], np.float32).reshape(-1, 12)
         arr = _instance_array(self._blas_idx, xforms, self._flags)
         h = C.c_void_p()
-        check(lib().rt_scene_create_instanced(handles, len(self._blas_objs), arr, len(inst), C.byref(h)))
+        check(lib().rt_scene_create_instanced_ex(handles, len(self._blas_objs), arr, len(inst),
+                                                 RT_INSTANCED_TLAS if tlas else 0, C.byref(h)))
         self._h = h
+        self.has_tlas = bool(tlas)
 
     def __len__(self):
         return len(self._blas_idx)
@@ -517,6 +551,17 @@ class InstancedScene(IScene):
         check(lib().rt_scene_update_instances_device(self._handle(), int(first), int(count),
                                                      C.c_void_p(ptr) if ptr else None,
                                                      C.c_void_p(stream) if stream else None))
+
+    def tlas(self):
+        """The top-level tree as the device holds it (rt_scene_get_tlas, one
+        synchronisation) -> (leaf boxes float32 [K, 6], node boxes float32
+        [2P, 6]; lo.xyz hi.xyz, node 0 unused)."""
+        P = C.c_int32(0)
+        check(lib().rt_scene_get_tlas(self._handle(), None, None, C.byref(P)))
+        leaf = np.zeros((len(self), 6), np.float32)
+        node = np.zeros((2 * P.value, 6), np.float32)
+        check(lib().rt_scene_get_tlas(self._handle(), _p(leaf), _p(node), None))
+        return leaf, node
 
     def instances(self) -> InstanceTable:
         """Read the instance table back from the device (one synchronisation)."""
