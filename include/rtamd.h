@@ -519,6 +519,56 @@ typedef struct rt_ray_batch {
 #define RT_RAYS_ANY_HIT 1u
 int rt_trace_rays_device(rt_scene *s, const rt_ray_batch *b, uint32_t flags, void *stream);
 
+/* ---- shaded rays (the per-ray body of Renderer::draw) -------------------- */
+/* The reference's eye rays as a ray batch in DEVICE buffers: ray i = y*W + x
+ * is pixel (x, y) of rt_render's frame. d_dir[3i..] is the direction the frame
+ * kernels trace for that pixel (EyeRayDir4f of loop row H - y - 1 under
+ * proj_inv and view_inv, src/raytracing.cpp:83-88), d_origin[3i..] is
+ * camera_pos. Either output may be NULL (not written), not both. p, W and H
+ * are checked as rt_render_device checks them. The call only launches on
+ * `stream`: no allocation, no copy, no host synchronisation. */
+int rt_eye_rays_device(const rt_render_params *p, int32_t W, int32_t H,
+                       float *d_origin, float *d_dir, void *stream);
+
+/* Renderer::intersectionColor, color_pack_rgba and draw's store rule
+ * (src/raytracing.cpp:13-102) for rays in device buffers, in stream order on
+ * `stream`; the call only launches (no allocation, no copy, no host
+ * synchronisation; the scene's device must be the current one). All four
+ * scene kinds, an instanced scene in both of its modes.
+ *
+ * Ray i, with (o, d) from the batch, tn_i = d_tnear ? d_tnear[i] : tnear and
+ * tf_i = d_tfar ? d_tfar[i] : tfar, is intersected with the union of the scene
+ * and its plane over [tn_i, tf_i] and shaded as the frame kernels shade a
+ * pixel: Lambert with the shadow ray (origin point + 0.3 sd over [0.01, 100])
+ * and one reflection bounce off the plane (origin point + 0.02 R over
+ * [0.01, 100]), or the Color / Normal modes. Of `p` only light_pos,
+ * shading_mode, enable_shadows and enable_reflections are read; reserved must
+ * be 0. For an instanced scene every one of the up to four rays per input ray
+ * goes through the loop above (with its box_pass line for RT_INSTANCED_TLAS);
+ * a shadow query may stop at its first hit, its flag being the closest-hit
+ * flag. A BLAS refitted since the scene last saw it is caught up in stream
+ * order ahead of the launch, as for rt_trace_rays_device.
+ *
+ * store = hit && !isinf(t), the frame kernels' rule. If store: d_color[i] =
+ * the packed RGBA8 colour and, when b->d_t is given, d_t[i] = t. Else with
+ * RT_SHADE_CLEAR: d_color[i] = 0 and d_t[i] = +inf. Else ray i writes neither
+ * (Renderer::draw on a frame that already holds something). b->d_hit[i] =
+ * store ? 1 : 0 and b->d_prim[i] = the first intersection's primitive id
+ * (-2 the plane, -1 a miss) are always written when given. b->d_normal must
+ * be NULL: colour is the output here, the normal is rt_trace_rays_device's.
+ *
+ * d_tfar may be the same buffer as d_t: each ray reads its own interval before
+ * its own stores, and no ray reads another's. Several scenes shaded one after
+ * another into one (d_color, d_t) pair without RT_SHADE_CLEAR, each with
+ * d_tfar = d_t, then compose by depth as the reference's tPrev does
+ * (tFar = min(tFar, tPrev), src/raytracing.cpp:89-94): a later scene's hit is
+ * stored only where it lies in front of what the pair holds.
+ *
+ * n == 0 launches nothing; n is limited as for rt_trace_rays_device. */
+#define RT_SHADE_CLEAR 1u
+int rt_shade_rays_device(rt_scene *s, const rt_ray_batch *b, const rt_render_params *p,
+                         uint32_t *d_color, uint32_t flags, void *stream);
+
 /* Timing helper for benchmarks: renders `frames` frames back to back on the
  * device (buffers owned by the library), returns the mean kernel ms per frame
  * and the total in *total_ms. params[frames] gives one camera per frame. */

@@ -197,6 +197,16 @@ class IScene {
   void intersectDevice(const rt_ray_batch &batch, uint32_t flags = 0, void *stream = nullptr) const {
     check(rt_trace_rays_device(handle(), &batch, flags, stream));
   }
+  // Renderer::intersectionColor + draw's store rule for rays already in device
+  // memory (rt_shade_rays_device): the packed colour of each ray of `batch`
+  // under `params` (light, shading mode, switches) into d_color, t / hit /
+  // prim into the batch's outputs (d_normal must be NULL); flags: 0 or
+  // RT_SHADE_CLEAR. Every scene kind, InstancedScene included. Returns after
+  // the launch.
+  void shadeDevice(const rt_ray_batch &batch, const rt_render_params &params, uint32_t *d_color,
+                   uint32_t flags = RT_SHADE_CLEAR, void *stream = nullptr) const {
+    check(rt_shade_rays_device(handle(), &batch, &params, d_color, flags, stream));
+  }
   void setPlane(const Plane *p) const {
     const float n[3] = {p ? p->normal.x : 0.0f, p ? p->normal.y : 1.0f, p ? p->normal.z : 0.0f};
     check(rt_scene_set_plane(handle(), p ? 1 : 0, n, p ? p->offset : 0.0f));
@@ -277,9 +287,18 @@ inline void loadSDFOctree(SDFOctree &o, const std::string &path) {  // octree_ra
   o.upload();
 }
 
+// The eye rays of the W x H frame `params` describes as a ray batch in device
+// buffers (rt_eye_rays_device): ray y * W + x is pixel (x, y); float[3 W H]
+// each, either may be nullptr. With IScene::shadeDevice: a frame of any scene.
+inline void eyeRaysDevice(const rt_render_params &params, int32_t W, int32_t H, float *d_origin, float *d_dir,
+                          void *stream = nullptr) {
+  check(rt_eye_rays_device(&params, W, H, d_origin, d_dir, stream));
+}
+
 // Rigid (affine) copies of mesh scenes under one ray query
 // (rt_scene_create_instanced; no reference counterpart). Ray queries only:
-// intersect / intersectDevice, with prim = (instance << 32) | triangle id. The
+// intersect / intersectDevice / shadeDevice (the way to a picture: the frame
+// entries refuse the kind), with prim = (instance << 32) | triangle id. The
 // BLAS scenes are not owned and must outlive this scene.
 class InstancedScene : public IScene {
  public:

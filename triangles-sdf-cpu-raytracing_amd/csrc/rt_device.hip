@@ -2154,18 +2154,8 @@ void launch_trace_t(const S &sc, const PlaneDev &pl, const rt_ray_batch &b, int 
 int launch_trace(rt_scene *s, const rt_ray_batch &b, int mode, hipStream_t stream) {
   if (s->kind == RT_SCENE_INSTANCED) {
     // a bottom-level scene refitted since its table entry was written: the
-    // entry is rewritten in stream order ahead of the trace, no host wait
-    for (size_t j = 0; j < s->blas.size(); ++j) {
-      if (s->blas[j]->version == s->blas_seen[j]) continue;
-      if (int rc = rti::blas_entry_launch(s->d_blas + j, mesh_dev(s->blas[j]), stream)) return rc;
-      s->blas_seen[j] = s->blas[j]->version;
-      if (!s->d_tlas) continue;
-      // its root box moved: that BLAS's leaves of the top-level tree and the
-      // tree above them, behind the entry
-      const rti::TlasArgs t = rti::tlas_args(s);
-      if (int rc = rti::tlas_boxes_launch(t, 0, s->ninst, nullptr, (int32_t)j, stream)) return rc;
-      if (int rc = rti::tlas_refit_launch(t, stream)) return rc;
-    }
+    // entry (and a top-level tree) catch up in stream order ahead of the trace
+    if (int rc = rti::instanced_sync(s, stream)) return rc;
     const rti::InstArgs a{s->d_inst, s->d_blas, s->ninst, s->maxd, s->d_tlas, s->tlas_leaves};
     return s->d_tlas ? rti::trace_tlas_launch(a, s->plane, b, mode, stream)
                      : rti::trace_instances_launch(a, s->plane, b, mode, stream);

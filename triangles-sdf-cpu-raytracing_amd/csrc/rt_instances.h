@@ -76,6 +76,12 @@ int blas_entry_launch(rtd::MeshDev *entry, const rtd::MeshDev &md, hipStream_t s
 // matrix per lane; blas and flags stay. Only launches.
 int pose_launch(InstRec *inst, int32_t first, int32_t count, const float *d_xform12, hipStream_t st);
 
+// ---- rt_shade_instances.hip: rt_shade_rays_device of an instanced scene ------
+// shade_one (rt_shade.h) over the flat list or, with a.tlas set, the top-level
+// tree; d_color and flags as rt_shade_rays_device takes them. Only launches.
+int shade_instances_launch(const InstArgs &a, const rtd::PlaneDev &pl, const rt_render_params &p,
+                           const rt_ray_batch &b, uint32_t *d_color, uint32_t flags, hipStream_t st);
+
 // ---- rt_tlas.hip: scenes created with RT_INSTANCED_TLAS ---------------------
 // the trace through the top-level tree (a.tlas set); as trace_instances_launch
 int trace_tlas_launch(const InstArgs &a, const rtd::PlaneDev &pl, const rt_ray_batch &b, int mode, hipStream_t st);

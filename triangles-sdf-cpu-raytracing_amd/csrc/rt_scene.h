@@ -130,6 +130,12 @@ int grid_mode(const rt_scene *s, const rtd::GridDev &gd);
 int no_instanced(const rt_scene *s, const char *who);
 // what maintains the top-level tree of an instanced scene that has one
 rti::TlasArgs tlas_args(const rt_scene *s);
+// What every ray query of an instanced scene queues ahead of its kernel
+// (rt_trace_rays_device, rt_shade_rays_device): the table entry of a
+// bottom-level scene refitted since the entry was written is rewritten in
+// stream order, and with a top-level tree that BLAS's leaf boxes and the tree
+// above them follow. Only launches; no host wait.
+int instanced_sync(rt_scene *s, hipStream_t stream);
 
 // ---- rt_device.hip: the renderer --------------------------------------------
 // the scene's cached device frame for px pixels / its timing events

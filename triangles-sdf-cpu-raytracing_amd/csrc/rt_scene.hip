@@ -99,6 +99,21 @@ int no_instanced(const rt_scene *s, const char *who) {
   return RT_OK;
 }
 
+int instanced_sync(rt_scene *s, hipStream_t stream) {
+  for (size_t j = 0; j < s->blas.size(); ++j) {
+    if (s->blas[j]->version == s->blas_seen[j]) continue;
+    if (int rc = rti::blas_entry_launch(s->d_blas + j, mesh_dev(s->blas[j]), stream)) return rc;
+    s->blas_seen[j] = s->blas[j]->version;
+    if (!s->d_tlas) continue;
+    // its root box moved: that BLAS's leaves of the top-level tree and the
+    // tree above them, behind the entry
+    const rti::TlasArgs t = rti::tlas_args(s);
+    if (int rc = rti::tlas_boxes_launch(t, 0, s->ninst, nullptr, (int32_t)j, stream)) return rc;
+    if (int rc = rti::tlas_refit_launch(t, stream)) return rc;
+  }
+  return RT_OK;
+}
+
 rti::TlasArgs tlas_args(const rt_scene *s) {
   return rti::TlasArgs{s->d_tlas, s->tlas_leaves, s->ninst, s->d_inst, s->d_xform, s->d_blas};
 }

@@ -214,11 +214,14 @@ __device__ __forceinline__ f4 lambert_color(const S &sc, const PlaneDev &pl,
   return f4{std_min(c.x, 1.0f), std_min(c.y, 1.0f), std_min(c.z, 1.0f), 1.0f};
 }
 
+// tNear: the primary ray's (the frames' constant 0.01; a ray batch passes its
+// own, rt_shade_rays.h); the secondary rays keep the reference's constants.
 template <class S, int B, class CT>
 __device__ __forceinline__ f4 shade_one(const S &sc, const PlaneDev &pl, const rt_render_params &P,
                                         f3 o, f3 d, float tFarEff, bool allow_refl, bool &hit,
-                                        float &t_out, StackOf<S, B> st, int64_t *prim, CT &cnt) {
-  const SurfHit sh = union_intersect<S, B>(sc, pl, o, d, 0.01f, tFarEff, st, cnt);
+                                        float &t_out, StackOf<S, B> st, int64_t *prim, CT &cnt,
+                                        float tNear = 0.01f) {
+  const SurfHit sh = union_intersect<S, B>(sc, pl, o, d, tNear, tFarEff, st, cnt);
   if (prim) *prim = sh.h.hit ? sh.h.prim : -1;
   if (!sh.h.hit) {
     hit = false;

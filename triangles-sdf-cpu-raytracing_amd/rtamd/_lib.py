@@ -18,6 +18,7 @@ RT_FLAG_CLEAR = 1
 RT_FLAG_TILE_NATURAL = 2
 RT_FLAG_HITS_ONLY = 4
 RT_RAYS_ANY_HIT = 1
+RT_SHADE_CLEAR = 1
 RT_MESH_DYNAMIC = 1
 RT_IPC_HANDLE_BYTES = 64
 RT_SCENE_MESH, RT_SCENE_GRID, RT_SCENE_OCTREE, RT_SCENE_INSTANCED = 1, 2, 3, 4
@@ -143,6 +144,9 @@ _SIGS = {
     "rt_intersect_rays": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float,
                                     C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rt_trace_rays_device": (C.c_int, [C.c_void_p, C.POINTER(RayBatch), C.c_uint32, C.c_void_p]),
+    "rt_eye_rays_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_shade_rays_device": (C.c_int, [C.c_void_p, C.POINTER(RayBatch), C.c_void_p, C.c_void_p, C.c_uint32,
+                                       C.c_void_p]),
     "rt_count_work": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
                                 C.c_uint32, C.c_void_p, C.c_void_p]),
     "rt_bench_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,

@@ -24,14 +24,14 @@ from dataclasses import dataclass
 import numpy as np
 
 from ._lib import (RT_FLAG_CLEAR, RT_FLAG_HITS_ONLY, RT_INSTANCE_DISABLED, RT_INSTANCED_TLAS, RT_MESH_DYNAMIC, RT_RAYS_ANY_HIT,
-                   CameraState, Instance, RayBatch, RenderParams, RtError, Tile, check, lib)
+                   RT_SHADE_CLEAR, CameraState, Instance, RayBatch, RenderParams, RtError, Tile, check, lib)
 
 __all__ = [
     "ShadingMode", "SimpleMesh", "FrameBuffer", "Camera", "Renderer", "HitInfo", "IScene",
     "BVHBuilder", "SDFGrid", "SDFOctree", "InstancedScene", "InstanceTable", "affine_inverse", "instance_world_box", "morton_order", "Plane", "SceneUnion", "load_mesh_from_obj",
     "load_sdf_grid", "load_sdf_octree", "camera_matrices", "render_params", "RtError",
     "RT_FLAG_CLEAR", "Tile", "device_count", "SDFMesh", "subdivide_mesh", "save_mesh_to_obj",
-    "MultiRenderer",
+    "MultiRenderer", "eye_rays_device",
 ]
 
 
@@ -126,6 +126,15 @@ def render_params(cam_pos, view_inv, proj_inv, light=(2.0, 2.0, 2.0), mode=Shadi
     P.enable_reflections = int(bool(reflections))
     P.reserved = 0
     return P
+
+
+def eye_rays_device(params: RenderParams, W: int, H: int, origin_ptr: int | None, dir_ptr: int | None,
+                    stream: int | None = None):
+    """The eye rays of the frame `params` describes as a ray batch in device
+    buffers (rt_eye_rays_device): ray y * W + x is pixel (x, y); float32[3 W H]
+    each, either pointer may be None. Queued on `stream`; only launches."""
+    check(lib().rt_eye_rays_device(C.byref(params), W, H, C.c_void_p(origin_ptr or None),
+                                   C.c_void_p(dir_ptr or None), C.c_void_p(stream) if stream else None))
 
 
 class Camera:
@@ -313,6 +322,24 @@ class IScene:
                      prim_ptr or None)
         check(lib().rt_trace_rays_device(self._handle(), C.byref(b), RT_RAYS_ANY_HIT if any_hit else 0,
                                          C.c_void_p(stream) if stream else None))
+
+    def shade_device(self, origin_ptr: int, dir_ptr: int, n: int, params: RenderParams, color_ptr: int, *,
+                     t_ptr: int | None = None, hit_ptr: int | None = None, prim_ptr: int | None = None,
+                     tnear: float = 0.01, tfar: float = 100.0, tnear_ptr: int | None = None,
+                     tfar_ptr: int | None = None, clear: bool = True, stream: int | None = None):
+        """The per-ray body of Renderer::draw on device buffers
+        (rt_shade_rays_device): n rays at origin_ptr / dir_ptr (float32[3n])
+        are intersected with the scene and its plane and shaded under
+        `params` (its light, shading mode and switches); a ray that hits gets
+        its packed RGBA8 colour at color_ptr (uint32[n]) and its t at t_ptr.
+        clear: a miss gets 0 / +inf; otherwise it writes neither, and
+        tfar_ptr may be t_ptr (the reference's tPrev). hit_ptr (int32) and
+        prim_ptr (int64) are always written when given. Queued on `stream`;
+        the call only launches. All scene kinds, instanced ones included."""
+        b = RayBatch(int(n), origin_ptr or None, dir_ptr or None, tnear_ptr or None, tfar_ptr or None,
+                     float(tnear), float(tfar), hit_ptr or None, t_ptr or None, None, prim_ptr or None)
+        check(lib().rt_shade_rays_device(self._handle(), C.byref(b), C.byref(params), C.c_void_p(color_ptr or None),
+                                         RT_SHADE_CLEAR if clear else 0, C.c_void_p(stream) if stream else None))
 
     def bench_frames(self, params_list, W: int, H: int, clear: bool = True):
         arr = (RenderParams * len(params_list))(*params_list)

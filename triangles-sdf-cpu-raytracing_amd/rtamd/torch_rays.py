@@ -20,6 +20,15 @@ gives an rtamd.InstancedScene new poses from a tensor of object-to-world
 matrices (rt_scene_update_instances_device: one small kernel on the same
 stream, nothing else), and split_prim() takes such a scene's primitive ids
 apart into (instance, triangle).
+
+    o, d = torch_rays.eye_rays(params, W, H)
+    r = torch_rays.shade(scene, o, d, params)
+
+is the renderer's colour for rays on the GPU (rt_eye_rays_device,
+rt_shade_rays_device): eye_rays writes the frame's eye rays as a ray batch, and
+shade runs the reference's shading (Lambert with its shadow ray and reflection
+bounce, Color, Normal) on any rays, for every scene kind. Eye rays plus shade
+is a frame; for an rtamd.InstancedScene it is the way to a picture.
 """
 from __future__ import annotations
 
@@ -28,6 +37,7 @@ from dataclasses import dataclass
 from ._lib import lib
 
 OUTPUTS = ("hit", "t", "normal", "prim")
+SHADE_OUTPUTS = ("color", "t", "hit", "prim")
 
 
 @dataclass
@@ -38,6 +48,16 @@ class RayHits:
     t: "object | None" = None        # torch.float32, +inf on a miss
     normal: "object | None" = None   # torch.float32 [N,3], (0,1,0) on a miss, not flipped
     prim: "object | None" = None     # torch.int64, include/rtamd.h's primitive id
+
+
+@dataclass
+class RayColors:
+    """The outputs of one shade() ([N] tensors on the rays' device); the ones
+    not requested are None."""
+    color: "object | None" = None    # torch.int32: the RGBA8 word, R in the low byte (view it as uint8 [N,4])
+    t: "object | None" = None        # torch.float32
+    hit: "object | None" = None      # torch.int32, 1 where a colour was stored
+    prim: "object | None" = None     # torch.int64, the first intersection's primitive id (-2 plane, -1 miss)
 
 
 def _rays(torch, x, what, device):
@@ -173,5 +193,95 @@ def trace(scene, origins, dirs, tnear=0.01, tfar=100.0, any_hit=False, outputs=O
         scene.trace_device(o.data_ptr(), d.data_ptr(), n, hit_ptr=ptr(r.hit), t_ptr=ptr(r.t),
                            normal_ptr=ptr(r.normal), prim_ptr=ptr(r.prim), tnear=tn, tfar=tf,
                            tnear_ptr=ptr(tn_t), tfar_ptr=ptr(tf_t), any_hit=any_hit,
+                           stream=torch.cuda.current_stream(device).cuda_stream)
+    return r
+
+
+def eye_rays(params, W: int, H: int, device=None):
+    """The eye rays of the W x H frame `params` (an rtamd.RenderParams)
+    describes, as a ray batch: (origins, dirs), float32 [W*H, 3] each, ray
+    y * W + x being pixel (x, y) of the rendered frame. The directions are the
+    ones the frame kernels trace, bit for bit; the origins are camera_pos.
+    Written by one kernel on torch.cuda.current_stream() of `device` (default:
+    the current one)."""
+    import torch
+
+    dev = torch.device("cuda", device) if isinstance(device, int) else torch.device(device or "cuda")
+    if dev.type != "cuda":
+        raise ValueError(f"device {dev}: eye rays are written on a HIP device")
+    if dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    W, H = int(W), int(H)
+    if W <= 0 or H <= 0:
+        raise ValueError(f"frame size {W} x {H}")
+    o = torch.empty((W * H, 3), dtype=torch.float32, device=dev)
+    d = torch.empty((W * H, 3), dtype=torch.float32, device=dev)
+    from .api import eye_rays_device
+    with torch.cuda.device(dev):
+        eye_rays_device(params, W, H, o.data_ptr(), d.data_ptr(), stream=torch.cuda.current_stream(dev).cuda_stream)
+    return o, d
+
+
+def _given(torch, x, what, dtype, n, device):
+    if not isinstance(x, torch.Tensor) or x.dtype != dtype or x.dim() != 1 or x.shape[0] != n:
+        raise ValueError(f"{what}: expected a {dtype} [{n}] tensor")
+    if x.device.type != "cuda" or x.device.index != device:
+        raise ValueError(f"{what}: on {x.device}, the scene is on HIP device {device}")
+    if not x.is_contiguous():
+        raise ValueError(f"{what}: not contiguous")
+    return x
+
+
+def shade(scene, origins, dirs, params, tnear=0.01, tfar=100.0, clear=True, color=None, t=None,
+          outputs=("color", "t")) -> RayColors:
+    """The renderer's colour of N rays against `scene` (an rtamd.IScene of any
+    kind, its plane included): Renderer::intersectionColor under `params`
+    (light, shading mode, shadow and reflection switches), packed as the frame
+    kernels pack it. origins, dirs, tnear, tfar: as trace(). "color" is always
+    produced; outputs selects what else is ("t", "hit", "prim").
+
+    clear=True: every ray is written (a miss: colour 0, t = +inf). clear=False:
+    a miss writes neither colour nor t, so the buffers must hold something --
+    pass them as color (int32 [N]) and t (float32 [N]); they are written in
+    place and returned. tfar may be that same t tensor: each ray then only
+    accepts a hit in front of what the buffers hold, and several scenes shaded
+    one after another compose by depth (the reference's tPrev). Queued on
+    torch.cuda.current_stream(); raises ValueError on a bad tensor before
+    anything is launched."""
+    import torch
+
+    device = int(lib().rt_scene_device(scene._handle()))
+    o = _rays(torch, origins, "origins", device)
+    d = _rays(torch, dirs, "dirs", device)
+    if o.shape != d.shape:
+        raise ValueError(f"origins {tuple(o.shape)} and dirs {tuple(d.shape)} differ in shape")
+    n = o.shape[0]
+    tn, tn_t = _interval(torch, tnear, "tnear", n, device)
+    tf, tf_t = _interval(torch, tfar, "tfar", n, device)
+    outputs = tuple(outputs)
+    if any(k not in SHADE_OUTPUTS for k in outputs) or len(set(outputs)) != len(outputs):
+        raise ValueError(f"outputs {outputs}: a selection of {SHADE_OUTPUTS}")
+    if not clear and color is None:
+        raise ValueError("clear=False leaves the rays that miss unwritten: pass the color (and t) tensors to keep")
+    r = RayColors()
+    r.color = torch.empty((n,), dtype=torch.int32, device=o.device) if color is None else \
+        _given(torch, color, "color", torch.int32, n, device)
+    if t is not None:
+        r.t = _given(torch, t, "t", torch.float32, n, device)
+    elif "t" in outputs:
+        if not clear:
+            raise ValueError("clear=False with a fresh t tensor: pass t")
+        r.t = torch.empty((n,), dtype=torch.float32, device=o.device)
+    if "hit" in outputs:
+        r.hit = torch.empty((n,), dtype=torch.int32, device=o.device)
+    if "prim" in outputs:
+        r.prim = torch.empty((n,), dtype=torch.int64, device=o.device)
+    ptr = lambda x: x.data_ptr() if x is not None and x.numel() else None
+    if n == 0:
+        return r
+    with torch.cuda.device(device):
+        scene.shade_device(o.data_ptr(), d.data_ptr(), n, params, r.color.data_ptr(), t_ptr=ptr(r.t),
+                           hit_ptr=ptr(r.hit), prim_ptr=ptr(r.prim), tnear=tn, tfar=tf, tnear_ptr=ptr(tn_t),
+                           tfar_ptr=ptr(tf_t), clear=bool(clear),
                            stream=torch.cuda.current_stream(device).cuda_stream)
     return r
