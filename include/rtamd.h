@@ -601,6 +601,69 @@ int rt_sdf_mesh_points(rt_sdf_mesh *m, const float *p3, int64_t n, float *dist);
 /* SDFGrid values for a size[0] x size[1] x size[2] lattice over [-1,1]^3
  * (sample i at 2i/(size-1)-1, index (x*sy+y)*sz+z), host buffer. */
 int rt_sdf_mesh_grid(rt_sdf_mesh *m, const uint32_t size[3], float *values);
+/* Closest point and signed distance for points that are already on the GPU:
+ * n points in DEVICE buffers, queried in stream order on `stream` (hipStream_t
+ * or NULL). The definition is the project's own (oracle/cpuref.cpp, sdfref;
+ * the reference has no such query). Point i, p = d_point[3i..3i+2], with
+ * r_i = d_radius ? d_radius[i] : radius:
+ *
+ *   r2 = r_i * r_i
+ *   for every triangle T = (a, b, c) of the mesh, in original (OBJ face) order:
+ *     (q, feat) = the closest point of T to p and its Voronoi region
+ *                 (sdfref::closest: Ericson, Real-Time Collision Detection
+ *                 5.1.5, f32, op for op)
+ *     d2 = dot(p - q, p - q)           (x*x + y*y + z*z left to right, unfused)
+ *     T is a candidate iff r_i >= 0 && d2 <= r2
+ *   the winner is the candidate with the least (d2, triangle id),
+ *   lexicographically
+ *
+ * so a NaN radius, a negative radius or a NaN point has no candidate, and
+ * radius = +inf is the unbounded query. With a winner: d_dist[i] = sqrt(d2),
+ * negated where dot(p - q, N) < 0 for N the angle-weighted pseudonormal of
+ * region `feat` of the winner (rt_sdf_mesh_points' sign; RT_POINTS_UNSIGNED:
+ * never negated); d_closest[3i..] = q; d_prim[i] = the winner's original
+ * triangle index; d_feature[i] = feat. Without one: d_dist[i] = +inf,
+ * d_closest[3i..] = p (copied bit for bit), d_prim[i] = -1, d_feature[i] = -1.
+ * With radius = +inf and no flag, d_dist is bit for bit what
+ * rt_sdf_mesh_points returns for the same points.
+ *
+ * Exactness: the kernel walks the BVH8 and skips a box whose squared distance
+ * exceeds (sqrt(best d2 so far, or r2) + 1e-5)^2. The absolute slack of 1e-5
+ * covers the f32 rounding of the triangle test for points and meshes in about
+ * [-1,1]^3; that is the domain in which the result is the loop
+ * above bit for bit, for this entry as for rt_sdf_mesh_points and _grid.
+ *
+ * The call only launches on `stream`: no allocation, no copy, no host
+ * synchronisation. The handle's device must be the current one. An output
+ * left NULL is neither written nor computed: without d_dist, or with
+ * RT_POINTS_UNSIGNED, no sign is computed and the pseudonormals are not read.
+ * n == 0 launches nothing; n is limited as for rt_trace_rays_device. The
+ * kernel only reads the handle's immutable arrays, so calls on different
+ * streams may overlap; the handle must outlive the work queued with it
+ * (rt_sdf_mesh_destroy does not wait for the caller's streams).
+ * RT_E_INVALID, with nothing launched: a NULL handle or batch, n < 0, a NULL
+ * d_point with n > 0, all four outputs NULL, an unknown flag bit, and a
+ * `radius` that is NaN or negative when d_radius is NULL. */
+typedef struct rt_point_batch {
+  int64_t n;              /* points */
+  const float *d_point;   /* float[3n], device */
+  const float *d_radius;  /* float[n] per-point search radius, or NULL: use radius */
+  float radius;           /* +inf = unbounded */
+  float   *d_dist;        /* outputs, device; each may be NULL = not wanted, not all */
+  float   *d_closest;     /* float[3n] */
+  int64_t *d_prim;        /* original triangle index (OBJ face order), -1 = none */
+  int32_t *d_feature;     /* 0..2 vertex a,b,c; 3 ab; 4 ac; 5 bc; 6 face; -1 = none */
+} rt_point_batch;
+#define RT_POINTS_UNSIGNED 1u   /* d_dist = sqrt(d2), no sign; the pseudonormals are not read */
+int rt_sdf_mesh_points_device(rt_sdf_mesh *m, const rt_point_batch *b, uint32_t flags, void *stream);
+/* rt_sdf_mesh_grid into a DEVICE buffer of size[0]*size[1]*size[2] floats: the
+ * same size checks, the same bits, the same kernel, queued on `stream`, and
+ * nothing else happens (no allocation, no copy, no host synchronisation). The
+ * handle's device must be the current one and the handle must outlive the
+ * queued work. */
+int rt_sdf_mesh_grid_device(rt_sdf_mesh *m, const uint32_t size[3], float *d_values, void *stream);
+/* HIP device the handle's arrays live on (the one current at rt_sdf_mesh_create). */
+int rt_sdf_mesh_device(const rt_sdf_mesh *m);
 /* Sparse SDFOctree of max depth `depth` (36-byte nodes, BFS, 8 children
  * contiguous): a node is refined when |sdf(centre)| <= its half-diagonal;
  * unrefined nodes are empty leaves (values 1000); depth-`depth` nodes are

@@ -12,6 +12,8 @@
 // point and its region follow Ericson (RTCD 5.1.5) op for op; the sign comes
 // from the host-computed pseudonormal of the closest feature (rt_meshops.cpp).
 // Lattice queries map a 4x4x4 brick of samples to each 64-lane wave.
+// The handle and the pieces of the walk that the point queries on device
+// buffers share (rt_points.hip) are in rt_points.h.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -24,88 +26,14 @@
 #include "rt_host.h"
 #include "rt_layout.h"
 #include "rt_math.h"
+#include "rt_points.h"
 
 using namespace rtd;
-
-struct rt_sdf_mesh {
-  rth::SdfMeshHost host;
-  rtl::GNode *d_nodes = nullptr;
-  float4 *d_tri = nullptr;
-  float4 *d_pn = nullptr;
-  uint32_t root = rtl::kInvalidChild;
-  int32_t stack_cap = 0;
-  int device = 0;
-  int32_t oct_depth = -1;          // octree cache (two-call protocol of rt_sdf_mesh_octree)
-  std::vector<uint8_t> oct_nodes;
-  // point queries: the handle's own non-blocking stream, and pinned host /
-  // device staging for up to q_cap points, reused across calls
-  hipStream_t qs = nullptr;
-  float *h_stage = nullptr;  // q_cap * 4 floats: points (3 per point), then distances
-  float *d_p3 = nullptr, *d_out = nullptr;
-  int64_t q_cap = 0;
-};
+using namespace rtsdf;
 
 namespace {
 
-constexpr int kWave = 64;
 thread_local std::string g_stale_seen;  // the last stale error a query found (rtx_sdf_last_stale)
-
-struct SdfDev {
-  const rtl::GNode *nodes;
-  const float4 *tri;
-  const float4 *pn;
-  uint32_t root;
-};
-
-// Ericson, Real-Time Collision Detection 5.1.5 ClosestPtPointTriangle, with
-// the Voronoi region reported: 0..2 vertex a,b,c; 3 ab; 4 ac; 5 bc; 6 face.
-__device__ __forceinline__ f3 closest_on_tri(f3 p, f3 a, f3 b, f3 c, int &feat) {
-  const f3 ab = b - a, ac = c - a, ap = p - a;
-  const float d1 = dot(ab, ap), d2 = dot(ac, ap);
-  if (d1 <= 0.0f && d2 <= 0.0f) { feat = 0; return a; }
-  const f3 bp = p - b;
-  const float d3 = dot(ab, bp), d4 = dot(ac, bp);
-  if (d3 >= 0.0f && d4 <= d3) { feat = 1; return b; }
-  const float vc = d1 * d4 - d3 * d2;
-  if (vc <= 0.0f && d1 >= 0.0f && d3 <= 0.0f) {
-    const float v = d1 / (d1 - d3);
-    feat = 3;
-    return a + ab * v;
-  }
-  const f3 cp = p - c;
-  const float d5 = dot(ab, cp), d6 = dot(ac, cp);
-  if (d6 >= 0.0f && d5 <= d6) { feat = 2; return c; }
-  const float vb = d5 * d2 - d1 * d6;
-  if (vb <= 0.0f && d2 >= 0.0f && d6 <= 0.0f) {
-    const float w = d2 / (d2 - d6);
-    feat = 4;
-    return a + ac * w;
-  }
-  const float va = d3 * d6 - d5 * d4;
-  if (va <= 0.0f && (d4 - d3) >= 0.0f && (d5 - d6) >= 0.0f) {
-    const float w = (d4 - d3) / ((d4 - d3) + (d5 - d6));
-    feat = 5;
-    return b + (c - b) * w;
-  }
-  const float denom = 1.0f / (va + vb + vc);
-  const float v = vb * denom, w = vc * denom;
-  feat = 6;
-  return a + ab * v + ac * w;
-}
-
-// bx: xMin xMax yMin yMax zMin zMax (rt_layout.h GNode)
-__device__ __forceinline__ float box_d2(const float *bx, f3 p) {
-  const float dx = fmaxf(fmaxf(bx[0] - p.x, p.x - bx[1]), 0.0f);
-  const float dy = fmaxf(fmaxf(bx[2] - p.y, p.y - bx[3]), 0.0f);
-  const float dz = fmaxf(fmaxf(bx[4] - p.z, p.z - bx[5]), 0.0f);
-  return dx * dx + dy * dy + dz * dz;
-}
-
-__device__ __forceinline__ float prune_bound(float best) {
-  if (!(best < kInf)) return kInf;
-  const float r = __builtin_sqrtf(best) + 1e-5f;
-  return r * r;
-}
 
 // Signed distance at p. st_d / st_w: this lane's LDS stack columns (stride 64).
 __device__ float sdf_query(const SdfDev &m, f3 p, float *st_d, uint32_t *st_w) {
@@ -219,9 +147,16 @@ int upload(T **d, const T *h, size_t n) {
   return RT_OK;
 }
 
-SdfDev dev_of(const rt_sdf_mesh *m) { return SdfDev{m->d_nodes, m->d_tri, m->d_pn, m->root}; }
-
-size_t lds_bytes(const rt_sdf_mesh *m) { return (size_t)m->stack_cap * kWave * 8; }
+// The size checks of a lattice query, and its launch's workgroups: one 4x4x4
+// brick of samples per wave.
+int grid_blocks(const uint32_t size[3], uint32_t &blocks) {
+  for (int a = 0; a < 3; ++a)
+    if (size[a] < 2 || size[a] > 4096) return rterr::set(RT_E_INVALID, "grid size must be in [2, 4096]");
+  const uint64_t b = (uint64_t)((size[0] + 3) / 4) * ((size[1] + 3) / 4) * ((size[2] + 3) / 4);
+  if (b > 0x7FFFFFFFull) return rterr::set(RT_E_INVALID, "grid too large");
+  blocks = (uint32_t)b;
+  return RT_OK;
+}
 
 // Points per staged batch of a host query (16 MiB of pinned staging at most).
 constexpr int64_t kQueryBatch = 1 << 20;
@@ -345,16 +280,14 @@ int rt_sdf_mesh_points(rt_sdf_mesh *m, const float *p3, int64_t n, float *dist) 
 
 int rt_sdf_mesh_grid(rt_sdf_mesh *m, const uint32_t size[3], float *values) {
   if (!m || !size || !values) return rterr::set(RT_E_INVALID, "bad arguments");
-  for (int a = 0; a < 3; ++a)
-    if (size[a] < 2 || size[a] > 4096) return rterr::set(RT_E_INVALID, "grid size must be in [2, 4096]");
+  uint32_t blocks = 0;
+  if (int rc = grid_blocks(size, blocks)) return rc;
   const int64_t n = (int64_t)size[0] * size[1] * size[2];
-  const uint64_t blocks = (uint64_t)((size[0] + 3) / 4) * ((size[1] + 3) / 4) * ((size[2] + 3) / 4);
-  if (blocks > 0x7FFFFFFFull) return rterr::set(RT_E_INVALID, "grid too large");
   g_stale_seen = rterr::take_stale();
   HIP_TRY(hipSetDevice(m->device));
   float *d = nullptr;
   HIP_TRY(hipMalloc(&d, (size_t)n * 4));
-  hipLaunchKernelGGL(sdf_kernel<true>, dim3((uint32_t)blocks), dim3(kWave), lds_bytes(m), 0, dev_of(m), nullptr,
+  hipLaunchKernelGGL(sdf_kernel<true>, dim3(blocks), dim3(kWave), lds_bytes(m), 0, dev_of(m), nullptr,
                      n, size[0], size[1], size[2], m->stack_cap, d);
   hipError_t e = hipGetLastError();
   if (e == hipSuccess) e = hipDeviceSynchronize();
@@ -363,6 +296,19 @@ int rt_sdf_mesh_grid(rt_sdf_mesh *m, const uint32_t size[3], float *values) {
   if (e != hipSuccess) return rterr::set(RT_E_DEVICE, std::string("sdf grid: ") + hipGetErrorString(e));
   return RT_OK;
 }
+
+int rt_sdf_mesh_grid_device(rt_sdf_mesh *m, const uint32_t size[3], float *d_values, void *stream) {
+  if (!m || !size || !d_values) return rterr::set(RT_E_INVALID, "bad arguments");
+  uint32_t blocks = 0;
+  if (int rc = grid_blocks(size, blocks)) return rc;
+  hipLaunchKernelGGL(sdf_kernel<true>, dim3(blocks), dim3(kWave), lds_bytes(m), (hipStream_t)stream, dev_of(m),
+                     nullptr, (int64_t)size[0] * size[1] * size[2], size[0], size[1], size[2], m->stack_cap,
+                     d_values);
+  HIP_TRY(hipGetLastError());
+  return RT_OK;
+}
+
+int rt_sdf_mesh_device(const rt_sdf_mesh *m) { return m ? m->device : RT_E_INVALID; }
 
 int rt_sdf_mesh_octree(rt_sdf_mesh *m, int32_t depth, int64_t *count, void *nodes36) {
   if (!m || !count) return rterr::set(RT_E_INVALID, "bad arguments");

@@ -19,6 +19,7 @@ RT_FLAG_TILE_NATURAL = 2
 RT_FLAG_HITS_ONLY = 4
 RT_RAYS_ANY_HIT = 1
 RT_SHADE_CLEAR = 1
+RT_POINTS_UNSIGNED = 1
 RT_MESH_DYNAMIC = 1
 RT_IPC_HANDLE_BYTES = 64
 RT_SCENE_MESH, RT_SCENE_GRID, RT_SCENE_OCTREE, RT_SCENE_INSTANCED = 1, 2, 3, 4
@@ -63,6 +64,13 @@ class RayBatch(C.Structure):
     _fields_ = [("n", C.c_int64), ("d_origin", C.c_void_p), ("d_dir", C.c_void_p), ("d_tnear", C.c_void_p),
                 ("d_tfar", C.c_void_p), ("tnear", C.c_float), ("tfar", C.c_float), ("d_hit", C.c_void_p),
                 ("d_t", C.c_void_p), ("d_normal", C.c_void_p), ("d_prim", C.c_void_p)]
+
+
+class PointBatch(C.Structure):
+    """rt_point_batch (include/rtamd.h): device pointers as integers, 0 / None = NULL."""
+    _fields_ = [("n", C.c_int64), ("d_point", C.c_void_p), ("d_radius", C.c_void_p), ("radius", C.c_float),
+                ("d_dist", C.c_void_p), ("d_closest", C.c_void_p), ("d_prim", C.c_void_p),
+                ("d_feature", C.c_void_p)]
 
 
 class Instance(C.Structure):
@@ -155,6 +163,9 @@ _SIGS = {
                                      C.POINTER(C.c_void_p)]),
     "rt_sdf_mesh_points": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "rt_sdf_mesh_grid": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_sdf_mesh_points_device": (C.c_int, [C.c_void_p, C.POINTER(PointBatch), C.c_uint32, C.c_void_p]),
+    "rt_sdf_mesh_grid_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_sdf_mesh_device": (C.c_int, [C.c_void_p]),
     "rt_sdf_mesh_octree": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.c_void_p]),
     "rt_sdf_mesh_destroy": (C.c_int, [C.c_void_p]),
     "rt_mesh_subdivide": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p,
@@ -202,6 +213,9 @@ _XSIGS = {
     "rtx_tlas_build_host": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
     "rtx_tlas_candidates": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_int32,
                                       C.c_void_p, C.c_int32]),
+    # unused LDS added to the point query's launches (occupancy measurements)
+    "rtx_set_points_lds_pad": (C.c_int, [C.c_int32]),
+    "rtx_sdf_mesh_lds_bytes": (C.c_int64, [C.c_void_p]),
 }
 
 

@@ -23,8 +23,8 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from ._lib import (RT_FLAG_CLEAR, RT_FLAG_HITS_ONLY, RT_INSTANCE_DISABLED, RT_INSTANCED_TLAS, RT_MESH_DYNAMIC, RT_RAYS_ANY_HIT,
-                   RT_SHADE_CLEAR, CameraState, Instance, RayBatch, RenderParams, RtError, Tile, check, lib)
+from ._lib import (RT_FLAG_CLEAR, RT_FLAG_HITS_ONLY, RT_INSTANCE_DISABLED, RT_INSTANCED_TLAS, RT_MESH_DYNAMIC,
+                   RT_POINTS_UNSIGNED, RT_RAYS_ANY_HIT, RT_SHADE_CLEAR, CameraState, Instance, PointBatch, RayBatch, RenderParams, RtError, Tile, check, lib)
 
 __all__ = [
     "ShadingMode", "SimpleMesh", "FrameBuffer", "Camera", "Renderer", "HitInfo", "IScene",
@@ -729,6 +729,33 @@ class SDFMesh:
         vals = np.empty(int(size[0]) * int(size[1]) * int(size[2]), np.float32)
         check(lib().rt_sdf_mesh_grid(self._h, _p(size), _p(vals)))
         return size, vals
+
+    def device(self) -> int:
+        """HIP device the mesh was prepared on."""
+        return int(lib().rt_sdf_mesh_device(self._h))
+
+    def points_device(self, point_ptr: int, n: int, *, radius: float = float("inf"), radius_ptr: int | None = None,
+                      dist_ptr: int | None = None, closest_ptr: int | None = None, prim_ptr: int | None = None,
+                      feature_ptr: int | None = None, unsigned: bool = False, stream: int | None = None):
+        """Closest point and signed distance on device buffers
+        (rt_sdf_mesh_points_device): n points at point_ptr (float32[3n], e.g.
+        a torch tensor's data_ptr()), queried in stream order on `stream`; the
+        call only launches. Outputs left None are neither computed nor written
+        (float32 dist, float32[3n] closest, int64 prim, int32 feature). Only
+        triangles within `radius` count (radius_ptr: float32[n], one per
+        point); a point without one gets +inf, itself, -1 and -1. unsigned:
+        the distance without its sign (the pseudonormals are not read)."""
+        b = PointBatch(int(n), point_ptr or None, radius_ptr or None, float(radius), dist_ptr or None,
+                       closest_ptr or None, prim_ptr or None, feature_ptr or None)
+        check(lib().rt_sdf_mesh_points_device(self._h, C.byref(b), RT_POINTS_UNSIGNED if unsigned else 0,
+                                              C.c_void_p(stream) if stream else None))
+
+    def grid_device(self, size, ptr: int, stream: int | None = None):
+        """grid() into a device buffer of sx*sy*sz float32 at `ptr`
+        (rt_sdf_mesh_grid_device), queued on `stream`; the call only launches."""
+        size = np.ascontiguousarray(np.broadcast_to(np.asarray(size, np.uint32), (3,)))
+        check(lib().rt_sdf_mesh_grid_device(self._h, _p(size), C.c_void_p(ptr) if ptr else None,
+                                            C.c_void_p(stream) if stream else None))
 
     def octree(self, depth: int) -> np.ndarray:
         """-> raw nodes, uint8 [count*36] (SDFOctreeNode records, BFS)."""

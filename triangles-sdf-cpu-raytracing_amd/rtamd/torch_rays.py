@@ -29,6 +29,14 @@ rt_shade_rays_device): eye_rays writes the frame's eye rays as a ray batch, and
 shade runs the reference's shading (Lambert with its shadow ray and reflection
 bounce, Color, Normal) on any rays, for every scene kind. Eye rays plus shade
 is a frame; for an rtamd.InstancedScene it is the way to a picture.
+
+    h = torch_rays.closest(sdf_mesh, points, radius=0.05, outputs=("dist", "closest", "prim"))
+    g = torch_rays.sdf_grid(sdf_mesh, (128, 128, 64))
+
+are the point queries of an rtamd.SDFMesh (rt_sdf_mesh_points_device,
+rt_sdf_mesh_grid_device): signed distance, closest point, triangle and Voronoi
+feature of points on the GPU, optionally only within a radius, and the
+SDFGrid lattice as a tensor.
 """
 from __future__ import annotations
 
@@ -38,6 +46,7 @@ from ._lib import lib
 
 OUTPUTS = ("hit", "t", "normal", "prim")
 SHADE_OUTPUTS = ("color", "t", "hit", "prim")
+POINT_OUTPUTS = ("dist", "closest", "prim", "feature")
 
 
 @dataclass
@@ -58,6 +67,16 @@ class RayColors:
     t: "object | None" = None        # torch.float32
     hit: "object | None" = None      # torch.int32, 1 where a colour was stored
     prim: "object | None" = None     # torch.int64, the first intersection's primitive id (-2 plane, -1 miss)
+
+
+@dataclass
+class PointHits:
+    """The requested outputs of one closest() ([N] tensors on the points'
+    device; closest is [N,3]); the others are None."""
+    dist: "object | None" = None     # torch.float32, signed (or |.| with unsigned); +inf where nothing is within the radius
+    closest: "object | None" = None  # torch.float32 [N,3], the point itself where nothing is within the radius
+    prim: "object | None" = None     # torch.int64, original triangle index, -1 = none
+    feature: "object | None" = None  # torch.int32, 0..2 vertex a,b,c; 3 ab; 4 ac; 5 bc; 6 face; -1 = none
 
 
 def _rays(torch, x, what, device):
@@ -285,3 +304,57 @@ def shade(scene, origins, dirs, params, tnear=0.01, tfar=100.0, clear=True, colo
                            tfar_ptr=ptr(tf_t), clear=bool(clear),
                            stream=torch.cuda.current_stream(device).cuda_stream)
     return r
+
+
+def closest(sdf_mesh, points, radius=float("inf"), outputs=("dist",), unsigned=False) -> PointHits:
+    """The closest triangle of `sdf_mesh` (an rtamd.SDFMesh) to each of N
+    points: a contiguous float32 [N,3] tensor on the mesh's device. radius: a
+    float (>= 0, +inf = unbounded) or a float32 [N] tensor; only triangles
+    within it count, and a point without one (also one with a negative or NaN
+    radius) gets dist +inf, itself as closest, prim -1 and feature -1. Only
+    the outputs named are computed and allocated (torch.empty); unsigned
+    gives the distance without its sign. The exact definition is
+    include/rtamd.h's. Queued on torch.cuda.current_stream(); raises
+    ValueError on a bad tensor or radius before anything is launched."""
+    import math
+
+    import torch
+
+    device = sdf_mesh.device()
+    p = _rays(torch, points, "points", device)
+    n = p.shape[0]
+    r, r_t = _interval(torch, radius, "radius", n, device)
+    if r_t is None and (math.isnan(r) or r < 0.0):
+        raise ValueError(f"radius {r}: expected >= 0 (inf = unbounded)")
+    outputs = tuple(outputs)
+    if not outputs or any(k not in POINT_OUTPUTS for k in outputs) or len(set(outputs)) != len(outputs):
+        raise ValueError(f"outputs {outputs}: a non-empty selection of {POINT_OUTPUTS}")
+    kinds = {"dist": ((n,), torch.float32), "closest": ((n, 3), torch.float32), "prim": ((n,), torch.int64),
+             "feature": ((n,), torch.int32)}
+    h = PointHits(**{k: torch.empty(kinds[k][0], dtype=kinds[k][1], device=p.device) for k in outputs})
+    ptr = lambda x: x.data_ptr() if x is not None and x.numel() else None
+    if n == 0:
+        return h
+    with torch.cuda.device(device):
+        sdf_mesh.points_device(p.data_ptr(), n, radius=r, radius_ptr=ptr(r_t), dist_ptr=ptr(h.dist),
+                               closest_ptr=ptr(h.closest), prim_ptr=ptr(h.prim), feature_ptr=ptr(h.feature),
+                               unsigned=bool(unsigned), stream=torch.cuda.current_stream(device).cuda_stream)
+    return h
+
+
+def sdf_grid(sdf_mesh, size):
+    """SDFMesh.grid as a tensor: the signed distance on a size[0] x size[1] x
+    size[2] lattice over [-1,1]^3 (sample i at 2i/(size-1)-1 per axis; an int
+    means a cube), float32 [sx, sy, sz] on the mesh's device, written by one
+    kernel on torch.cuda.current_stream() (rt_sdf_mesh_grid_device). Raises
+    ValueError on a size outside [2, 4096] before anything is launched."""
+    import torch
+
+    device = sdf_mesh.device()
+    size = tuple(int(x) for x in ((size,) * 3 if isinstance(size, int) else size))
+    if len(size) != 3 or any(x < 2 or x > 4096 for x in size):
+        raise ValueError(f"size {size}: three lattice sizes in [2, 4096]")
+    g = torch.empty(size, dtype=torch.float32, device=torch.device("cuda", device))
+    with torch.cuda.device(device):
+        sdf_mesh.grid_device(size, g.data_ptr(), stream=torch.cuda.current_stream(device).cuda_stream)
+    return g
