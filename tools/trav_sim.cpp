@@ -25,6 +25,11 @@
 // LDS can take off the vector L1; see share_model below
 // (profiles/r16/trav_sim_share.txt).
 //
+// trav_sim --order [obj[@N] W H [px py pz]]: per wave-level expansion, the most
+// children any lane enters and whether a lane's entered children tie -- which
+// ordering path the expansion takes; see order_model below
+// (profiles/r21/trav_sim_order.txt).
+//
 // build: g++ -O2 -std=c++17 -Iinclude tools/trav_sim.cpp
 //          -Ltriangles-sdf-cpu-raytracing_amd/lib -lrtamd -Wl,-rpath,... -o /tmp/trav_sim
 #include <algorithm>
@@ -223,6 +228,8 @@ struct Iter {
   char top;      // 'I', 'L' (leaf, either batch count), 'P'
   bool second;   // the tail needs a global round trip after the top part's
   uint32_t node = 0;  // 'I': the node expanded (--share)
+  uint8_t nent = 0;   // 'I': children entered (--order)
+  uint8_t tie = 0;    // 'I': bit 0 two entered t equal, bit 1 equal in the top 29 bits (--order)
 };
 struct RayCounts {
   double inner = 0, leaf = 0, two = 0, pushed = 0, resume_visit = 0, resume_prune = 0, prune_second = 0,
@@ -235,6 +242,7 @@ struct Frame {
   float t[8];
   int n, next;
   float best;
+  uint8_t tie;  // see Iter::tie
 };
 
 // the sorted, entered children of an inner node (expand_node)
@@ -258,6 +266,13 @@ Frame expand(uint32_t ni, V3 o, V3 inv, float tn, float tf) {
   f.best = INFINITY;
   for (int i = 0; i < 8; ++i)
     if (!(t[i] < 0.0f) && (uint32_t)id[i] < nd.n) { f.id[f.n] = id[i]; f.t[f.n] = t[i]; ++f.n; }
+  for (int i = 1; i < f.n; ++i) {  // sorted: ties are neighbours
+    uint32_t a, b;
+    std::memcpy(&a, &f.t[i - 1], 4);
+    std::memcpy(&b, &f.t[i], 4);
+    if (a == b) f.tie |= 1;
+    if ((a >> 3) == (b >> 3)) f.tie |= 2;
+  }
   return f;
 }
 
@@ -291,6 +306,8 @@ void run_ray(V3 o, V3 d, V3 inv, float tn, float tf, int variant, std::vector<It
         rc.inner += 1;
         Frame f = expand((uint32_t)word, o, inv, tn, tf);
         rc.two += f.n >= 2;
+        it.nent = (uint8_t)f.n;
+        it.tie = f.tie;
         if (f.n != 0) {
           if (st.back().next == st.back().n) {  // tail call: the top frame is replaced
             if (st.size() >= 2 && st.back().best < st[st.size() - 2].best) st[st.size() - 2].best = st.back().best;
@@ -573,11 +590,121 @@ int share_model(Eye eye, V3 org, int W, int H) {
   return 0;
 }
 
+// ---- --order: which ordering path an expansion takes -----------------------
+// The same lockstep as --share. Per wave-level expansion: the largest number
+// of children any expanding lane enters (the shipped shortcut takes waves with
+// at most 2 and no tie), and whether any lane has two entered children with
+// equal t, exactly or in the top 29 bits (the keyed order, expand_keyed in
+// csrc/rt_scenes.h, sends such a wave to sort8). The same figures over the
+// expansions in which a lane of a long ray expands: a ray whose chain is
+// kLongChain loop iterations (mesh_run's units of work) or more, the rays a
+// launch's tail is made of.
+// Then VALU instructions per expansion for the three forms, from the counts
+// below (read off `make isa`, render_persist_kernel<MeshS, 4, false>).
+constexpr double kLongChain = 64;
+struct OrderBin {
+  double n = 0, hist[9] = {}, tie_exact = 0, tie29 = 0, le2_notie = 0;
+};
+// VALU per expansion block. Shipped before round 21: the slab tests and the
+// shortcut's test, then the shortcut's tail or the sorted tail. Keyed: 8 slab
+// tests of 18 (144), the keys (8), the network (38), the tie check (11), then
+// count, list and first t (36); its fallback computes the slab tests again in
+// the shipped form (160) and runs the sorted tail. Behind the shortcut (built,
+// measured, not kept): the shortcut's test on bit patterns (about 50).
+constexpr double kShipCommon = 211, kShipShort = 27, kShipSorted = 137;
+constexpr double kKeySlab = 144, kKeyOrder = 93, kKeyShortTest = 50, kKeyShortTail = 24;
+constexpr double kKeyFallback = 160 + kShipSorted;
+
+template <class Eye>
+int order_model(Eye eye, V3 org, int W, int H) {
+  OrderBin all, tail;
+  double wave_iters = 0, longest = 0, nlong = 0;
+  RayCounts rc;
+  for (int ty = 0; ty < (H + 7) / 8; ++ty)
+    for (int tx = 0; tx < (W + 7) / 8; ++tx) {
+      std::vector<std::vector<Iter>> s(64);
+      bool lng[64] = {};
+      bool any = false;
+      for (int l = 0; l < 64; ++l) {
+        const int x = tx * 8 + (l & 7), yo = ty * 8 + (l >> 3), y = H - yo - 1;
+        if (x >= W || yo >= H) continue;
+        const V3 d = eye(x, y);
+        const V3 inv{1.0f / d.x, 1.0f / d.y, 1.0f / d.z};
+        run_ray(org, d, inv, 0.01f, 100.0f, 0, s[l], rc);
+        any |= !s[l].empty();
+        lng[l] = (double)s[l].size() >= kLongChain;
+        longest = std::max(longest, (double)s[l].size());
+        nlong += lng[l];
+      }
+      if (!any) continue;
+      std::vector<size_t> pos(64, 0);
+      for (;;) {
+        int nI = 0, nL = 0, live = 0;
+        for (int k = 0; k < 64; ++k) {
+          if (pos[k] >= s[k].size()) continue;
+          ++live;
+          nI += s[k][pos[k]].top == 'I';
+          nL += s[k][pos[k]].top == 'L';
+        }
+        if (!live) break;
+        const bool waitL = nL < nI, waitI = !waitL && nI < nL;
+        int mx = -1, tie = 0;
+        bool has_long = false;
+        for (int k = 0; k < 64; ++k) {
+          if (pos[k] >= s[k].size()) continue;
+          const Iter &i = s[k][pos[k]];
+          if ((i.top == 'L' && waitL) || (i.top == 'I' && waitI)) continue;
+          if (i.top == 'I') {
+            mx = std::max(mx, (int)i.nent);
+            tie |= i.tie;
+            has_long |= lng[k];
+          }
+          ++pos[k];
+        }
+        wave_iters += 1;
+        if (mx < 0) continue;
+        for (OrderBin *b : {&all, has_long ? &tail : (OrderBin *)nullptr}) {
+          if (!b) continue;
+          b->n += 1;
+          b->hist[mx] += 1;
+          b->tie_exact += (tie & 1) != 0;
+          b->tie29 += (tie & 2) != 0;
+          b->le2_notie += mx <= 2 && !(tie & 1);
+        }
+      }
+    }
+  std::printf("frame %d x %d, camera (%g, %g, %g), wave iterations %.0f\n", W, H, org.x, org.y, org.z, wave_iters);
+  for (int part = 0; part < 2; ++part) {
+    const OrderBin &b = part ? tail : all;
+    if (part) std::printf("rays of %.0f iterations or more: %.0f (longest ray %.0f); ", kLongChain, nlong, longest);
+    std::printf("%s: wave-level expansions %.0f\n", part ? "expansions in which one of them expands" : "whole frame", b.n);
+    if (b.n == 0) continue;
+    std::printf("  most children any lane enters:");
+    for (int i = 0; i <= 8; ++i) std::printf(" %d:%.0f", i, b.hist[i]);
+    std::printf("\n  shortcut (<= 2 children, no exact tie) %.0f = %.1f %%, sorted tail %.0f = %.1f %%\n", b.le2_notie,
+                100 * b.le2_notie / b.n, b.n - b.le2_notie, 100 * (1 - b.le2_notie / b.n));
+    std::printf("  a lane ties exactly %.0f = %.2f %%, in the top 29 bits %.0f = %.2f %% (the keyed order's fallback)\n",
+                b.tie_exact, 100 * b.tie_exact / b.n, b.tie29, 100 * b.tie29 / b.n);
+    const double ps = b.le2_notie / b.n, pf = b.tie29 / b.n;
+    const double ship = kShipCommon + ps * kShipShort + (1 - ps) * kShipSorted;
+    const double k1 = kKeySlab + kKeyShortTest + ps * kKeyShortTail + (1 - ps) * kKeyOrder + pf * kKeyFallback;
+    const double k2 = kKeySlab + kKeyOrder + pf * kKeyFallback;
+    std::printf("  modelled VALU per expansion: shipped %.1f, keys behind the shortcut %.1f, keys only %.1f\n", ship, k1, k2);
+    // keys only saves ship - (slab + order) per expansion and pays the fallback
+    // on the share pf: level with the shipped form at pf = saving / fallback
+    const double S = ship - (kKeySlab + kKeyOrder);
+    std::printf("  break-even fallback share, keys only: %.1f / %.0f = %.1f %% of the expansions; here %.2f %%\n", S,
+                kKeyFallback, 100 * S / kKeyFallback, 100 * pf);
+  }
+  return 0;
+}
+
 }  // namespace
 
 int main(int argc, char **argv) {
   const bool resume = argc > 1 && std::strcmp(argv[1], "--resume") == 0;
-  const bool share = argc > 1 && std::strcmp(argv[1], "--share") == 0;
+  const bool order = argc > 1 && std::strcmp(argv[1], "--order") == 0;
+  const bool share = order || (argc > 1 && std::strcmp(argv[1], "--share") == 0);  // the same arguments
   if (resume || share) { --argc; ++argv; }
   const char *obj = argc > 1 ? argv[1] : "data/_unpacked/stanford-bunny.obj";
   const int W = argc > 2 ? std::atoi(argv[2]) : 1920, H = argc > 3 ? std::atoi(argv[3]) : 1080;
@@ -641,6 +768,7 @@ int main(int argc, char **argv) {
               vi[2] * dd.x + vi[6] * dd.y + vi[10] * dd.z};
   };
   if (resume) return resume_model(eye, V3{pos[0], pos[1], pos[2]}, W, H);
+  if (order) return order_model(eye, V3{pos[0], pos[1], pos[2]}, W, H);
   if (share) return share_model(eye, V3{pos[0], pos[1], pos[2]}, W, H);
   Cost c[3];
   double both = 0, iters0 = 0, steps = 0;

@@ -244,6 +244,30 @@ int rtx_grp_test(const float *keys, int32_t n, float *st, uint32_t *sid, float *
   return RT_OK;
 }
 
+// key_order (rt_math.h, the keyed expansion's visit order) for tests, host
+// only: n vectors of 8 entry distances as slab_key hands them over (t < 0: a
+// miss, which takes its slot's miss constant) -> per vector the packed list,
+// the count, the bits of the first child's t and the tie flag. Not part of
+// include/rtamd.h.
+int rtx_expand_order(const float *t, int64_t n, uint32_t *list, uint32_t *cnt, uint32_t *tfirst, uint8_t *tie) {
+  if (!t || n < 0 || !list || !cnt || !tfirst || !tie) return set_err(RT_E_INVALID, "bad arguments");
+  for (int64_t i = 0; i < n; ++i) {
+    uint32_t tb[8];
+    for (uint32_t c = 0; c < 8; ++c) {
+      const float v = t[8 * i + c];
+      uint32_t b;
+      __builtin_memcpy(&b, &v, 4);
+      tb[c] = v < 0.0f ? rtd::order_miss_bits(c) : b;
+    }
+    const rtd::KeyOrder r = rtd::key_order(tb);
+    list[i] = r.list;
+    cnt[i] = r.cnt;
+    tfirst[i] = r.tfirst;
+    tie[i] = r.tie ? 1 : 0;
+  }
+  return RT_OK;
+}
+
 // Exhaustive check of rtm::rcp_rn (rt_rcp.h, tri_t's reciprocal) on this
 // device: every float x with 1e-8 <= |x| < 2^126 against the IEEE division
 // 1 / x. *checked = floats in that range, *bad = mismatches, *first_bad = the

@@ -163,6 +163,86 @@ __device__ __forceinline__ void sort8(float t[8], uint32_t id[8]) {
 }
 #undef RTD_CSWAP
 
+// ---- visit order from packed keys (expand_loaded<true, true>) ---------------
+// sort8 leaves the entered children (t >= 0) in ascending t, and only among
+// equal t is the order the network's own. An entered child's t is at least
+// tNear > 0, a positive float, so its bit pattern orders as an unsigned integer:
+// key[c] = (bits(t[c]) & ~7) | c carries the child's slot through the same 19
+// comparators as unsigned min / max on 8 registers, with no id array. Two
+// entered children whose keys agree above bit 2 (equal t, or t within 7 ulp)
+// are a tie: after the network they are neighbours, and the caller then takes
+// sort8 itself. A miss is t < 0 as before, but one constant per slot, so that
+// misses sort behind every entered child and never look like a tie.
+__host__ __device__ __forceinline__ constexpr uint32_t order_miss_bits(uint32_t c) {
+  return 0xBF800000u | (c << 3);  // -1.0f and its next 7 neighbours at 8 ulp steps
+}
+__host__ __device__ __forceinline__ constexpr uint32_t umin_u32(uint32_t a, uint32_t b) { return a < b ? a : b; }
+__host__ __device__ __forceinline__ constexpr uint32_t umax_u32(uint32_t a, uint32_t b) { return a < b ? b : a; }
+struct KeyOrder {
+  uint32_t list;      // entered children in visit order, 3 bits each, first in the low bits
+  uint32_t cnt;       // entered children
+  uint32_t tfirst;    // bits of the first child's entry t (exact; 0.0f with none)
+  uint32_t first_id;  // the first child's slot (0 with none)
+  bool tie;           // two entered children agree in the top 29 bits of t: the rest is not to be used
+};
+#define RTD_KSWAP(a, b)                                  \
+  {                                                      \
+    const uint32_t lo_ = umin_u32(k[a], k[b]);           \
+    k[b] = umax_u32(k[a], k[b]);                         \
+    k[a] = lo_;                                          \
+  }
+// tb[c]: bits of slot c's entry t, or order_miss_bits(c) for a miss.
+__host__ __device__ __forceinline__ constexpr KeyOrder key_order(const uint32_t (&tb)[8]) {
+  uint32_t k[8] = {};
+  for (int c = 0; c < 8; ++c) k[c] = (tb[c] & ~7u) | (uint32_t)c;
+  // the exact entry t of the first child: the keys have lost 3 bits
+  const uint32_t tmin = umin_u32(umin_u32(umin_u32(tb[0], tb[1]), umin_u32(tb[2], tb[3])),
+                                 umin_u32(umin_u32(tb[4], tb[5]), umin_u32(tb[6], tb[7])));
+  RTD_KSWAP(0, 1); RTD_KSWAP(2, 3); RTD_KSWAP(4, 5); RTD_KSWAP(6, 7);
+  RTD_KSWAP(0, 2); RTD_KSWAP(1, 3); RTD_KSWAP(4, 6); RTD_KSWAP(5, 7);
+  RTD_KSWAP(1, 2); RTD_KSWAP(5, 6); RTD_KSWAP(0, 4); RTD_KSWAP(3, 7);
+  RTD_KSWAP(1, 5); RTD_KSWAP(2, 6); RTD_KSWAP(1, 4); RTD_KSWAP(3, 6);
+  RTD_KSWAP(2, 4); RTD_KSWAP(3, 5); RTD_KSWAP(3, 4);
+  // neighbours that differ only below bit 3 (two misses differ above it, a
+  // miss and an entered child in the sign)
+  uint32_t x = k[0] ^ k[1];
+  for (int i = 1; i < 7; ++i) x = umin_u32(x, k[i] ^ k[i + 1]);
+  // misses (sign set) are the sorted order's suffix
+  uint32_t miss = 0, all = 0;
+  for (int i = 0; i < 8; ++i) {
+    miss += k[i] >> 31;
+    all |= (k[i] & 7u) << (3 * i);
+  }
+  KeyOrder r{};
+  r.cnt = 8u - miss;
+  r.list = all & ((1u << (3u * r.cnt)) - 1u);
+  r.tfirst = r.cnt ? tmin : 0u;
+  r.first_id = r.list & 7u;
+  r.tie = x < 8u;
+  return r;
+}
+#undef RTD_KSWAP
+
+// slab_fast for key_order, slot c: the bits of the entry t, or the slot's miss
+// constant. Valid with tNear > 0 (besides slab_fast's finite 1/d): tMin is then
+// at least tNear (max returns its non-NaN operand), so tMax < 0 implies
+// tMin > tMax and the miss test is that one comparison. slab_fast's form
+// max(tMin, 0) > tMax, which the compiler makes of the two tests, puts a
+// canonicalising v_max_f32 x, x in front of the v_max3 result in every box;
+// a comparison needs none.
+__device__ __forceinline__ uint32_t slab_key(uint32_t c, float bx0, float by0, float bz0, float bx1, float by1,
+                                             float bz1, f3 o, f3 inv, float tNear, float tFar) {
+  const v2f tx = (v2f{bx0, bx1} - v2f{o.x, o.x}) * v2f{inv.x, inv.x};
+  const v2f ty = (v2f{by0, by1} - v2f{o.y, o.y}) * v2f{inv.y, inv.y};
+  const v2f tz = (v2f{bz0, bz1} - v2f{o.z, o.z}) * v2f{inv.z, inv.z};
+  const float t1x = tx.x, t2x = tx.y, t1y = ty.x, t2y = ty.y, t1z = tz.x, t2z = tz.y;
+  const float tMin = __builtin_fmaxf(__builtin_fmaxf(__builtin_fminf(t1x, t2x), __builtin_fminf(t1y, t2y)),
+                                     __builtin_fmaxf(__builtin_fminf(t1z, t2z), tNear));
+  const float tMax = __builtin_fminf(__builtin_fminf(__builtin_fmaxf(t1x, t2x), __builtin_fmaxf(t1y, t2y)),
+                                     __builtin_fminf(__builtin_fmaxf(t1z, t2z), tFar));
+  return (tMin > tMax) ? order_miss_bits(c) : __float_as_uint(tMin);
+}
+
 // Column-major 4x4 (LiteMath m_col): M(r,c) = m[c*4+r]; mul as LiteMath
 // (row r: M(r,0)*v.x + M(r,1)*v.y + M(r,2)*v.z + M(r,3)*v.w, left to right).
 struct f4 {

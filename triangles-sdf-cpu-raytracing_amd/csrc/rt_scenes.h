@@ -222,6 +222,34 @@ __device__ __forceinline__ void node_load_shared(const rtl::GNode *__restrict__ 
   cw1 = uint4{__float_as_uint(w1.x), __float_as_uint(w1.y), __float_as_uint(w1.z), __float_as_uint(w1.w)};
 }
 
+// The network's part of an expansion, on the 8 entry distances: sort8, the
+// packed list of the entered children, and the first child's word read from
+// the node again.
+__device__ __forceinline__ void expand_sorted(const rtl::GNode *__restrict__ node, float (&t)[8], uint32_t &list,
+                                              uint32_t &cnt, float &tfirst, uint32_t &cwfirst) {
+  uint32_t id[8];
+#pragma unroll
+  for (int c = 0; c < 8; ++c) id[c] = (uint32_t)c;
+  sort8(t, id);
+  uint32_t first_id = 0;
+  list = 0;
+  cnt = 0;
+  tfirst = 0.0f;
+#pragma unroll
+  for (int i = 7; i >= 0; --i) {  // build from the back so the first visit ends in the low bits
+    if (!(t[i] < 0.0f)) {
+      list = (list << 3) | id[i];
+      cnt += 1;
+      tfirst = t[i];
+      first_id = id[i];
+    }
+  }
+  // the first child's word, read again now that the order is known (the
+  // node's line is in the L1): the 8 words need not stay in registers
+  // across the network
+  cwfirst = node->child[first_id];
+}
+
 // The rest of an expansion, on the node's boxes and child words in registers.
 template <bool FAST>
 __device__ __forceinline__ void expand_loaded(const rtl::GNode *__restrict__ node, const float (&bx)[48],
@@ -229,13 +257,10 @@ __device__ __forceinline__ void expand_loaded(const rtl::GNode *__restrict__ nod
                                               uint32_t &list, uint32_t &cnt, float &tfirst,
                                               uint32_t &cwfirst) {
   float t[8];
-  uint32_t id[8];
 #pragma unroll
-  for (int c = 0; c < 8; ++c) {
+  for (int c = 0; c < 8; ++c)
     t[c] = slab<FAST>(bx[6 * c], bx[6 * c + 2], bx[6 * c + 4], bx[6 * c + 1], bx[6 * c + 3],
                       bx[6 * c + 5], o, inv, tNear, tFar);  // box: xMin xMax yMin yMax zMin zMax
-    id[c] = (uint32_t)c;
-  }
   bool sorted = false;
   if constexpr (FAST) {
     // At most two children entered with distinct t: the network's output order
@@ -264,26 +289,45 @@ __device__ __forceinline__ void expand_loaded(const rtl::GNode *__restrict__ nod
       cwfirst = select_word(cw0, cw1, sw ? ib : ia);
     }
   }
-  if (!sorted) {
-    sort8(t, id);
-    uint32_t first_id = 0;
-    list = 0;
-    cnt = 0;
-    tfirst = 0.0f;
+  if (!sorted) expand_sorted(node, t, list, cnt, tfirst, cwfirst);
+}
+// expand_loaded<true> with the visit order from packed keys (key_order,
+// rt_math.h), for every expansion: the network runs on 8 keys with no id array
+// (38 unsigned min / max in place of 19 compares and 76 selects), the <= 2
+// children shortcut and its test go, and the slab tests need one comparison per
+// box (slab_key). A wave in which any lane has a tie (two entered children
+// equal in the top 29 bits of t: 3 % of the bunny's wave-level expansions at
+// 1080p, tools/trav_sim.cpp --order), or whose tNear is not positive, takes
+// expand_sorted, sort8 itself, on entry distances computed again from the
+// node (a rare path: t[8] need not stay live across the key network for it).
+// The first child's word is read from the node again, as expand_sorted does:
+// selected from the 8 words kept in registers across the network it measured
+// slower.
+__device__ __forceinline__ void expand_keyed(const rtl::GNode *__restrict__ node, const float (&bx)[48], f3 o, f3 inv,
+                                             float tNear, float tFar, uint32_t &list, uint32_t &cnt, float &tfirst,
+                                             uint32_t &cwfirst) {
+  uint32_t tb[8];
 #pragma unroll
-    for (int i = 7; i >= 0; --i) {  // build from the back so the first visit ends in the low bits
-      if (!(t[i] < 0.0f)) {
-        list = (list << 3) | id[i];
-        cnt += 1;
-        tfirst = t[i];
-        first_id = id[i];
-      }
-    }
-    // the first child's word, read again now that the order is known (the
-    // node's line is in the L1): the 8 words need not stay in registers
-    // across the network
-    cwfirst = node->child[first_id];
+  for (int c = 0; c < 8; ++c)
+    tb[c] = slab_key((uint32_t)c, bx[6 * c], bx[6 * c + 2], bx[6 * c + 4], bx[6 * c + 1], bx[6 * c + 3],
+                     bx[6 * c + 5], o, inv, tNear, tFar);
+  const KeyOrder r = key_order(tb);
+  if (tNear > 0.0f && __ballot(r.tie) == 0) {  // (tNear is wave-uniform)
+    list = r.list;
+    cnt = r.cnt;
+    tfirst = __uint_as_float(r.tfirst);
+    cwfirst = node->child[r.first_id];
+    return;
   }
+  float t[8];
+#pragma unroll
+  for (int c = 0; c < 8; ++c) {
+    float b[6];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) b[i] = node->box[c][i];
+    t[c] = slab<true>(b[0], b[2], b[4], b[1], b[3], b[5], o, inv, tNear, tFar);
+  }
+  expand_sorted(node, t, list, cnt, tfirst, cwfirst);
 }
 template <bool FAST>
 __device__ __forceinline__ void expand_node(const rtl::GNode *__restrict__ node, f3 o, f3 inv,
@@ -392,8 +436,10 @@ constexpr int kCoopRays = RT_COOP_RAYS;
 // through pad, the wave's 224 bytes of LDS (node_load_shared); any other
 // expansion loads per lane. Modelled first on the CPU (tools/trav_sim.cpp
 // --share, bunny 1080p: 39 % of a frame's wave-level expansions).
+// KEYS (with SHARE and FAST, the primary path): the expansion orders the
+// children by packed keys (expand_keyed).
 template <int BLOCK, bool ANY, bool FAST, bool TAIL, uint32_t LB = RT_LEAF_BATCH, bool MAJ = false, bool SHARE = false,
-          int F, class CT>
+          bool KEYS = false, int F, class CT>
 __device__ __forceinline__ bool mesh_run(const MeshDev &sc, f3 o, f3 d, f3 inv, float tNear, float tFar,
                                          LdsStack<BLOCK, F> st, MState &S, CT &cnt, int coop_rays = kCoopRays,
                                          int prio_iters = 0, NodePad *pad = nullptr) {
@@ -475,7 +521,10 @@ __device__ __forceinline__ bool mesh_run(const MeshDev &sc, f3 o, f3 d, f3 inv, 
           uint4 cw0, cw1;
           if (shared) node_load_shared(sc.nodes + w0, act, pad, bx, cw0, cw1);
           else node_load(sc.nodes + word, bx, cw0, cw1);
-          expand_loaded<FAST>(sc.nodes + word, bx, cw0, cw1, o, inv, tNear, tFar, l, c, tf, cwf);
+          if constexpr (KEYS && FAST)
+            expand_keyed(sc.nodes + word, bx, o, inv, tNear, tFar, l, c, tf, cwf);
+          else
+            expand_loaded<FAST>(sc.nodes + word, bx, cw0, cw1, o, inv, tNear, tFar, l, c, tf, cwf);
         } else {
           expand_node<FAST>(sc.nodes + word, o, inv, tNear, tFar, l, c, tf, cwf);
         }
@@ -737,7 +786,11 @@ __device__ __forceinline__ void mesh_run_coop(const MeshDev &sc, f3 o, f3 d, f3 
 // bytes per wave of the block, so every kernel on this path gets it with the
 // call. cnt: the counting kernel's counters (with sc.coop off: the groups do
 // not count); the timed kernels pass none.
-template <int BLOCK, int F, class CT>
+// KEYS: the fast rays' expansions order the children by packed keys
+// (expand_keyed). The render kernels turn it on; the ray, instance and TLAS
+// queries keep sort8: with it their 4- and 7-slot kernels spill or lose a wave
+// per SIMD (profiles/r21/README.md), and their tNear is the caller's.
+template <int BLOCK, int F, bool KEYS = false, class CT>
 __device__ __forceinline__ bool mesh_primary_wave(const MeshDev &sc, f3 o, f3 d, float tNear, float tFar,
                                                   bool active, uint32_t *stk_block, float &out_t,
                                                   uint32_t &out_k, int coop_rays, int prio_iters, CT &cnt) {
@@ -771,12 +824,12 @@ __device__ __forceinline__ bool mesh_primary_wave(const MeshDev &sc, f3 o, f3 d,
   }
   bool suspended = false;
   if (pending && sc.coop)
-    suspended = fast ? mesh_run<BLOCK, false, true, true, RT_LEAF_BATCH_PRIMARY, true, kShare>(
+    suspended = fast ? mesh_run<BLOCK, false, true, true, RT_LEAF_BATCH_PRIMARY, true, kShare, KEYS>(
                            sc, o, d, inv, tNear, tFar, st, S, cnt, coop_rays, prio_iters, pad)
                      : mesh_run<BLOCK, false, false, true, RT_LEAF_BATCH_PRIMARY, true, kShare>(
                            sc, o, d, inv, tNear, tFar, st, S, cnt, coop_rays, prio_iters, pad);
   else if (pending)
-    (void)(fast ? mesh_run<BLOCK, false, true, false, RT_LEAF_BATCH_PRIMARY, true, kShare>(
+    (void)(fast ? mesh_run<BLOCK, false, true, false, RT_LEAF_BATCH_PRIMARY, true, kShare, KEYS>(
                       sc, o, d, inv, tNear, tFar, st, S, cnt, kCoopRays, 0, pad)
                 : mesh_run<BLOCK, false, false, false, RT_LEAF_BATCH_PRIMARY, true, kShare>(
                       sc, o, d, inv, tNear, tFar, st, S, cnt, kCoopRays, 0, pad));
@@ -838,13 +891,13 @@ __device__ __forceinline__ bool mesh_primary_wave(const MeshDev &sc, f3 o, f3 d,
   return S.gk != rtl::kInvalidChild;
 }
 
-template <int BLOCK, int F>
+template <int BLOCK, int F, bool KEYS = false>
 __device__ __forceinline__ bool mesh_primary_wave(const MeshDev &sc, f3 o, f3 d, float tNear, float tFar,
                                                   bool active, uint32_t *stk_block, float &out_t,
                                                   uint32_t &out_k, int coop_rays = kCoopRays,
                                                   int prio_iters = 0) {
   NoCnt cnt;
-  return mesh_primary_wave<BLOCK, F>(sc, o, d, tNear, tFar, active, stk_block, out_t, out_k, coop_rays, prio_iters,
+  return mesh_primary_wave<BLOCK, F, KEYS>(sc, o, d, tNear, tFar, active, stk_block, out_t, out_k, coop_rays, prio_iters,
                                      cnt);
 }
 

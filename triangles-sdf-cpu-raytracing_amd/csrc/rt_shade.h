@@ -71,7 +71,7 @@ struct MeshS {
     float t;
     uint32_t k;
     Hit h = miss_hit();
-    if (mesh_primary_wave<B, kFields>(d, o, dir, tn, tf, active, stk, t, k, coop_rays, prio_iters) && active) {
+    if (mesh_primary_wave<B, kFields, true>(d, o, dir, tn, tf, active, stk, t, k, coop_rays, prio_iters) && active) {
       h.hit = true;
       h.t = t;
       h.n = tri_normal(d.tris, k);
@@ -91,7 +91,7 @@ struct MeshS {
     Hit h = miss_hit();
     MeshDev dc = d;
     dc.coop = false;
-    if (mesh_primary_wave<B, kFields>(dc, o, dir, tn, tf, active, stk, t, k, kCoopRays, 0, cnt) && active) {
+    if (mesh_primary_wave<B, kFields, true>(dc, o, dir, tn, tf, active, stk, t, k, kCoopRays, 0, cnt) && active) {
       h.hit = true;
       h.t = t;
       h.n = tri_normal(d.tris, k);
