@@ -325,6 +325,51 @@ int rt_scene_create_instanced(rt_scene *const *blas, int32_t nblas, const rt_ins
 #define RT_INSTANCED_TLAS 1u
 int rt_scene_create_instanced_ex(rt_scene *const *blas, int32_t nblas, const rt_instance *inst, int32_t ninst,
                                  uint32_t flags, rt_scene **out);
+/* ---- mixed bottom-level kinds: meshes, SDF grids and SDF octrees -----------
+ * rt_scene_create_instanced_any is rt_scene_create_instanced_ex (flags 0 or
+ * RT_INSTANCED_TLAS, every argument rule the same) whose BLAS may also be
+ * RT_SCENE_GRID and RT_SCENE_OCTREE scenes; an instanced scene as a BLAS is
+ * still RT_E_STATE. When every BLAS is a mesh the call IS
+ * rt_scene_create_instanced_ex: the same scene, kernels and
+ * rt_scene_device_bytes. Otherwise the scene (still RT_SCENE_INSTANCED) is
+ * "mixed": the device holds one 112-byte table record per BLAS instead of the
+ * 56-byte mesh record, which rt_scene_device_bytes counts, and its queries run
+ * kernels of their own. The definition is the loop above (THE ORDER IS THE
+ * DEFINITION), read literally:
+ *   - h = IScene::intersect of BLAS[blas_i] alone on (o', d', tNear, tf_i) is
+ *     that BLAS kind's own entry: the answer rt_trace_rays_device gives for the
+ *     BLAS scene on that ray, bit for bit;
+ *   - prim = ((int64)i << 32) | p with p what the plain kind reports: the
+ *     original triangle id, the grid cell, or the octree node;
+ *   - the world normal is the same inverse-transpose formula on the
+ *     object-space normal the BLAS reports for the winner;
+ *   - for RT_INSTANCED_TLAS the box_pass line is unchanged; the object box of
+ *     an SDF BLAS is (-1,-1,-1, 1,1,1), the cube both SDF kinds live in;
+ *   - the flat list skips an SDF instance only by a test its own intersection
+ *     makes (a mesh instance by the traversal's root-box test, as above);
+ *   - RT_RAYS_ANY_HIT is the OR over the instances (with box_pass under the
+ *     full tFar for RT_INSTANCED_TLAS) of the BLAS any hit under the full tFar.
+ *     It equals the closest-hit flag for SDF kinds as well, and the reason needs
+ *     no monotonicity of a BLAS in tFar: until a ray's first accepted hit best
+ *     is +inf, so tf_i IS tFar and both loops ask every instance the same
+ *     question; the first instance that answers yes sets both flags. (The
+ *     composed oracle of tests/test_mixed_host.py finds 0 differing rays.)
+ * d' is not renormalised. A sphere march steps by the sampled distance in
+ * units of |d'|, so under a map with scale an SDF BLAS is marched with steps
+ * that are too long or too short by that factor: the definition, and the bits,
+ * are still the composition above, but the picture is geometrically
+ * meaningful for rigid maps only (|d'| = 1 up to rounding). Meshes have no
+ * such limit.
+ * Every entry listed above for instanced scenes works on a mixed one with its
+ * rules: rt_trace_rays_device, rt_intersect_rays, rt_shade_rays_device,
+ * rt_scene_update_instances (which may move an instance to a BLAS of another
+ * kind), rt_scene_update_instances_device, rt_scene_get_instances,
+ * rt_scene_get_tlas, the plane, kind, device and byte getters and
+ * rt_scene_destroy; a dynamic mesh BLAS refitted by rt_scene_update_vertices*
+ * is seen by the next query. SDF scenes cannot change after creation. The
+ * frame entries keep returning RT_E_STATE. */
+int rt_scene_create_instanced_any(rt_scene *const *blas, int32_t nblas, const rt_instance *inst, int32_t ninst,
+                                  uint32_t flags, rt_scene **out);
 /* Host-only: the definition of an instance's world box (above). */
 int rt_instance_world_box(const float xform[12], const float obox[6], float wbox[6]);
 /* The tree as the device holds it, after one device synchronisation:

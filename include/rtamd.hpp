@@ -314,6 +314,20 @@ class InstancedScene : public IScene {
     reset(s);
     count_ = (int32_t)instances.size();
   }
+  // The same over bottom-level scenes of any plain kind (BVHBuilder, SDFGrid,
+  // SDFOctree; rt_scene_create_instanced_any): prim's low word is then the
+  // triangle id, the grid cell or the octree node. A mesh-only list gives the
+  // scene perform() above gives. SDF instances want rigid poses.
+  void performAny(const std::vector<const IScene *> &blas, const std::vector<rt_instance> &instances,
+                  uint32_t flags = 0) {
+    std::vector<rt_scene *> h;
+    for (const IScene *b : blas) h.push_back(b ? b->handle() : nullptr);
+    rt_scene *s = nullptr;
+    check(rt_scene_create_instanced_any(h.data(), (int32_t)h.size(), instances.data(), (int32_t)instances.size(),
+                                        flags, &s));
+    reset(s);
+    count_ = (int32_t)instances.size();
+  }
   int32_t size() const { return count_; }
   // New blas / flags / poses for instances first .. first + n - 1 (host
   // buffer, validated; a refused call changes nothing).

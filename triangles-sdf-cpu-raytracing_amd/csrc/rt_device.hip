@@ -2157,6 +2157,7 @@ int launch_trace(rt_scene *s, const rt_ray_batch &b, int mode, hipStream_t strea
     // entry (and a top-level tree) catch up in stream order ahead of the trace
     if (int rc = rti::instanced_sync(s, stream)) return rc;
     const rti::InstArgs a{s->d_inst, s->d_blas, s->ninst, s->maxd, s->d_tlas, s->tlas_leaves};
+    if (s->d_mixed) return rti::trace_mixed_launch(rti::MixedArgs{a, s->d_mixed}, s->plane, b, mode, stream);
     return s->d_tlas ? rti::trace_tlas_launch(a, s->plane, b, mode, stream)
                      : rti::trace_instances_launch(a, s->plane, b, mode, stream);
   }

@@ -104,4 +104,38 @@ int tlas_boxes_launch(const TlasArgs &t, int32_t first, int32_t count, const flo
 // every inner node from the leaves, bottom-up. Only launches.
 int tlas_refit_launch(const TlasArgs &t, hipStream_t st);
 
+// ---- rt_instances_mixed.hip: scenes of rt_scene_create_instanced_any whose ----
+// bottom-level scenes are not all meshes. One table record per BLAS, 112
+// bytes: the kind (RT_SCENE_MESH / _GRID / _OCTREE), the kind's variant (a
+// grid's launch mode, kGridBuf | kGridBricked as rti::grid_mode gives it; an
+// octree's PACK bit, rt_dispatch.h's rule on the BLAS's own depth) and the
+// three device views, of which the kind's own is filled. The flat list reads a
+// record through a wave-uniform address (scalar loads, the view stays in
+// SGPRs); the tree's mesh phase reads it per lane. InstRec is unchanged.
+struct BlasRec {
+  uint32_t kind;
+  uint32_t var;
+  rtd::MeshDev mesh;
+  rtd::GridDev grid;
+  rtd::OctDev oct;
+};
+static_assert(sizeof(BlasRec) == 112, "mixed table record: 112 bytes");
+
+// InstArgs of a mixed scene: its table instead of InstArgs::blas (left NULL)
+struct MixedArgs {
+  InstArgs a;
+  const BlasRec *tab;
+};
+// as trace_instances_launch / trace_tlas_launch (a.a.tlas picks the tree)
+int trace_mixed_launch(const MixedArgs &a, const rtd::PlaneDev &pl, const rt_ray_batch &b, int mode, hipStream_t st);
+// as shade_instances_launch
+int shade_mixed_launch(const MixedArgs &a, const rtd::PlaneDev &pl, const rt_render_params &p, const rt_ray_batch &b,
+                       uint32_t *d_color, uint32_t flags, hipStream_t st);
+// as blas_entry_launch: the mesh view of a record of kind RT_SCENE_MESH
+int mixed_entry_launch(BlasRec *entry, const rtd::MeshDev &md, hipStream_t st);
+// as tlas_boxes_launch with the object boxes of the mixed table (t.blas is not
+// read): a mesh's rbox, the cube (-1,-1,-1, 1,1,1) for both SDF kinds
+int mixed_boxes_launch(const TlasArgs &t, const BlasRec *tab, int32_t first, int32_t count, const float *d_xsrc,
+                       int32_t only_blas, hipStream_t st);
+
 }  // namespace rti

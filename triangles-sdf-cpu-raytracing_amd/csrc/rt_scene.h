@@ -65,6 +65,10 @@ struct rt_scene {
   int32_t ninst = 0;
   std::vector<rt_scene *> blas;
   std::vector<uint64_t> blas_seen;
+  // a mixed scene (rt_scene_create_instanced_any with a grid or an octree among
+  // its bottom-level scenes): the table of tagged records instead of d_blas,
+  // which stays NULL (rt_instances_mixed.hip)
+  rti::BlasRec *d_mixed = nullptr;
   // created with RT_INSTANCED_TLAS: the top-level tree (2 * tlas_leaves nodes,
   // rt_tlas.h) and the object-to-world matrices (12 floats per instance) its
   // leaves are recomputed from when a BLAS's root box moves. Both live on the

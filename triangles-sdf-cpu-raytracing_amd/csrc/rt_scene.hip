@@ -101,14 +101,19 @@ int no_instanced(const rt_scene *s, const char *who) {
 
 int instanced_sync(rt_scene *s, hipStream_t stream) {
   for (size_t j = 0; j < s->blas.size(); ++j) {
+    // (only a dynamic mesh's version ever moves: SDF scenes are immutable)
     if (s->blas[j]->version == s->blas_seen[j]) continue;
-    if (int rc = rti::blas_entry_launch(s->d_blas + j, mesh_dev(s->blas[j]), stream)) return rc;
+    if (int rc = s->d_mixed ? rti::mixed_entry_launch(s->d_mixed + j, mesh_dev(s->blas[j]), stream)
+                            : rti::blas_entry_launch(s->d_blas + j, mesh_dev(s->blas[j]), stream))
+      return rc;
     s->blas_seen[j] = s->blas[j]->version;
     if (!s->d_tlas) continue;
     // its root box moved: that BLAS's leaves of the top-level tree and the
     // tree above them, behind the entry
     const rti::TlasArgs t = rti::tlas_args(s);
-    if (int rc = rti::tlas_boxes_launch(t, 0, s->ninst, nullptr, (int32_t)j, stream)) return rc;
+    if (int rc = s->d_mixed ? rti::mixed_boxes_launch(t, s->d_mixed, 0, s->ninst, nullptr, (int32_t)j, stream)
+                            : rti::tlas_boxes_launch(t, 0, s->ninst, nullptr, (int32_t)j, stream))
+      return rc;
     if (int rc = rti::tlas_refit_launch(t, stream)) return rc;
   }
   return RT_OK;
@@ -548,12 +553,32 @@ int instance_range(const rt_scene *s, int32_t first, int32_t count, const char *
 static int tlas_update(const rt_scene *s, int32_t first, int32_t count, const float *d_xsrc, int32_t only_blas,
                        hipStream_t st) {
   const rti::TlasArgs t = rti::tlas_args(s);
-  if (int rc = rti::tlas_boxes_launch(t, first, count, d_xsrc, only_blas, st)) return rc;
+  if (int rc = s->d_mixed ? rti::mixed_boxes_launch(t, s->d_mixed, first, count, d_xsrc, only_blas, st)
+                          : rti::tlas_boxes_launch(t, first, count, d_xsrc, only_blas, st))
+    return rc;
   return rti::tlas_refit_launch(t, st);
 }
 
+// the record of the mixed table for one bottom-level scene (rt_instances.h)
+static rti::BlasRec blas_rec(const rt_scene *bl) {
+  rti::BlasRec e{};
+  e.kind = (uint32_t)bl->kind;
+  if (bl->kind == RT_SCENE_MESH) {
+    e.mesh = mesh_dev(bl);
+  } else if (bl->kind == RT_SCENE_GRID) {
+    e.grid = grid_dev(bl);
+    e.var = (uint32_t)grid_mode(bl, e.grid);
+  } else {
+    e.oct = OctDev{bl->d_child, bl->d_ovals};
+    e.var = bl->maxd <= 7 ? 1u : 0u;  // rt_dispatch.h: packed node coordinates for trees of up to 7 slots
+  }
+  return e;
+}
+
+// any: rt_scene_create_instanced_any, which also takes grids and octrees; with
+// one of them among the BLAS the scene gets the mixed table instead of d_blas
 static int create_instanced(const char *who, rt_scene *const *blas, int32_t nblas, const rt_instance *inst,
-                            int32_t ninst, uint32_t flags, rt_scene **out) {
+                            int32_t ninst, uint32_t flags, rt_scene **out, bool any = false) {
   if (!blas || !inst || !out) return set_err(RT_E_INVALID, std::string(who) + ": NULL argument");
   *out = nullptr;
   if (flags & ~RT_INSTANCED_TLAS) return set_err(RT_E_INVALID, std::string(who) + ": unknown flag bits");
@@ -561,20 +586,32 @@ static int create_instanced(const char *who, rt_scene *const *blas, int32_t nbla
   int dev = 0;
   HIP_TRY(hipGetDevice(&dev));
   int32_t maxd = 1;
+  bool mixed = false;
   for (int32_t j = 0; j < nblas; ++j) {
     if (!blas[j]) return set_err(RT_E_INVALID, std::string(who) + ": BLAS " + std::to_string(j) + " is NULL");
-    if (blas[j]->kind != RT_SCENE_MESH)
-      return set_err(RT_E_STATE, std::string(who) + ": BLAS " + std::to_string(j) + " is not a mesh scene");
+    const int kind = blas[j]->kind;
+    if (any && (kind == RT_SCENE_GRID || kind == RT_SCENE_OCTREE))
+      mixed = true;
+    else if (kind != RT_SCENE_MESH)
+      return set_err(RT_E_STATE, std::string(who) + ": BLAS " + std::to_string(j) +
+                                     (any ? " is not a mesh, grid or octree scene" : " is not a mesh scene"));
     if (blas[j]->device != dev)
       return set_err(RT_E_INVALID, std::string(who) + ": BLAS " + std::to_string(j) + " lives on device " +
                                        std::to_string(blas[j]->device) + ", the current device is " + std::to_string(dev));
-    maxd = std::max(maxd, blas[j]->maxd);
+    maxd = std::max(maxd, blas[j]->maxd);  // (a grid keeps the default 1: it has no stack)
   }
+  if (mixed) maxd = std::max(maxd, 4);  // the smallest slot option (rt_dispatch.h) when only grids are there
   std::vector<rti::InstRec> recs((size_t)ninst);
   for (int32_t i = 0; i < ninst; ++i)
     if (int rc = instance_record(inst[i], nblas, i, who, recs[(size_t)i])) return rc;
   std::vector<MeshDev> tab;
-  for (int32_t j = 0; j < nblas; ++j) tab.push_back(mesh_dev(blas[j]));
+  std::vector<rti::BlasRec> mtab;
+  for (int32_t j = 0; j < nblas; ++j) {
+    if (mixed)
+      mtab.push_back(blas_rec(blas[j]));
+    else
+      tab.push_back(mesh_dev(blas[j]));
+  }
   rt_scene *s = nullptr;
   if (int rc = new_scene(&s)) return rc;
   s->kind = RT_SCENE_INSTANCED;
@@ -583,7 +620,8 @@ static int create_instanced(const char *who, rt_scene *const *blas, int32_t nbla
   s->blas.assign(blas, blas + nblas);
   for (int32_t j = 0; j < nblas; ++j) s->blas_seen.push_back(blas[j]->version);
   int rc = upload(&s->d_inst, recs.data(), recs.size(), s->dev_bytes);
-  if (!rc) rc = upload(&s->d_blas, tab.data(), tab.size(), s->dev_bytes);
+  if (!rc) rc = mixed ? upload(&s->d_mixed, mtab.data(), mtab.size(), s->dev_bytes)
+                      : upload(&s->d_blas, tab.data(), tab.size(), s->dev_bytes);
   if (!rc && (flags & RT_INSTANCED_TLAS)) {
     // the matrices as given, the node array zeroed (node 0 and the pad words
     // stay zero), every leaf (the empty ones past ninst too) and the inner
@@ -616,6 +654,11 @@ int rt_scene_create_instanced(rt_scene *const *blas, int32_t nblas, const rt_ins
 int rt_scene_create_instanced_ex(rt_scene *const *blas, int32_t nblas, const rt_instance *inst, int32_t ninst,
                                  uint32_t flags, rt_scene **out) {
   return create_instanced("rt_scene_create_instanced_ex", blas, nblas, inst, ninst, flags, out);
+}
+
+int rt_scene_create_instanced_any(rt_scene *const *blas, int32_t nblas, const rt_instance *inst, int32_t ninst,
+                                  uint32_t flags, rt_scene **out) {
+  return create_instanced("rt_scene_create_instanced_any", blas, nblas, inst, ninst, flags, out, true);
 }
 
 int rt_scene_update_instances(rt_scene *s, int32_t first, int32_t count, const rt_instance *inst) {
@@ -815,7 +858,7 @@ int rt_scene_destroy(rt_scene *s) {
     if (x) HIP_NOTE(hipStreamSynchronize(x));
   if (s->sched_os) HIP_NOTE(hipStreamSynchronize(s->sched_os));
   void *ptrs[] = {s->d_nodes, s->d_tris, s->d_vals, s->d_child, s->d_ovals, s->d_color, s->d_t,
-                  s->d_cost[0], s->d_order[0], s->d_cost[1], s->d_order[1], s->d_idx, s->d_vstage, s->d_edge, s->d_inst, s->d_blas, s->d_tlas, s->d_xform};
+                  s->d_cost[0], s->d_order[0], s->d_cost[1], s->d_order[1], s->d_idx, s->d_vstage, s->d_edge, s->d_inst, s->d_blas, s->d_mixed, s->d_tlas, s->d_xform};
   for (void *p : ptrs)
     if (p) HIP_NOTE(hipFree(p));
   if (s->h_refit) HIP_NOTE(hipHostFree(s->h_refit));

@@ -90,6 +90,7 @@ int rt_shade_rays_device(rt_scene *s, const rt_ray_batch *b, const rt_render_par
   if (s->kind == RT_SCENE_INSTANCED) {
     if (int rc = rti::instanced_sync(s, st)) return rc;
     const rti::InstArgs a{s->d_inst, s->d_blas, s->ninst, s->maxd, s->d_tlas, s->tlas_leaves};
+    if (s->d_mixed) return rti::shade_mixed_launch(rti::MixedArgs{a, s->d_mixed}, s->plane, *p, *b, d_color, flags, st);
     return rti::shade_instances_launch(a, s->plane, *p, *b, d_color, flags, st);
   }
   const unsigned blocks = (unsigned)((b->n + kSBlock - 1) / kSBlock);

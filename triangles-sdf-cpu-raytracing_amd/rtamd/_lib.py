@@ -105,6 +105,8 @@ _SIGS = {
                                             C.POINTER(C.c_void_p)]),
     "rt_scene_create_instanced_ex": (C.c_int, [C.POINTER(C.c_void_p), C.c_int32, C.POINTER(Instance), C.c_int32,
                                                C.c_uint32, C.POINTER(C.c_void_p)]),
+    "rt_scene_create_instanced_any": (C.c_int, [C.POINTER(C.c_void_p), C.c_int32, C.POINTER(Instance), C.c_int32,
+                                                C.c_uint32, C.POINTER(C.c_void_p)]),
     "rt_instance_world_box": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "rt_scene_get_tlas": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]),
     "rt_scene_update_instances": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(Instance)]),

@@ -536,7 +536,11 @@ class InstancedScene(IScene):
     (instance << 32) | triangle id. Keeps its BLAS objects alive.
     tlas=True (RT_INSTANCED_TLAS): a top-level tree over the instances' world
     boxes, for hundreds of instances; its quality is the spatial coherence of
-    the index order (morton_order)."""
+    the index order (morton_order).
+    blas_list may also hold SDFGrid and SDFOctree scenes
+    (rt_scene_create_instanced_any): prim's low word is then the grid cell or
+    the octree node of the winner, and `mixed` is True. An SDF instance wants
+    a rigid pose: the march steps in units of the transformed direction."""
 
     DISABLED = RT_INSTANCE_DISABLED
 
@@ -549,26 +553,31 @@ class InstancedScene(IScene):
         xforms = np.asarray([np.asarray(t[1], np.float32).reshape(12) for t in inst], np.float32).reshape(-1, 12)
         arr = _instance_array(self._blas_idx, xforms, self._flags)
         h = C.c_void_p()
-        check(lib().rt_scene_create_instanced_ex(handles, len(self._blas_objs), arr, len(inst),
-                                                 RT_INSTANCED_TLAS if tlas else 0, C.byref(h)))
+        # mesh-only lists keep their entry; the general one only when it is needed
+        self.mixed = any(not isinstance(b, BVHBuilder) for b in self._blas_objs)
+        create = lib().rt_scene_create_instanced_any if self.mixed else lib().rt_scene_create_instanced_ex
+        check(create(handles, len(self._blas_objs), arr, len(inst), RT_INSTANCED_TLAS if tlas else 0, C.byref(h)))
         self._h = h
         self.has_tlas = bool(tlas)
 
     def __len__(self):
         return len(self._blas_idx)
 
-    def update_instances(self, xforms, first: int = 0, flags=None):
-        """New poses (and, with flags, new flags) for instances first ..
-        first + K - 1 from host matrices [K, 3, 4] or [K, 12]; the blas indices
-        stay (rt_scene_update_instances). A refused call changes nothing."""
+    def update_instances(self, xforms, first: int = 0, flags=None, blas=None):
+        """New poses (and, with flags, new flags; with blas, new BLAS indices)
+        for instances first .. first + K - 1 from host matrices [K, 3, 4] or
+        [K, 12]; without blas the indices stay (rt_scene_update_instances). A
+        refused call changes nothing."""
         x = np.ascontiguousarray(xforms, np.float32)
         k = x.shape[0] if x.ndim >= 2 else 0
         if first < 0 or first + k > len(self):
             raise RtError(f"update_instances: [{first}, {first + k}) outside the scene's {len(self)} instances")
         fl = self._flags[first:first + k] if flags is None else np.broadcast_to(np.asarray(flags, np.uint32), (k,))
-        arr = _instance_array(self._blas_idx[first:first + k], x, fl)
+        bi = self._blas_idx[first:first + k] if blas is None else np.broadcast_to(np.asarray(blas, np.int32), (k,))
+        arr = _instance_array(bi, x, fl)
         check(lib().rt_scene_update_instances(self._handle(), int(first), k, arr))
         self._flags[first:first + k] = fl
+        self._blas_idx[first:first + k] = bi
 
     def update_instances_device(self, ptr: int, count: int, first: int = 0, stream: int | None = None):
         """The same from device memory: `count` matrices (float32[12 * count] at

@@ -171,7 +171,9 @@ def update_instances(scene, xforms, first: int = 0) -> None:
 def split_prim(prim):
     """(instance, triangle) of an InstancedScene's primitive ids (an int64
     tensor or numpy array): prim = (instance << 32) | triangle on a hit.
-    Misses (-1) and the plane (-2) give instance -1 and triangle -1 / -2."""
+    Misses (-1) and the plane (-2) give instance -1 and triangle -1 / -2.
+    The low word is what the instance's BLAS kind reports: original triangle
+    id (mesh), c0 cell (SDFGrid) or leaf node (SDFOctree)."""
     neg = prim < 0
     inst = prim >> 32  # arithmetic shift: -1 for the negative ids
     tri = prim & 0xFFFFFFFF
