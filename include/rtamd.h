@@ -716,6 +716,86 @@ int rt_sdf_mesh_device(const rt_sdf_mesh *m);
  * result is cached in the handle). */
 int rt_sdf_mesh_octree(rt_sdf_mesh *m, int32_t depth, int64_t *count, void *nodes36);
 int rt_sdf_mesh_destroy(rt_sdf_mesh *m);
+
+/* ---- deforming meshes under point queries -----------------
+ * rt_sdf_mesh_create_ex with flags = 0 is exactly rt_sdf_mesh_create. With
+ * RT_MESH_DYNAMIC the vertices may be moved afterwards: an update keeps the
+ * topology of creation and recomputes on the device everything that depends on
+ * a position.
+ *
+ * What stays: the tree (child words), the leaf order, the original triangle
+ * ids, and the weld map of creation -- vertices whose divided positions
+ * (v / v.w) had equal bits at creation share one pseudonormal for the life of
+ * the handle, wherever they move; an edge is the pair of its welded end
+ * points. nverts must equal the creation value.
+ *
+ * What is recomputed, from the new positions:
+ *   (a) every triangle record: the corners v / v.w (correctly rounded
+ *       division) in the order idx[3 id + 0..2];
+ *   (b) every child box: the exact min/max of its subtree's divided corners
+ *       (the order and the std::min / std::max tie rules of the scene refit,
+ *       rt_scene_update_vertices);
+ *   (c) the 7 pseudonormals of every original triangle, as creation computes
+ *       them: the face normal nf in float (cross product, sqrt, divide; zero
+ *       when the length is 0); each corner angle in double (0 when an adjacent
+ *       edge has zero length, the cosine clamped to [-1, 1]); each welded
+ *       vertex the double sum of ang * nf over its incident (triangle, corner)
+ *       pairs in ascending triangle id, then corner; each welded edge the
+ *       double sum of nf over its incident triangles in ascending triangle id,
+ *       then ab, ac, bc; each sum rounded to float once.
+ *
+ * Against a fresh handle of the moved mesh (rt_sdf_mesh_create of the new
+ * positions, when they have the weld classes of creation): distance magnitude,
+ * closest point, triangle and feature of every query are bit for bit the
+ * fresh handle's, and the brute-force loop's above (the winner is the least
+ * (d2, id), which any valid tree finds; the exactness domain is the one named
+ * there, points and meshes in about [-1,1]^3). The sign is the fresh handle's
+ * wherever the winning feature's pseudonormal has the same bits. Face and edge
+ * normals always have: they are IEEE operations in a fixed order. Vertex
+ * normals go through acos in double, and the device's acos may differ from the
+ * host library's in the last bits of the double; that can, rarely, move the
+ * final float rounding of a component by one ulp.
+ *
+ * Vertex values are not validated: topology is only read, so no value can make
+ * a walk index out of bounds, and NaN positions give NaN distances, as the
+ * arithmetic says.
+ *
+ * rt_sdf_mesh_update_vertices_device only launches on `stream` (hipStream_t or
+ * NULL): no allocation, no copy, no host wait; the handle's device must be the
+ * current one; d_vpos4 is read by the queued kernels. Queries queued on the
+ * same stream afterwards see the moved mesh; the caller orders updates against
+ * queries still running on other streams. Each update records an event on
+ * `stream` after its last kernel, and the handle's own host entries
+ * (rt_sdf_mesh_points, _grid, _octree) make their stream wait for it before
+ * they read. rt_sdf_mesh_update_vertices copies a host buffer through a
+ * staging buffer the handle keeps and returns when the update is complete.
+ * Both invalidate the octree cache of rt_sdf_mesh_octree.
+ *
+ * RT_E_INVALID: a NULL handle or pointer, nverts unlike creation, an unknown
+ * flag bit. RT_E_STATE: an update of a handle created without RT_MESH_DYNAMIC.
+ * A refused call launches nothing and leaves the handle as it was.
+ *
+ * A handle without the flag holds three device arrays: the inner nodes (224
+ * bytes each), the triangle records (48 bytes per triangle) and the
+ * pseudonormals (112 bytes per triangle). With T triangles, V vertices, WV
+ * welded vertices and WE welded edges a dynamic handle adds: the index array
+ * (12 T), the vertex staging buffer (16 V), the weld id per vertex (4 V), the
+ * welded edge ids (12 T), the incidence lists of the welded vertices
+ * (4 (WV + 1) + 12 T) and edges (4 (WE + 1) + 12 T), the face normals (16 T)
+ * and corner angles (24 T) as scratch, and the welded vertex (16 WV) and edge
+ * (16 WE) normals. rt_sdf_mesh_device_bytes returns the sum for the handle
+ * (its query staging, which grows with use, is not counted). RT_MESH_DYNAMIC
+ * is the flag of rt_scene_create_mesh_ex. */
+int rt_sdf_mesh_create_ex(const float *vpos4, int64_t nverts, const uint32_t *idx, int64_t nidx,
+                          uint32_t flags, rt_sdf_mesh **out);
+int rt_sdf_mesh_update_vertices(rt_sdf_mesh *m, const float *vpos4, int64_t nverts);              /* host buffer */
+int rt_sdf_mesh_update_vertices_device(rt_sdf_mesh *m, const float *d_vpos4, int64_t nverts, void *stream);
+/* After one device synchronisation: pn28[28 t + 4 f + 0..2] = the pseudonormal
+ * of feature f (0..6) of ORIGINAL triangle t, as the device holds it (the 4th
+ * float of each is whatever is stored). Any handle, dynamic or not; ntri must
+ * be the handle's triangle count (else RT_E_INVALID). */
+int rt_sdf_mesh_get_pseudonormals(const rt_sdf_mesh *m, float *pn28, int64_t ntri);
+int64_t rt_sdf_mesh_device_bytes(const rt_sdf_mesh *m);   /* RT_E_INVALID for a NULL handle */
 /* Host-only: midpoint subdivision `levels` times (each triangle -> 4, edge
  * midpoints shared, (a+b)*0.5 on the 4 components): the config-5 stand-in
  * for MotorcycleCylinderHead.obj. Two-call protocol on the counts. */

@@ -160,6 +160,33 @@ int rtx_bvh_refit_host(const float *vpos4, int64_t nverts, const uint32_t *idx, 
   return RT_OK;
 }
 
+// The host restatement of the SDF-mesh refit, no GPU: rth::prep_sdf_mesh of
+// the mesh -- n_inner GNode records of 224 bytes, n_tri triangle records of 48
+// bytes (a.xyz, id | b.xyz, 0 | c.xyz, 0) and 28 floats of pseudonormals per
+// ORIGINAL triangle (pn28: nidx / 3 * 28 floats) -- moved to new_vpos4
+// (rth::refit_sdf_mesh), or as built when new_vpos4 is NULL. Two-call protocol
+// on the counts, as rtx_bvh_refit_host. Not part of include/rtamd.h.
+int rtx_sdf_mesh_refit_host(const float *vpos4, int64_t nverts, const uint32_t *idx, int64_t nidx,
+                            const float *new_vpos4, void *nodes224, int64_t *n_inner, void *tri48, int64_t *n_tri,
+                            float *pn28) {
+  if (!vpos4 || !idx || !n_inner || !n_tri || nverts <= 0 || nidx <= 0) return set_err(RT_E_INVALID, "bad mesh");
+  rth::SdfMeshHost m;
+  rth::SdfTopo topo;
+  std::string err;
+  if (!rth::prep_sdf_mesh(vpos4, nverts, idx, nidx, m, err, &topo)) return set_err(RT_E_INVALID, err);
+  const int64_t ni = (int64_t)m.bvh.nodes.size(), nt = (int64_t)m.bvh.tris.size();
+  if (nodes224 || tri48 || pn28) {
+    if (!nodes224 || !tri48 || !pn28 || *n_inner < ni || *n_tri < nt) return set_err(RT_E_INVALID, "buffers too small");
+    if (new_vpos4) rth::refit_sdf_mesh(m, topo, idx, nidx, new_vpos4);
+    if (ni) std::memcpy(nodes224, m.bvh.nodes.data(), (size_t)ni * sizeof(rtl::GNode));
+    std::memcpy(tri48, m.tri.data(), m.tri.size() * 4);
+    std::memcpy(pn28, m.pn.data(), m.pn.size() * 4);
+  }
+  *n_inner = ni;
+  *n_tri = nt;
+  return RT_OK;
+}
+
 // The pageable drop-in's host copy (rth::copy_spans) on caller arrays, no GPU:
 // span[2y] = first stored column of row y, span[2y+1] = -last (INT32_MAX,
 // INT32_MAX: none); threads 0 = the library's default; clear_src != 0: the

@@ -178,8 +178,34 @@ struct SdfMeshHost {
   std::vector<float> tri;   // per GPU leaf-order triangle: a.xyz,id | b.xyz,0 | c.xyz,0
   std::vector<float> pn;    // per ORIGINAL triangle: 7 x float4 angle-weighted pseudonormals
 };
+// The weld map of a mesh and what a refit of its pseudonormals walks (rt_sdf_refit.hip,
+// refit_sdf_mesh). Vertices whose divided positions have equal bits share one
+// welded vertex; an edge is the unordered pair of its welded end points. Ids
+// are in order of first appearance (vertex order; triangle order, then ab, ac,
+// bc). The incidence lists are CSR, each list in the order prep_sdf_mesh adds
+// its terms: ascending triangle id, then corner / then ab, ac, bc (a triangle
+// with welded corners appears more than once in a list).
+struct SdfTopo {
+  std::vector<uint32_t> weld;      // per vertex: welded vertex id
+  std::vector<uint32_t> tri_edge;  // 3 per triangle: welded edge id of ab, ac, bc
+  std::vector<uint32_t> v_off;     // n_wverts + 1
+  std::vector<uint32_t> v_inc;     // 3 * ntri entries: 3 * triangle + corner
+  std::vector<uint32_t> e_off;     // n_wedges + 1
+  std::vector<uint32_t> e_inc;     // 3 * ntri entries: triangle
+  uint32_t n_wverts = 0, n_wedges = 0;
+};
+// topo: also return the weld map (a dynamic handle keeps it).
 bool prep_sdf_mesh(const float *vpos4, int64_t nverts, const uint32_t *idx, int64_t nidx,
-                   SdfMeshHost &out, std::string &err);
+                   SdfMeshHost &out, std::string &err, SdfTopo *topo = nullptr);
+// Refit: m (from prep_sdf_mesh of the creation mesh, with its topo and idx)
+// moved to new positions, as rt_sdf_mesh_update_vertices defines it and the
+// device computes it (rt_sdf_refit.hip). The tree is refitted (refit_bvh8),
+// m.tri is rewritten from the divided new positions and m.pn recomputed with
+// prep_sdf_mesh's arithmetic, each welded vertex and edge summing its
+// incidence list in the stored order; the weld map stays the creation one.
+// When the moved mesh has the weld classes of creation, m.pn is bit for bit
+// prep_sdf_mesh's of the moved mesh.
+void refit_sdf_mesh(SdfMeshHost &m, const SdfTopo &topo, const uint32_t *idx, int64_t nidx, const float *new_vpos4);
 
 // Loop-free midpoint subdivision, `levels` times (config-5 stand-in mesh).
 bool subdivide_mesh(const float *vpos4, int64_t nverts, const uint32_t *idx, int64_t nidx, int levels,

@@ -38,31 +38,153 @@ struct KeyHash {
   }
 };
 
-}  // namespace
-
-bool prep_sdf_mesh(const float *vpos4, int64_t nverts, const uint32_t *idx, int64_t nidx,
-                   SdfMeshHost &out, std::string &err) {
-  out = SdfMeshHost();
-  if (!build_bvh8(vpos4, nverts, idx, nidx, out.bvh, err, kBvhTris)) return false;
-  const size_t ntri = (size_t)nidx / 3;
-  if (ntri == 0) { err = "mesh has no triangles"; return false; }
-
-  // positions after the renderer's v /= v.w (triangles_raytracing.cpp:307-309)
+// positions after the renderer's v /= v.w (triangles_raytracing.cpp:307-309)
+std::vector<P3> divided(const float *vpos4, int64_t nverts) {
   std::vector<P3> P((size_t)nverts);
   for (int64_t v = 0; v < nverts; ++v) {
     const float *q = vpos4 + 4 * v;
     P[(size_t)v] = {q[0] / q[3], q[1] / q[3], q[2] / q[3]};
   }
+  return P;
+}
+
+inline uint64_t edge_key(uint32_t wa, uint32_t wb) {
+  return wa < wb ? ((uint64_t)wa << 32 | wb) : ((uint64_t)wb << 32 | wa);
+}
+
+// The weld map of divided positions P and the incidence lists over it (SdfTopo, rt_host.h).
+// lists false: the vertex weld map only.
+SdfTopo sdf_topology(const std::vector<P3> &P, const uint32_t *idx, size_t ntri, bool lists) {
+  SdfTopo T;
   // weld by exact bits, ids in order of first appearance
   std::unordered_map<std::array<uint32_t, 3>, uint32_t, KeyHash> wmap;
-  std::vector<uint32_t> weld((size_t)nverts);
-  for (int64_t v = 0; v < nverts; ++v) {
+  T.weld.resize(P.size());
+  for (size_t v = 0; v < P.size(); ++v) {
     std::array<uint32_t, 3> k;
-    std::memcpy(k.data(), &P[(size_t)v], 12);
+    std::memcpy(k.data(), &P[v], 12);
     auto it = wmap.emplace(k, (uint32_t)wmap.size()).first;
-    weld[(size_t)v] = it->second;
+    T.weld[v] = it->second;
   }
-  std::vector<double> vacc(3 * wmap.size(), 0.0);
+  T.n_wverts = (uint32_t)wmap.size();
+  if (!lists) return T;
+  std::unordered_map<uint64_t, uint32_t> emap;
+  emap.reserve(ntri * 2);
+  T.tri_edge.resize(3 * ntri);
+  for (size_t t = 0; t < ntri; ++t) {
+    const uint32_t w[3] = {T.weld[idx[3 * t]], T.weld[idx[3 * t + 1]], T.weld[idx[3 * t + 2]]};
+    const uint64_t ek[3] = {edge_key(w[0], w[1]), edge_key(w[0], w[2]), edge_key(w[1], w[2])};
+    for (int k = 0; k < 3; ++k) T.tri_edge[3 * t + k] = emap.emplace(ek[k], (uint32_t)emap.size()).first->second;
+  }
+  T.n_wedges = (uint32_t)emap.size();
+  // CSR by counting; filling in ascending (triangle, slot) keeps each list in that order
+  T.v_off.assign((size_t)T.n_wverts + 1, 0);
+  T.e_off.assign((size_t)T.n_wedges + 1, 0);
+  for (size_t j = 0; j < 3 * ntri; ++j) {
+    ++T.v_off[(size_t)T.weld[idx[j]] + 1];
+    ++T.e_off[(size_t)T.tri_edge[j] + 1];
+  }
+  for (size_t w = 0; w < T.n_wverts; ++w) T.v_off[w + 1] += T.v_off[w];
+  for (size_t e = 0; e < T.n_wedges; ++e) T.e_off[e + 1] += T.e_off[e];
+  T.v_inc.resize(3 * ntri);
+  T.e_inc.resize(3 * ntri);
+  std::vector<uint32_t> vfill(T.v_off.begin(), T.v_off.end() - 1), efill(T.e_off.begin(), T.e_off.end() - 1);
+  for (size_t j = 0; j < 3 * ntri; ++j) {
+    T.v_inc[vfill[T.weld[idx[j]]]++] = (uint32_t)j;
+    T.e_inc[efill[T.tri_edge[j]]++] = (uint32_t)(j / 3);
+  }
+  return T;
+}
+
+// triangle corners in the BVH's leaf order (GTri order), original id in a.w
+void fill_sdf_tris(SdfMeshHost &out, const std::vector<P3> &P, const uint32_t *idx) {
+  out.tri.resize(out.bvh.tris.size() * 12);
+  for (size_t g = 0; g < out.bvh.tris.size(); ++g) {
+    const uint32_t id = out.bvh.tris[g].orig_id;
+    float *o = &out.tri[12 * g];
+    for (int k = 0; k < 3; ++k) {
+      const P3 p = P[idx[3 * (size_t)id + k]];
+      o[4 * k + 0] = p.x;
+      o[4 * k + 1] = p.y;
+      o[4 * k + 2] = p.z;
+      o[4 * k + 3] = 0.0f;
+    }
+    std::memcpy(&o[3], &id, 4);
+  }
+}
+
+}  // namespace
+
+void refit_sdf_mesh(SdfMeshHost &m, const SdfTopo &T, const uint32_t *idx, int64_t nidx, const float *new_vpos4) {
+  const size_t ntri = (size_t)nidx / 3;
+  refit_bvh8(m.bvh, new_vpos4, idx);
+  const std::vector<P3> P = divided(new_vpos4, (int64_t)T.weld.size());
+  fill_sdf_tris(m, P, idx);
+  // per triangle: the face normal (float) and the three corner angles (double)
+  std::vector<P3> fn(ntri);
+  std::vector<double> ang(3 * ntri);
+  for (size_t t = 0; t < ntri; ++t) {
+    const P3 vv[3] = {P[idx[3 * t]], P[idx[3 * t + 1]], P[idx[3 * t + 2]]};
+    const P3 n = cross3(sub(vv[1], vv[0]), sub(vv[2], vv[0]));
+    const float l = std::sqrt(dot3(n, n));
+    fn[t] = l > 0.0f ? P3{n.x / l, n.y / l, n.z / l} : P3{0.0f, 0.0f, 0.0f};
+    for (int k = 0; k < 3; ++k) {
+      const P3 u = vv[(k + 1) % 3], w = vv[(k + 2) % 3], o = vv[k];
+      const double ux = (double)u.x - o.x, uy = (double)u.y - o.y, uz = (double)u.z - o.z;
+      const double wx = (double)w.x - o.x, wy = (double)w.y - o.y, wz = (double)w.z - o.z;
+      const double lu = std::sqrt(ux * ux + uy * uy + uz * uz), lw = std::sqrt(wx * wx + wy * wy + wz * wz);
+      double a = 0.0;
+      if (lu > 0.0 && lw > 0.0) a = std::acos(std::min(1.0, std::max(-1.0, (ux * wx + uy * wy + uz * wz) / (lu * lw))));
+      ang[3 * t + k] = a;
+    }
+  }
+  // per welded vertex / edge: its list summed in the stored order, rounded once
+  std::vector<P3> vn(T.n_wverts), en(T.n_wedges);
+  for (size_t w = 0; w < T.n_wverts; ++w) {
+    double acc[3] = {0.0, 0.0, 0.0};
+    for (uint32_t j = T.v_off[w]; j < T.v_off[w + 1]; ++j) {
+      const uint32_t e = T.v_inc[j];
+      const P3 nf = fn[e / 3];
+      acc[0] += ang[e] * nf.x;
+      acc[1] += ang[e] * nf.y;
+      acc[2] += ang[e] * nf.z;
+    }
+    vn[w] = {(float)acc[0], (float)acc[1], (float)acc[2]};
+  }
+  for (size_t e = 0; e < T.n_wedges; ++e) {
+    double acc[3] = {0.0, 0.0, 0.0};
+    for (uint32_t j = T.e_off[e]; j < T.e_off[e + 1]; ++j) {
+      const P3 nf = fn[T.e_inc[j]];
+      acc[0] += nf.x;
+      acc[1] += nf.y;
+      acc[2] += nf.z;
+    }
+    en[e] = {(float)acc[0], (float)acc[1], (float)acc[2]};
+  }
+  m.pn.assign(ntri * 4 * kSdfFeatures, 0.0f);
+  for (size_t t = 0; t < ntri; ++t) {
+    float *o = &m.pn[t * 4 * kSdfFeatures];
+    for (int k = 0; k < 3; ++k) {
+      const P3 a = vn[T.weld[idx[3 * t + k]]], b = en[T.tri_edge[3 * t + k]];
+      o[4 * k + 0] = a.x; o[4 * k + 1] = a.y; o[4 * k + 2] = a.z;
+      o[4 * (3 + k) + 0] = b.x; o[4 * (3 + k) + 1] = b.y; o[4 * (3 + k) + 2] = b.z;
+    }
+    o[24] = fn[t].x;
+    o[25] = fn[t].y;
+    o[26] = fn[t].z;
+  }
+}
+
+bool prep_sdf_mesh(const float *vpos4, int64_t nverts, const uint32_t *idx, int64_t nidx,
+                   SdfMeshHost &out, std::string &err, SdfTopo *topo) {
+  out = SdfMeshHost();
+  if (!build_bvh8(vpos4, nverts, idx, nidx, out.bvh, err, kBvhTris)) return false;
+  const size_t ntri = (size_t)nidx / 3;
+  if (ntri == 0) { err = "mesh has no triangles"; return false; }
+
+  const std::vector<P3> P = divided(vpos4, nverts);
+  SdfTopo T = sdf_topology(P, idx, ntri, topo != nullptr);
+  const std::vector<uint32_t> &weld = T.weld;
+  std::vector<double> vacc(3 * (size_t)T.n_wverts, 0.0);
   std::unordered_map<uint64_t, std::array<double, 3>> eacc;
   eacc.reserve(ntri * 2);
   std::vector<P3> fn(ntri);
@@ -122,20 +244,8 @@ bool prep_sdf_mesh(const float *vpos4, int64_t nverts, const uint32_t *idx, int6
     o[25] = fn[t].y;
     o[26] = fn[t].z;
   }
-  // triangle corners in the BVH's leaf order (GTri order), original id in a.w
-  out.tri.resize(out.bvh.tris.size() * 12);
-  for (size_t g = 0; g < out.bvh.tris.size(); ++g) {
-    const uint32_t id = out.bvh.tris[g].orig_id;
-    float *o = &out.tri[12 * g];
-    for (int k = 0; k < 3; ++k) {
-      const P3 p = P[idx[3 * (size_t)id + k]];
-      o[4 * k + 0] = p.x;
-      o[4 * k + 1] = p.y;
-      o[4 * k + 2] = p.z;
-      o[4 * k + 3] = 0.0f;
-    }
-    std::memcpy(&o[3], &id, 4);
-  }
+  fill_sdf_tris(out, P, idx);
+  if (topo) *topo = std::move(T);
   return true;
 }
 

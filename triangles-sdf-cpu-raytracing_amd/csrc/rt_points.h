@@ -1,6 +1,7 @@
 // rt_points.h -- what the two closest-point units share: the SDF-mesh handle
-// (rt_sdfgen.hip creates and destroys it, rt_points.hip only reads its
-// immutable device arrays) and the device pieces of the closest-point walk
+// (rt_sdfgen.hip creates, updates and destroys it, rt_points.hip only reads
+// its device arrays, which change only under an update of an RT_MESH_DYNAMIC
+// handle, in stream order) and the device pieces of the closest-point walk
 // over the BVH8 (DESIGN.md sections 9 and 9a): Ericson's closest point on a
 // triangle with its Voronoi region, the squared distance to a child box and
 // the prune bound with its absolute slack.
@@ -31,6 +32,20 @@ struct rt_sdf_mesh {
   float *h_stage = nullptr;  // q_cap * 4 floats: points (3 per point), then distances
   float *d_p3 = nullptr, *d_out = nullptr;
   int64_t q_cap = 0;
+  // RT_MESH_DYNAMIC only (rt_sdf_mesh_update_vertices*, rt_sdf_refit.hip): the
+  // creation topology on the device, scratch, and the event every update
+  // records after its last kernel. The host copies host.tri / host.pn are
+  // dropped at creation: after an update only the device arrays are current.
+  bool dynamic = false;
+  int64_t nverts = 0, ntri = 0;
+  uint32_t n_wverts = 0, n_wedges = 0;
+  uint32_t *d_idx = nullptr, *d_weld = nullptr, *d_tri_edge = nullptr;
+  uint32_t *d_v_off = nullptr, *d_v_inc = nullptr, *d_e_off = nullptr, *d_e_inc = nullptr;
+  float4 *d_vstage = nullptr, *d_fn = nullptr, *d_vn = nullptr, *d_en = nullptr;
+  double *d_ang = nullptr;
+  std::vector<uint32_t> level_first;
+  hipEvent_t updated = nullptr;
+  int64_t dev_bytes = 0;  // what the handle's mesh arrays hold on the device (rt_sdf_mesh_device_bytes)
 };
 
 namespace rtsdf {

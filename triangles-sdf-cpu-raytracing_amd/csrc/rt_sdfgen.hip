@@ -27,6 +27,7 @@
 #include "rt_layout.h"
 #include "rt_math.h"
 #include "rt_points.h"
+#include "rt_sdf_refit.h"
 
 using namespace rtd;
 using namespace rtsdf;
@@ -147,6 +148,82 @@ int upload(T **d, const T *h, size_t n) {
   return RT_OK;
 }
 
+// What an RT_MESH_DYNAMIC handle adds (rt_points.h): the creation topology,
+// the vertex staging buffer, scratch, and the event of the updates.
+int upload_dynamic(rt_sdf_mesh *m, const rth::SdfTopo &t, const uint32_t *idx, int64_t nidx) {
+  const size_t ntri = (size_t)m->ntri, nv = (size_t)m->nverts;
+  m->n_wverts = t.n_wverts;
+  m->n_wedges = t.n_wedges;
+  m->level_first = rth::bvh_level_first(m->host.bvh.nodes);
+  if (int rc = upload(&m->d_idx, idx, (size_t)nidx)) return rc;
+  if (int rc = upload(&m->d_weld, t.weld.data(), t.weld.size())) return rc;
+  if (int rc = upload(&m->d_tri_edge, t.tri_edge.data(), t.tri_edge.size())) return rc;
+  if (int rc = upload(&m->d_v_off, t.v_off.data(), t.v_off.size())) return rc;
+  if (int rc = upload(&m->d_v_inc, t.v_inc.data(), t.v_inc.size())) return rc;
+  if (int rc = upload(&m->d_e_off, t.e_off.data(), t.e_off.size())) return rc;
+  if (int rc = upload(&m->d_e_inc, t.e_inc.data(), t.e_inc.size())) return rc;
+  HIP_TRY(hipMalloc(reinterpret_cast<void **>(&m->d_vstage), std::max<size_t>(nv, 1) * 16));
+  HIP_TRY(hipMalloc(reinterpret_cast<void **>(&m->d_fn), ntri * 16));
+  HIP_TRY(hipMalloc(reinterpret_cast<void **>(&m->d_ang), ntri * 24));
+  HIP_TRY(hipMalloc(reinterpret_cast<void **>(&m->d_vn), (size_t)t.n_wverts * 16));
+  HIP_TRY(hipMalloc(reinterpret_cast<void **>(&m->d_en), (size_t)t.n_wedges * 16));
+  HIP_TRY(hipEventCreateWithFlags(&m->updated, hipEventDisableTiming));
+  m->dev_bytes += (int64_t)(4 * (size_t)nidx + 16 * nv + 4 * nv + 12 * ntri + 4 * ((size_t)t.n_wverts + 1) + 12 * ntri +
+                            4 * ((size_t)t.n_wedges + 1) + 12 * ntri + 16 * ntri + 24 * ntri +
+                            16 * (size_t)t.n_wverts + 16 * (size_t)t.n_wedges);
+  // after an update only the device arrays are current: no stale host copy is kept
+  std::vector<float>().swap(m->host.tri);
+  std::vector<float>().swap(m->host.pn);
+  return RT_OK;
+}
+
+int check_update(const rt_sdf_mesh *m, const float *vpos4, int64_t nverts, const char *who) {
+  if (!m) return rterr::set(RT_E_INVALID, std::string(who) + ": handle is NULL");
+  if (!m->dynamic) return rterr::set(RT_E_STATE, std::string(who) + ": the handle was not created with RT_MESH_DYNAMIC");
+  if (!vpos4) return rterr::set(RT_E_INVALID, std::string(who) + ": vertex pointer is NULL");
+  if (nverts != m->nverts)
+    return rterr::set(RT_E_INVALID, std::string(who) + ": nverts " + std::to_string(nverts) + ", created with " +
+                                        std::to_string(m->nverts));
+  return RT_OK;
+}
+
+// Queues one refit on `st` and records the handle's event behind it. Only launches.
+int update_device(rt_sdf_mesh *m, const float *d_vpos4, hipStream_t st) {
+  SdfRefitArgs a{};
+  a.nodes = m->d_nodes;
+  a.tri = m->d_tri;
+  a.pn = m->d_pn;
+  a.root = m->root;
+  a.vpos4 = d_vpos4;
+  a.idx = m->d_idx;
+  a.weld = m->d_weld;
+  a.tri_edge = m->d_tri_edge;
+  a.v_off = m->d_v_off;
+  a.v_inc = m->d_v_inc;
+  a.e_off = m->d_e_off;
+  a.e_inc = m->d_e_inc;
+  a.fn = m->d_fn;
+  a.ang = m->d_ang;
+  a.vn = m->d_vn;
+  a.en = m->d_en;
+  a.ntri = (uint32_t)m->ntri;
+  a.n_wverts = m->n_wverts;
+  a.n_wedges = m->n_wedges;
+  a.level_first = m->level_first.data();
+  a.levels = m->level_first.empty() ? 0 : (int32_t)m->level_first.size() - 1;
+  m->oct_depth = -1;  // the octree cache is of the mesh before
+  std::vector<uint8_t>().swap(m->oct_nodes);
+  const int rc = sdf_refit_launch(a, st);
+  HIP_TRY(hipEventRecord(m->updated, st));  // (also behind a partly queued refit)
+  return rc;
+}
+
+// The handle's own host entries read behind the last update (its event).
+int wait_updated(const rt_sdf_mesh *m, hipStream_t st) {
+  if (m->updated) HIP_TRY(hipStreamWaitEvent(st, m->updated, 0));
+  return RT_OK;
+}
+
 // The size checks of a lattice query, and its launch's workgroups: one 4x4x4
 // brick of samples per wave.
 int grid_blocks(const uint32_t size[3], uint32_t &blocks) {
@@ -201,6 +278,7 @@ int query_host(rt_sdf_mesh *m, const float *p3, int64_t n, float *out) {
                                        hipGetErrorString(e) + (stale.empty() ? "" : "; " + stale));
   int rc = query_staging(m, n);
   if (rc != RT_OK) return rc;
+  if ((rc = wait_updated(m, m->qs)) != RT_OK) return rc;
   for (int64_t i0 = 0; i0 < n; i0 += m->q_cap) {
     const int64_t k = std::min(m->q_cap, n - i0);
     std::memcpy(m->h_stage, p3 + 3 * i0, (size_t)k * 12);
@@ -245,15 +323,25 @@ extern "C" {
 
 int rt_sdf_mesh_create(const float *vpos4, int64_t nverts, const uint32_t *idx, int64_t nidx,
                        rt_sdf_mesh **out) {
+  return rt_sdf_mesh_create_ex(vpos4, nverts, idx, nidx, 0u, out);
+}
+
+int rt_sdf_mesh_create_ex(const float *vpos4, int64_t nverts, const uint32_t *idx, int64_t nidx, uint32_t flags,
+                          rt_sdf_mesh **out) {
   if (!out || (!vpos4 && nverts) || (!idx && nidx) || nverts < 0 || nidx < 0)
     return rterr::set(RT_E_INVALID, "bad mesh arguments");
   *out = nullptr;
+  if (flags & ~RT_MESH_DYNAMIC) return rterr::set(RT_E_INVALID, "rt_sdf_mesh_create_ex: unknown flag bits");
   rt_sdf_mesh *m = new rt_sdf_mesh();
+  m->dynamic = (flags & RT_MESH_DYNAMIC) != 0;
   std::string err;
-  if (!rth::prep_sdf_mesh(vpos4, nverts, idx, nidx, m->host, err)) {
+  rth::SdfTopo topo;
+  if (!rth::prep_sdf_mesh(vpos4, nverts, idx, nidx, m->host, err, m->dynamic ? &topo : nullptr)) {
     delete m;
     return rterr::set(RT_E_INVALID, err);
   }
+  m->nverts = nverts;
+  m->ntri = nidx / 3;
   const rth::BVHGpu &b = m->host.bvh;
   m->root = b.root_word;
   m->stack_cap = 7 * std::max(b.max_depth, 1) + 1;
@@ -265,11 +353,80 @@ int rt_sdf_mesh_create(const float *vpos4, int64_t nverts, const uint32_t *idx, 
   if (rc == RT_OK) rc = upload(&m->d_nodes, b.nodes.data(), b.nodes.size());
   if (rc == RT_OK) rc = upload(&m->d_tri, reinterpret_cast<const float4 *>(m->host.tri.data()), m->host.tri.size() / 4);
   if (rc == RT_OK) rc = upload(&m->d_pn, reinterpret_cast<const float4 *>(m->host.pn.data()), m->host.pn.size() / 4);
+  m->dev_bytes = (int64_t)(b.nodes.size() * sizeof(rtl::GNode) + m->host.tri.size() * 4 + m->host.pn.size() * 4);
+  if (rc == RT_OK && m->dynamic) rc = upload_dynamic(m, topo, idx, nidx);
   if (rc != RT_OK) {
     rt_sdf_mesh_destroy(m);
     return rc;
   }
   *out = m;
+  return RT_OK;
+}
+
+int rt_sdf_mesh_update_vertices_device(rt_sdf_mesh *m, const float *d_vpos4, int64_t nverts, void *stream) {
+  if (int rc = check_update(m, d_vpos4, nverts, "rt_sdf_mesh_update_vertices_device")) return rc;
+  return update_device(m, d_vpos4, (hipStream_t)stream);
+}
+
+int rt_sdf_mesh_update_vertices(rt_sdf_mesh *m, const float *vpos4, int64_t nverts) {
+  if (int rc = check_update(m, vpos4, nverts, "rt_sdf_mesh_update_vertices")) return rc;
+  int prev = 0;
+  HIP_TRY(hipGetDevice(&prev));
+  HIP_TRY(hipSetDevice(m->device));
+  int rc = RT_OK;
+  // (the staging buffer may still be read by an earlier update's kernels)
+  hipError_t e = hipEventSynchronize(m->updated);
+  if (e == hipSuccess) e = rtdma::h2d(m->d_vstage, vpos4, 16 * (size_t)nverts, nullptr);
+  if (e != hipSuccess) rc = rterr::set(RT_E_DEVICE, rterr::hip_fail("rt_sdf_mesh_update_vertices: vertex upload", e));
+  if (!rc) rc = update_device(m, reinterpret_cast<const float *>(m->d_vstage), nullptr);
+  if (!rc) {
+    e = hipEventSynchronize(m->updated);
+    if (e != hipSuccess) rc = rterr::set(RT_E_DEVICE, rterr::hip_fail("rt_sdf_mesh_update_vertices: wait", e));
+  }
+  HIP_NOTE(hipSetDevice(prev));
+  return rc;
+}
+
+int rt_sdf_mesh_get_pseudonormals(const rt_sdf_mesh *m, float *pn28, int64_t ntri) {
+  if (!m || !pn28) return rterr::set(RT_E_INVALID, "rt_sdf_mesh_get_pseudonormals: NULL argument");
+  if (ntri != m->ntri) return rterr::set(RT_E_INVALID, "rt_sdf_mesh_get_pseudonormals: ntri is not the handle's");
+  int prev = 0;
+  HIP_TRY(hipGetDevice(&prev));
+  HIP_TRY(hipSetDevice(m->device));
+  hipError_t e = hipDeviceSynchronize();
+  if (e == hipSuccess) e = rtdma::d2h(pn28, m->d_pn, (size_t)ntri * 28 * 4, nullptr);
+  HIP_NOTE(hipSetDevice(prev));
+  if (e != hipSuccess) return rterr::set(RT_E_DEVICE, rterr::hip_fail("rt_sdf_mesh_get_pseudonormals", e));
+  return RT_OK;
+}
+
+int64_t rt_sdf_mesh_device_bytes(const rt_sdf_mesh *m) {
+  if (!m) return rterr::set(RT_E_INVALID, "rt_sdf_mesh_device_bytes: handle is NULL");
+  return m->dev_bytes;
+}
+
+// Diagnostic (not part of include/rtamd.h): the handle's device tree, as it is
+// now: n_inner GNode records (224 bytes each) and n_tri triangle records (48
+// bytes each: a.xyz, id | b.xyz, 0 | c.xyz, 0). Two-call protocol: with
+// nodes224 = tri48 = NULL only the counts are returned; else *n_inner / *n_tri
+// are the buffers' capacities.
+int rtx_sdf_mesh_download(const rt_sdf_mesh *m, void *nodes224, int64_t *n_inner, void *tri48, int64_t *n_tri) {
+  if (!m || !n_inner || !n_tri) return rterr::set(RT_E_INVALID, "rtx_sdf_mesh_download: NULL argument");
+  const int64_t ni = (int64_t)m->host.bvh.nodes.size(), nt = (int64_t)m->host.bvh.tris.size();
+  if (nodes224 || tri48) {
+    if (!nodes224 || !tri48 || *n_inner < ni || *n_tri < nt)
+      return rterr::set(RT_E_INVALID, "rtx_sdf_mesh_download: buffers too small");
+    int prev = 0;
+    HIP_TRY(hipGetDevice(&prev));
+    HIP_TRY(hipSetDevice(m->device));
+    hipError_t e = hipDeviceSynchronize();
+    if (e == hipSuccess && ni) e = rtdma::d2h(nodes224, m->d_nodes, (size_t)ni * sizeof(rtl::GNode), nullptr);
+    if (e == hipSuccess && nt) e = rtdma::d2h(tri48, m->d_tri, (size_t)nt * 48, nullptr);
+    HIP_NOTE(hipSetDevice(prev));
+    if (e != hipSuccess) return rterr::set(RT_E_DEVICE, rterr::hip_fail("rtx_sdf_mesh_download", e));
+  }
+  *n_inner = ni;
+  *n_tri = nt;
   return RT_OK;
 }
 
@@ -285,6 +442,7 @@ int rt_sdf_mesh_grid(rt_sdf_mesh *m, const uint32_t size[3], float *values) {
   const int64_t n = (int64_t)size[0] * size[1] * size[2];
   g_stale_seen = rterr::take_stale();
   HIP_TRY(hipSetDevice(m->device));
+  if (int rc = wait_updated(m, nullptr)) return rc;
   float *d = nullptr;
   HIP_TRY(hipMalloc(&d, (size_t)n * 4));
   hipLaunchKernelGGL(sdf_kernel<true>, dim3(blocks), dim3(kWave), lds_bytes(m), 0, dev_of(m), nullptr,
@@ -343,6 +501,11 @@ int rt_sdf_mesh_destroy(rt_sdf_mesh *m) {
   if (m->d_nodes) HIP_NOTE(hipFree(m->d_nodes));
   if (m->d_tri) HIP_NOTE(hipFree(m->d_tri));
   if (m->d_pn) HIP_NOTE(hipFree(m->d_pn));
+  for (void *p : {(void *)m->d_idx, (void *)m->d_weld, (void *)m->d_tri_edge, (void *)m->d_v_off, (void *)m->d_v_inc,
+                  (void *)m->d_e_off, (void *)m->d_e_inc, (void *)m->d_vstage, (void *)m->d_fn, (void *)m->d_ang,
+                  (void *)m->d_vn, (void *)m->d_en})
+    if (p) HIP_NOTE(hipFree(p));
+  if (m->updated) HIP_NOTE(hipEventDestroy(m->updated));
   delete m;
   return RT_OK;
 }

@@ -170,6 +170,12 @@ _SIGS = {
     "rt_sdf_mesh_device": (C.c_int, [C.c_void_p]),
     "rt_sdf_mesh_octree": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.c_void_p]),
     "rt_sdf_mesh_destroy": (C.c_int, [C.c_void_p]),
+    "rt_sdf_mesh_create_ex": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_uint32,
+                                        C.POINTER(C.c_void_p)]),
+    "rt_sdf_mesh_update_vertices": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
+    "rt_sdf_mesh_update_vertices_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "rt_sdf_mesh_get_pseudonormals": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
+    "rt_sdf_mesh_device_bytes": (C.c_int64, [C.c_void_p]),
     "rt_mesh_subdivide": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p,
                                     C.POINTER(C.c_int64), C.c_void_p, C.POINTER(C.c_int64)]),
     "rt_camera_init": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(CameraState)]),
@@ -218,6 +224,12 @@ _XSIGS = {
     # unused LDS added to the point query's launches (occupancy measurements)
     "rtx_set_points_lds_pad": (C.c_int, [C.c_int32]),
     "rtx_sdf_mesh_lds_bytes": (C.c_int64, [C.c_void_p]),
+    # the SDF-mesh refit's diagnostics: a handle's device tree, and the host
+    # restatement of prep + refit (no GPU)
+    "rtx_sdf_mesh_download": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_void_p,
+                                        C.POINTER(C.c_int64)]),
+    "rtx_sdf_mesh_refit_host": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                          C.POINTER(C.c_int64), C.c_void_p, C.POINTER(C.c_int64), C.c_void_p]),
 }
 
 

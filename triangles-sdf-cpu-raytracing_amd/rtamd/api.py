@@ -717,14 +717,54 @@ class SDFMesh:
     """A triangle mesh prepared on the GPU for signed-distance queries
     (rt_sdf_mesh_*): point queries, SDFGrid lattices and sparse SDFOctrees in
     the reference's file formats (grid_raytracing.cpp:127-134,
-    octree_raytracing.cpp:8-16). Generates the config-3/4 stand-ins."""
+    octree_raytracing.cpp:8-16). Generates the config-3/4 stand-ins.
 
-    def __init__(self, mesh: SimpleMesh):
+    dynamic: the vertices may be moved afterwards (update_vertices*,
+    RT_MESH_DYNAMIC): the handle then keeps its index array, the weld map of
+    creation with its incidence lists, a vertex staging buffer and scratch on
+    the device (device_bytes()), and an update recomputes tree boxes, triangle
+    records and pseudonormals there."""
+
+    def __init__(self, mesh: SimpleMesh, dynamic: bool = False):
         v = np.ascontiguousarray(mesh.vPos4f, np.float32)
         i = np.ascontiguousarray(mesh.indices, np.uint32)
         h = C.c_void_p()
-        check(lib().rt_sdf_mesh_create(_p(v), len(v), _p(i), len(i), C.byref(h)))
+        if dynamic:
+            check(lib().rt_sdf_mesh_create_ex(_p(v), len(v), _p(i), len(i), RT_MESH_DYNAMIC, C.byref(h)))
+        else:
+            check(lib().rt_sdf_mesh_create(_p(v), len(v), _p(i), len(i), C.byref(h)))
         self._h = h
+        self.ntri = len(i) // 3
+
+    def update_vertices(self, vPos4f):
+        """Move the mesh to new positions (float32 [N, 4] on the host, N as at
+        creation): rt_sdf_mesh_update_vertices. Returns when the update is complete."""
+        v = np.ascontiguousarray(vPos4f, np.float32)
+        if v.ndim != 2 or v.shape[1] != 4:
+            raise RtError(f"update_vertices: shape {v.shape}, expected [N, 4]")
+        check(lib().rt_sdf_mesh_update_vertices(self._h, _p(v), len(v)))
+
+    def update_vertices_device(self, ptr: int, nverts: int, stream: int | None = None):
+        """The same from device memory (float32[4 * nverts] at ptr, e.g. a torch
+        tensor's data_ptr()), queued on `stream` after the work already there:
+        rt_sdf_mesh_update_vertices_device. The call only launches."""
+        check(lib().rt_sdf_mesh_update_vertices_device(self._h, C.c_void_p(ptr) if ptr else None, int(nverts),
+                                                       C.c_void_p(stream) if stream else None))
+
+    def pseudonormals(self) -> np.ndarray:
+        """The pseudonormals the device holds now, float32 [T, 7, 4] (features
+        0..2 vertex a, b, c; 3 ab; 4 ac; 5 bc; 6 face), after one device
+        synchronisation: rt_sdf_mesh_get_pseudonormals."""
+        pn = np.empty((self.ntri, 7, 4), np.float32)
+        check(lib().rt_sdf_mesh_get_pseudonormals(self._h, _p(pn), self.ntri))
+        return pn
+
+    def device_bytes(self) -> int:
+        """Bytes of the handle's mesh arrays on the device (rt_sdf_mesh_device_bytes)."""
+        n = int(lib().rt_sdf_mesh_device_bytes(self._h))
+        if n < 0:
+            check(n)
+        return n
 
     def points(self, p3) -> np.ndarray:
         p3 = np.ascontiguousarray(p3, np.float32).reshape(-1, 3)

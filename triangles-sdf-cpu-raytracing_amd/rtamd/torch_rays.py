@@ -36,7 +36,9 @@ is a frame; for an rtamd.InstancedScene it is the way to a picture.
 are the point queries of an rtamd.SDFMesh (rt_sdf_mesh_points_device,
 rt_sdf_mesh_grid_device): signed distance, closest point, triangle and Voronoi
 feature of points on the GPU, optionally only within a radius, and the
-SDFGrid lattice as a tensor.
+SDFGrid lattice as a tensor. torch_rays.update_sdf_mesh(sdf_mesh, verts) moves
+an SDFMesh(mesh, dynamic=True) to new vertex positions on the current stream
+(rt_sdf_mesh_update_vertices_device), ahead of the queries queued after it.
 """
 from __future__ import annotations
 
@@ -133,6 +135,36 @@ def update_vertices(scene, verts) -> None:
             verts = torch.cat([verts, verts.new_ones((verts.shape[0], 1))], dim=1)
         scene.update_vertices_device(verts.data_ptr(), verts.shape[0],
                                      stream=torch.cuda.current_stream(device).cuda_stream)
+
+
+def update_sdf_mesh(sdf_mesh, verts) -> None:
+    """Move a dynamic rtamd.SDFMesh (SDFMesh(mesh, dynamic=True)) to the
+    positions in `verts`, with the tensor rules of update_vertices: a
+    contiguous float32 tensor on the handle's device with one row per creation
+    vertex, [V, 4] (x, y, z, w) read in place or [V, 3], which gets a w = 1
+    column through torch first. The update is queued on
+    torch.cuda.current_stream(), after the torch kernels that produced `verts`
+    there and before the queries queued there afterwards
+    (rt_sdf_mesh_update_vertices_device); the call only launches, with no host
+    wait. Raises ValueError on a bad tensor before anything is launched."""
+    import torch
+
+    device = sdf_mesh.device()
+    if not isinstance(verts, torch.Tensor):
+        raise ValueError(f"verts: expected a torch tensor, got {type(verts).__name__}")
+    if verts.dtype != torch.float32:
+        raise ValueError(f"verts: dtype {verts.dtype}, expected torch.float32")
+    if verts.dim() != 2 or verts.shape[1] not in (3, 4) or verts.shape[0] == 0:
+        raise ValueError(f"verts: shape {tuple(verts.shape)}, expected [V, 4] or [V, 3]")
+    if verts.device.type != "cuda" or verts.device.index != device:
+        raise ValueError(f"verts: on {verts.device}, the mesh is on HIP device {device}")
+    if not verts.is_contiguous():
+        raise ValueError("verts: not contiguous")
+    with torch.cuda.device(device):
+        if verts.shape[1] == 3:
+            verts = torch.cat([verts, verts.new_ones((verts.shape[0], 1))], dim=1)
+        sdf_mesh.update_vertices_device(verts.data_ptr(), verts.shape[0],
+                                        stream=torch.cuda.current_stream(device).cuda_stream)
 
 
 def update_instances(scene, xforms, first: int = 0) -> None:
