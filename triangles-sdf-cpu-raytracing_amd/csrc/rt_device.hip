@@ -34,6 +34,7 @@
 #include "rt_error.h"
 #include "rt_host.h"
 #include "rt_queue.h"
+#include "rt_ray_io.h"
 #include "rt_scene.h"
 #include "rt_shade.h"
 
@@ -2116,19 +2117,7 @@ void trace_rays_kernel(S sc, PlaneDev pl, rt_ray_batch b) {
     }
     if (!active) return;
     if (!traced) h = rays_closest<kRBlock, MODE == kRaysNormal>(sc, o, d, tn, tf, st, b.d_prim != nullptr, cnt);
-    if (pl.on) {  // SceneUnion::intersect, as union_intersect
-      float tp = kInf, ap = 1.0f;
-      const bool ph = plane_hit(pl, o, d, tn, tf, tp, ap);
-      if (!(h.t < (ph ? tp : kInf))) h = ph ? Hit{true, tp, pl.n, -2} : miss_hit();
-    }
-    if (b.d_hit) b.d_hit[i] = h.hit ? 1 : 0;
-    if (b.d_t) b.d_t[i] = h.t;
-    if constexpr (MODE == kRaysNormal) {
-      b.d_normal[3 * i] = h.n.x;
-      b.d_normal[3 * i + 1] = h.n.y;
-      b.d_normal[3 * i + 2] = h.n.z;
-    }
-    if (b.d_prim) b.d_prim[i] = h.hit ? h.prim : -1;
+    store_closest<MODE>(b, i, pl, RayIn{o, d, tn, tf}, h);
   }
 }
 
@@ -2142,11 +2131,9 @@ void launch_rays_t(const S &sc, const PlaneDev &pl, const float *o, const float 
 template <class S, int MAXD>
 void launch_trace_t(const S &sc, const PlaneDev &pl, const rt_ray_batch &b, int mode, hipStream_t stream) {
   const unsigned blocks = (unsigned)((b.n + kRBlock - 1) / kRBlock);
-  switch (mode) {
-    case kRaysAny: trace_rays_kernel<S, MAXD, kRaysAny><<<blocks, kRBlock, 0, stream>>>(sc, pl, b); break;
-    case kRaysClosest: trace_rays_kernel<S, MAXD, kRaysClosest><<<blocks, kRBlock, 0, stream>>>(sc, pl, b); break;
-    default: trace_rays_kernel<S, MAXD, kRaysNormal><<<blocks, kRBlock, 0, stream>>>(sc, pl, b); break;
-  }
+  with_mode(mode, [&](auto m) {
+    trace_rays_kernel<S, MAXD, decltype(m)::value><<<blocks, kRBlock, 0, stream>>>(sc, pl, b);
+  });
 }
 
 // rt_trace_rays_device's launch: an instanced scene goes to rt_instances.hip,

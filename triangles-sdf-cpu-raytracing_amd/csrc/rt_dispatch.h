@@ -1,7 +1,7 @@
 // rt_dispatch.h -- which kernel instantiation serves a scene. The rules are
 // written here once: the LDS stack slot options 4 / 7 / 15 / 31 (pick_maxd,
 // rt_scene.hip, chooses among them), the octree's packed coordinates for up to
-// 7 slots, and a grid's three launch modes. Every launcher (rt_device.hip,
+// 7 slots, a grid's three launch modes, and the three modes of a ray batch. Every launcher (rt_device.hip,
 // rt_instances.hip) passes a generic callable and gets the adapter and the
 // slot count as types; rtx_dispatch_probe (rt_scene.hip) reports the same
 // mapping to the tests.
@@ -45,6 +45,18 @@ void with_slots(int maxd, F &&f) {
     case 7: f(Slots<7>{}); break;
     case 15: f(Slots<15>{}); break;
     default: f(Slots<31>{}); break;
+  }
+}
+
+// f(Mode<M>{}) for the mode of a ray batch (kRaysAny / kRaysClosest / kRaysNormal, rt_shade.h)
+template <int M>
+using Mode = std::integral_constant<int, M>;
+template <class F>
+void with_mode(int mode, F &&f) {
+  switch (mode) {
+    case kRaysAny: f(Mode<kRaysAny>{}); break;
+    case kRaysClosest: f(Mode<kRaysClosest>{}); break;
+    default: f(Mode<kRaysNormal>{}); break;
   }
 }
 

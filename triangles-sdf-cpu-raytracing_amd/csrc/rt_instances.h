@@ -131,10 +131,10 @@ int trace_mixed_launch(const MixedArgs &a, const rtd::PlaneDev &pl, const rt_ray
 // as shade_instances_launch
 int shade_mixed_launch(const MixedArgs &a, const rtd::PlaneDev &pl, const rt_render_params &p, const rt_ray_batch &b,
                        uint32_t *d_color, uint32_t flags, hipStream_t st);
-// as blas_entry_launch: the mesh view of a record of kind RT_SCENE_MESH
-int mixed_entry_launch(BlasRec *entry, const rtd::MeshDev &md, hipStream_t st);
-// as tlas_boxes_launch with the object boxes of the mixed table (t.blas is not
-// read): a mesh's rbox, the cube (-1,-1,-1, 1,1,1) for both SDF kinds
+// (the mesh view of a record of kind RT_SCENE_MESH is rewritten by
+// blas_entry_launch on &record->mesh; kind and variant stay)
+// rt_tlas.hip: as tlas_boxes_launch with the object boxes of the mixed table
+// (t.blas is not read): a mesh's rbox, the cube (-1,-1,-1, 1,1,1) for both SDF kinds
 int mixed_boxes_launch(const TlasArgs &t, const BlasRec *tab, int32_t first, int32_t count, const float *d_xsrc,
                        int32_t only_blas, hipStream_t st);
 

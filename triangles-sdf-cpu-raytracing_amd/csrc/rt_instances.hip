@@ -4,8 +4,9 @@
 // bottom-level scenes. Semantics: include/rtamd.h and DESIGN.md section 4a.
 //
 // A translation unit of its own: the kernels of rt_device.hip compile exactly
-// as before whatever is instantiated here. The stack slot switch is
-// rt_dispatch.h's, the mode enum rt_shade.h's.
+// as before whatever is instantiated here. The stack slot and mode switches
+// are rt_dispatch.h's, the per-lane helpers rt_instance_dev.h's, the ray load
+// and the store tails rt_ray_io.h's.
 //
 // The instance loop is wave-uniform. An instance record (64 bytes) and the
 // MeshDev of its bottom-level scene are read through addresses every lane
@@ -19,37 +20,14 @@
 
 #include "rt_dispatch.h"
 #include "rt_error.h"
-#include "rt_instances.h"
-#include "rt_layout.h"
-#include "rt_math.h"
-#include "rt_scenes.h"
+#include "rt_instance_dev.h"
+#include "rt_ray_io.h"
 
 using namespace rtd;
 
 namespace {
 
 constexpr int kIBlock = 64;  // one wave, as trace_rays_kernel (rt_device.hip)
-
-// world -> object, with the operation order of include/rtamd.h (no fusing)
-__device__ __forceinline__ f3 xf_point(const float *m, f3 p) {
-  return f3{((m[0] * p.x + m[1] * p.y) + m[2] * p.z) + m[3], ((m[4] * p.x + m[5] * p.y) + m[6] * p.z) + m[7],
-            ((m[8] * p.x + m[9] * p.y) + m[10] * p.z) + m[11]};
-}
-__device__ __forceinline__ f3 xf_dir(const float *m, f3 d) {
-  return f3{(m[0] * d.x + m[1] * d.y) + m[2] * d.z, (m[4] * d.x + m[5] * d.y) + m[6] * d.z,
-            (m[8] * d.x + m[9] * d.y) + m[10] * d.z};
-}
-
-// The traversal's own root test on the transformed ray, ahead of the traversal:
-// mesh_root evaluates root_box_miss on exactly these operands first, so a lane
-// it rejects here would return "no hit" there. A leaf root has no such test
-// and is never pre-culled. (root_box_miss itself passes every ray whose 1/d
-// has a non-finite component.)
-__device__ __forceinline__ bool root_passes(const MeshDev &md, f3 o, f3 d, float tn, float tf) {
-  if (md.root & rtl::kLeafBit) return true;
-  const f3 inv{1.0f / d.x, 1.0f / d.y, 1.0f / d.z};
-  return !root_box_miss(md.rbox, o, inv, tn, tf);
-}
 
 template <int SLOTS, int MODE>
 __global__ __launch_bounds__(kIBlock) void trace_instances_kernel(const rti::InstRec *__restrict__ inst,
@@ -61,14 +39,9 @@ __global__ __launch_bounds__(kIBlock) void trace_instances_kernel(const rti::Ins
   // the whole wave): they carry active = false and touch no memory
   const bool active = i < b.n;
   LdsStack<kIBlock, MeshS::kFields> st{stk + threadIdx.x};
-  f3 o{0.0f, 0.0f, 0.0f}, d{0.0f, 0.0f, 1.0f};
-  float tn = b.tnear, tf = b.tfar;
-  if (active) {
-    o = f3{b.d_origin[3 * i], b.d_origin[3 * i + 1], b.d_origin[3 * i + 2]};
-    d = f3{b.d_dir[3 * i], b.d_dir[3 * i + 1], b.d_dir[3 * i + 2]};
-    if (b.d_tnear) tn = b.d_tnear[i];
-    if (b.d_tfar) tf = b.d_tfar[i];
-  }
+  const RayIn ray = load_ray(b, i, active);
+  const f3 o = ray.o, d = ray.d;
+  const float tn = ray.tn, tf = ray.tf;
   NoCnt cnt;
   if constexpr (MODE == kRaysAny) {
     // OR over the instances of the bottom-level any hit under the full tFar;
@@ -89,11 +62,7 @@ __global__ __launch_bounds__(kIBlock) void trace_instances_kernel(const rti::Ins
       }
     }
     if (!active) return;
-    if (!occ && pl.on) {  // HitInfo::hitten of the union: the OR of both
-      float tp, ap;
-      occ = plane_hit(pl, o, d, tn, tf, tp, ap);
-    }
-    b.d_hit[i] = occ ? 1 : 0;
+    store_any(b, i, pl, ray, occ);
   } else {
     float best = kInf;
     int32_t wi = -1;      // winning instance
@@ -123,34 +92,8 @@ __global__ __launch_bounds__(kIBlock) void trace_instances_kernel(const rti::Ins
       }
     }
     if (!active) return;
-    Hit h = miss_hit();
-    if (wi >= 0) {
-      // the winner's record and triangle, per lane (lanes differ in wi)
-      const float *m = inst[wi].m;
-      const rtl::GTri *tris = tab[inst[wi].blas].tris;
-      h.hit = true;
-      h.t = best;
-      if constexpr (MODE == kRaysNormal) {
-        const f3 n = tri_normal(tris, wk);  // object space
-        // the inverse transpose of the object-to-world map: M^T n
-        h.n = normalize(f3{(m[0] * n.x + m[4] * n.y) + m[8] * n.z, (m[1] * n.x + m[5] * n.y) + m[9] * n.z,
-                           (m[2] * n.x + m[6] * n.y) + m[10] * n.z});
-      }
-      if (b.d_prim) h.prim = (int64_t)(((uint64_t)(uint32_t)wi << 32) | (uint64_t)tris[wk].orig_id);
-    }
-    if (pl.on) {  // SceneUnion::intersect, as trace_rays_kernel
-      float tp = kInf, ap = 1.0f;
-      const bool ph = plane_hit(pl, o, d, tn, tf, tp, ap);
-      if (!(h.t < (ph ? tp : kInf))) h = ph ? Hit{true, tp, pl.n, -2} : miss_hit();
-    }
-    if (b.d_hit) b.d_hit[i] = h.hit ? 1 : 0;
-    if (b.d_t) b.d_t[i] = h.t;
-    if constexpr (MODE == kRaysNormal) {
-      b.d_normal[3 * i] = h.n.x;
-      b.d_normal[3 * i + 1] = h.n.y;
-      b.d_normal[3 * i + 2] = h.n.z;
-    }
-    if (b.d_prim) b.d_prim[i] = h.hit ? h.prim : -1;
+    const Hit h = mesh_winner_hit<MODE == kRaysNormal>(inst, tab, best, wi, wk, b.d_prim);
+    store_closest<MODE>(b, i, pl, ray, h);
   }
 }
 
@@ -186,17 +129,9 @@ __global__ __launch_bounds__(64) void pose_kernel(rti::InstRec *inst, int32_t fi
 template <int SLOTS>
 void launch_t(const rti::InstArgs &a, const PlaneDev &pl, const rt_ray_batch &b, int mode, hipStream_t st) {
   const unsigned blocks = (unsigned)((b.n + kIBlock - 1) / kIBlock);
-  switch (mode) {
-    case kRaysAny:
-      trace_instances_kernel<SLOTS, kRaysAny><<<blocks, kIBlock, 0, st>>>(a.inst, a.blas, a.ninst, pl, b);
-      break;
-    case kRaysClosest:
-      trace_instances_kernel<SLOTS, kRaysClosest><<<blocks, kIBlock, 0, st>>>(a.inst, a.blas, a.ninst, pl, b);
-      break;
-    default:
-      trace_instances_kernel<SLOTS, kRaysNormal><<<blocks, kIBlock, 0, st>>>(a.inst, a.blas, a.ninst, pl, b);
-      break;
-  }
+  with_mode(mode, [&](auto m) {
+    trace_instances_kernel<SLOTS, decltype(m)::value><<<blocks, kIBlock, 0, st>>>(a.inst, a.blas, a.ninst, pl, b);
+  });
 }
 
 }  // namespace

@@ -2,13 +2,13 @@
 // all meshes (rt_scene_create_instanced_any, include/rtamd.h; DESIGN.md section
 // 4a, "Mixed bottom-level kinds"): the trace kernels over the flat list and the
 // top-level tree, the two adapters that give shade_one (rt_shade.h) such a
-// scene with the interface of MeshS and their shade kernels, the leaf-box
-// kernel that takes object boxes from the mixed table and the one-entry
-// rewrite of that table.
+// scene with the interface of MeshS and their shade kernels. (The tree's leaf
+// boxes are rt_tlas.hip's tlas_box_kernel over this table, a dynamic mesh's
+// entry blas_entry_launch on the record's mesh view.)
 //
 // A translation unit of its own, as rt_instances.hip, rt_tlas.hip and
-// rt_shade_instances.hip: nothing instantiated here moves a block of a kernel
-// that existed before. Mesh-only scenes never come here.
+// rt_shade_instances.hip, on the same shared pieces (rt_instance_dev.h,
+// rt_ray_io.h). Mesh-only scenes never come here.
 //
 // What is compile time and what is run time. The stack slots (with_slots over
 // the deepest mesh or octree BLAS; both traversals use frames of 3 words, so
@@ -35,12 +35,9 @@
 
 #include "rt_dispatch.h"
 #include "rt_error.h"
-#include "rt_instances.h"
-#include "rt_layout.h"
-#include "rt_math.h"
-#include "rt_scenes.h"
+#include "rt_instance_dev.h"
+#include "rt_ray_io.h"
 #include "rt_shade_rays.h"
-#include "rt_tlas.h"
 
 using namespace rtd;
 
@@ -52,70 +49,6 @@ static_assert(kMBlock == kSBlock, "the trace and the shade kernels share the per
 // traversal when at least this many lanes hold the wave's lowest candidate
 constexpr int kUniformMin = 16;
 constexpr uint32_t kNoKind = 0xFFFFFFFFu;
-
-// world -> object, with the operation order of include/rtamd.h (no fusing)
-__device__ __forceinline__ f3 xf_point(const float *m, f3 p) {
-  return f3{((m[0] * p.x + m[1] * p.y) + m[2] * p.z) + m[3], ((m[4] * p.x + m[5] * p.y) + m[6] * p.z) + m[7],
-            ((m[8] * p.x + m[9] * p.y) + m[10] * p.z) + m[11]};
-}
-__device__ __forceinline__ f3 xf_dir(const float *m, f3 d) {
-  return f3{(m[0] * d.x + m[1] * d.y) + m[2] * d.z, (m[4] * d.x + m[5] * d.y) + m[6] * d.z,
-            (m[8] * d.x + m[9] * d.y) + m[10] * d.z};
-}
-// the inverse transpose of the object-to-world map on an object-space normal: M^T n, normalised
-__device__ __forceinline__ f3 world_normal(const float *m, f3 n) {
-  return normalize(f3{(m[0] * n.x + m[4] * n.y) + m[8] * n.z, (m[1] * n.x + m[5] * n.y) + m[9] * n.z,
-                      (m[2] * n.x + m[6] * n.y) + m[10] * n.z});
-}
-
-// as rt_instances.hip: the mesh traversal's own root test, ahead of the traversal
-__device__ __forceinline__ bool root_passes(const MeshDev &md, f3 o, f3 d, float tn, float tf) {
-  if (md.root & rtl::kLeafBit) return true;
-  const f3 inv{1.0f / d.x, 1.0f / d.y, 1.0f / d.z};
-  return !root_box_miss(md.rbox, o, inv, tn, tf);
-}
-
-// a lane's own copy of a record's matrix and of a mesh view (vector loads)
-__device__ __forceinline__ void load_m(const rti::InstRec *r, float m[12]) {
-  const float4 *q = reinterpret_cast<const float4 *>(r->m);
-  const float4 a = q[0], b = q[1], c = q[2];
-  m[0] = a.x; m[1] = a.y; m[2] = a.z; m[3] = a.w;
-  m[4] = b.x; m[5] = b.y; m[6] = b.z; m[7] = b.w;
-  m[8] = c.x; m[9] = c.y; m[10] = c.z; m[11] = c.w;
-}
-__device__ __forceinline__ MeshDev load_md(const MeshDev *e) {
-  MeshDev md{e->nodes, e->tris, e->root, {}, e->coop, e->dmax2};
-#pragma unroll
-  for (int k = 0; k < 6; ++k) md.rbox[k] = e->rbox[k];
-  return md;
-}
-
-// the smallest value of the wave (all 64 lanes call it)
-__device__ __forceinline__ uint32_t wave_min(uint32_t v) {
-#pragma unroll
-  for (int s = 32; s >= 1; s >>= 1) {
-    const uint32_t w = (uint32_t)__shfl_xor((int)v, s, 64);
-    v = w < v ? w : v;
-  }
-  return v;
-}
-
-// a lane's walk to its next candidate: rtt::walk_next on 16-byte loads
-__device__ __forceinline__ uint32_t lane_next(const rtt::TNode *__restrict__ nodes, uint32_t P, uint32_t n, f3 o,
-                                              f3 inv, float tn, float tf) {
-  while (n != 0u) {
-    const float4 *q = reinterpret_cast<const float4 *>(nodes + n);
-    const float4 a = q[0], c = q[1];
-    const float bx[6] = {a.x, a.y, a.z, a.w, c.x, c.y};
-    if (rtt::box_pass_inv(bx, o.x, o.y, o.z, inv.x, inv.y, inv.z, tn, tf)) {
-      if (n >= P) return n;
-      n = 2u * n;
-    } else {
-      n = rtt::walk_skip(n);
-    }
-  }
-  return 0u;
-}
 
 // What a lane keeps of its best candidate so far: t, the instance, the
 // primitive (mesh: triangle slot; grid: cell; octree: node) and, for an SDF
@@ -242,7 +175,7 @@ __device__ __forceinline__ Hit winner_hit(const rti::InstRec *inst, const rti::B
     h.hit = true;
     h.t = w.best;
     if constexpr (NORMAL) h.n = world_normal(rp->m, n);
-    h.prim = (int64_t)(((uint64_t)(uint32_t)w.wi << 32) | (uint64_t)p);
+    h.prim = inst_prim(w.wi, p);
   }
   return h;
 }
@@ -310,47 +243,6 @@ __device__ __forceinline__ void round_lanes(const rti::InstRec *__restrict__ ins
       mk &= ~__ballot(me);
     }
   }
-}
-
-// ---- ray load / hit store of the two trace kernels ---------------------------
-struct RayIn {
-  f3 o, d;
-  float tn, tf;
-};
-__device__ __forceinline__ RayIn load_ray(const rt_ray_batch &b, int64_t i, bool active) {
-  RayIn r{f3{0.0f, 0.0f, 0.0f}, f3{0.0f, 0.0f, 1.0f}, b.tnear, b.tfar};
-  if (active) {
-    r.o = f3{b.d_origin[3 * i], b.d_origin[3 * i + 1], b.d_origin[3 * i + 2]};
-    r.d = f3{b.d_dir[3 * i], b.d_dir[3 * i + 1], b.d_dir[3 * i + 2]};
-    if (b.d_tnear) r.tn = b.d_tnear[i];
-    if (b.d_tfar) r.tf = b.d_tfar[i];
-  }
-  return r;
-}
-__device__ __forceinline__ void store_any(const rt_ray_batch &b, int64_t i, const PlaneDev &pl, const RayIn &r,
-                                          bool occ) {
-  if (!occ && pl.on) {  // HitInfo::hitten of the union: the OR of both
-    float tp, ap;
-    occ = plane_hit(pl, r.o, r.d, r.tn, r.tf, tp, ap);
-  }
-  b.d_hit[i] = occ ? 1 : 0;
-}
-template <int MODE>
-__device__ __forceinline__ void store_closest(const rt_ray_batch &b, int64_t i, const PlaneDev &pl, const RayIn &r,
-                                              Hit h) {
-  if (pl.on) {  // SceneUnion::intersect, as trace_rays_kernel
-    float tp = kInf, ap = 1.0f;
-    const bool ph = plane_hit(pl, r.o, r.d, r.tn, r.tf, tp, ap);
-    if (!(h.t < (ph ? tp : kInf))) h = ph ? Hit{true, tp, pl.n, -2} : miss_hit();
-  }
-  if (b.d_hit) b.d_hit[i] = h.hit ? 1 : 0;
-  if (b.d_t) b.d_t[i] = h.t;
-  if constexpr (MODE == kRaysNormal) {
-    b.d_normal[3 * i] = h.n.x;
-    b.d_normal[3 * i + 1] = h.n.y;
-    b.d_normal[3 * i + 2] = h.n.z;
-  }
-  if (b.d_prim) b.d_prim[i] = h.hit ? h.prim : -1;
 }
 
 // ---- the flat list -----------------------------------------------------------
@@ -643,95 +535,18 @@ void shade_mixed_tlas_kernel(const rti::InstRec *__restrict__ inst, const rti::B
   shade_rays_body<MixedTlasS, SLOTS>(sc, pl, P, b, d_color, flags, stk);
 }
 
-// ---- maintenance ---------------------------------------------------------------
-// tlas_box_kernel (rt_tlas.hip) with the object box taken from the mixed table:
-// a mesh's rbox (the unbounded box for a leaf root, the empty box for an empty
-// mesh), the cube (-1,-1,-1, 1,1,1) for a grid or an octree.
-__global__ __launch_bounds__(64) void mixed_box_kernel(rtt::TNode *nodes, uint32_t P, int32_t ninst,
-                                                       const rti::InstRec *__restrict__ inst, float *xform,
-                                                       const rti::BlasRec *__restrict__ tab, int32_t first,
-                                                       int32_t count, const float *__restrict__ xsrc,
-                                                       int32_t only_blas) {
-  const int32_t j = (int32_t)(blockIdx.x * 64u + threadIdx.x);
-  if (j >= count) return;
-  const int32_t i = first + j;
-  if ((uint32_t)i >= P) return;
-  float wb[6];
-  rtt::empty_box(wb);
-  if (i < ninst) {
-    float x[12];
-    const float *src = xsrc ? xsrc + 12 * (int64_t)j : xform + 12 * (int64_t)i;
-#pragma unroll
-    for (int k = 0; k < 12; ++k) x[k] = src[k];
-    if (xsrc) {
-#pragma unroll
-      for (int k = 0; k < 12; ++k) xform[12 * (int64_t)i + k] = x[k];
-    }
-    const rti::InstRec *r = inst + i;
-    if (only_blas >= 0 && r->blas != only_blas) return;
-    if (!((r->flags & RT_INSTANCE_DISABLED) || r->skipped)) {
-      const rti::BlasRec *e = tab + r->blas;
-      if (e->kind == (uint32_t)RT_SCENE_MESH) {
-        const uint32_t root = e->mesh.root;
-        if (root != rtl::kInvalidChild) {
-          if (root & rtl::kLeafBit) {
-            rtt::unbounded_box(wb);
-          } else {
-            float ob[6];
-#pragma unroll
-            for (int k = 0; k < 6; ++k) ob[k] = e->mesh.rbox[k];
-            rtt::world_box(x, ob, wb);
-          }
-        }
-      } else {
-        const float ob[6] = {-1.0f, -1.0f, -1.0f, 1.0f, 1.0f, 1.0f};
-        rtt::world_box(x, ob, wb);
-      }
-    }
-  }
-  float4 *q = reinterpret_cast<float4 *>(nodes + P + (uint32_t)i);
-  q[0] = make_float4(wb[0], wb[1], wb[2], wb[3]);
-  q[1] = make_float4(wb[4], wb[5], 0.0f, 0.0f);
-}
-
-// The mesh view of one table record, taken by value and written word by word
-// by one lane (blas_entry_kernel, rt_instances.hip); kind and variant stay.
-__global__ void mixed_entry_kernel(rti::BlasRec *entry, MeshDev md) {
-  if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  entry->mesh.nodes = md.nodes;
-  entry->mesh.tris = md.tris;
-  entry->mesh.root = md.root;
-  for (int k = 0; k < 6; ++k) entry->mesh.rbox[k] = md.rbox[k];
-  entry->mesh.coop = md.coop;
-  entry->mesh.dmax2 = md.dmax2;
-}
-
 template <int SLOTS>
 void launch_trace_t(const rti::MixedArgs &m, const PlaneDev &pl, const rt_ray_batch &b, int mode, hipStream_t st) {
   const unsigned blocks = (unsigned)((b.n + kMBlock - 1) / kMBlock);
   const rti::InstArgs &a = m.a;
   const uint32_t P = (uint32_t)a.tlas_leaves;
-  if (a.tlas) {
-    switch (mode) {
-      case kRaysAny:
-        trace_mixed_tlas_kernel<SLOTS, kRaysAny><<<blocks, kMBlock, 0, st>>>(a.inst, m.tab, a.tlas, P, pl, b);
-        break;
-      case kRaysClosest:
-        trace_mixed_tlas_kernel<SLOTS, kRaysClosest><<<blocks, kMBlock, 0, st>>>(a.inst, m.tab, a.tlas, P, pl, b);
-        break;
-      default:
-        trace_mixed_tlas_kernel<SLOTS, kRaysNormal><<<blocks, kMBlock, 0, st>>>(a.inst, m.tab, a.tlas, P, pl, b);
-        break;
-    }
-    return;
-  }
-  switch (mode) {
-    case kRaysAny: trace_mixed_kernel<SLOTS, kRaysAny><<<blocks, kMBlock, 0, st>>>(a.inst, m.tab, a.ninst, pl, b); break;
-    case kRaysClosest:
-      trace_mixed_kernel<SLOTS, kRaysClosest><<<blocks, kMBlock, 0, st>>>(a.inst, m.tab, a.ninst, pl, b);
-      break;
-    default: trace_mixed_kernel<SLOTS, kRaysNormal><<<blocks, kMBlock, 0, st>>>(a.inst, m.tab, a.ninst, pl, b); break;
-  }
+  with_mode(mode, [&](auto md) {
+    constexpr int M = decltype(md)::value;
+    if (a.tlas)
+      trace_mixed_tlas_kernel<SLOTS, M><<<blocks, kMBlock, 0, st>>>(a.inst, m.tab, a.tlas, P, pl, b);
+    else
+      trace_mixed_kernel<SLOTS, M><<<blocks, kMBlock, 0, st>>>(a.inst, m.tab, a.ninst, pl, b);
+  });
 }
 
 }  // namespace
@@ -756,21 +571,6 @@ int shade_mixed_launch(const MixedArgs &m, const PlaneDev &pl, const rt_render_p
     else
       shade_mixed_kernel<N><<<blocks, kSBlock, 0, st>>>(a.inst, m.tab, a.ninst, pl, p, b, d_color, flags);
   });
-  HIP_TRY(hipGetLastError());
-  return RT_OK;
-}
-
-int mixed_entry_launch(BlasRec *entry, const MeshDev &md, hipStream_t st) {
-  mixed_entry_kernel<<<1, 64, 0, st>>>(entry, md);
-  HIP_TRY(hipGetLastError());
-  return RT_OK;
-}
-
-int mixed_boxes_launch(const TlasArgs &t, const BlasRec *tab, int32_t first, int32_t count, const float *d_xsrc,
-                       int32_t only_blas, hipStream_t st) {
-  if (count <= 0) return RT_OK;
-  mixed_box_kernel<<<(unsigned)((count + 63) / 64), 64, 0, st>>>(t.nodes, (uint32_t)t.leaves, t.ninst, t.inst, t.xform,
-                                                               tab, first, count, d_xsrc, only_blas);
   HIP_TRY(hipGetLastError());
   return RT_OK;
 }

@@ -103,9 +103,9 @@ int instanced_sync(rt_scene *s, hipStream_t stream) {
   for (size_t j = 0; j < s->blas.size(); ++j) {
     // (only a dynamic mesh's version ever moves: SDF scenes are immutable)
     if (s->blas[j]->version == s->blas_seen[j]) continue;
-    if (int rc = s->d_mixed ? rti::mixed_entry_launch(s->d_mixed + j, mesh_dev(s->blas[j]), stream)
-                            : rti::blas_entry_launch(s->d_blas + j, mesh_dev(s->blas[j]), stream))
-      return rc;
+    // (a mixed table: the mesh view of the record; kind and variant stay)
+    rtd::MeshDev *entry = s->d_mixed ? &(s->d_mixed + j)->mesh : s->d_blas + j;
+    if (int rc = rti::blas_entry_launch(entry, mesh_dev(s->blas[j]), stream)) return rc;
     s->blas_seen[j] = s->blas[j]->version;
     if (!s->d_tlas) continue;
     // its root box moved: that BLAS's leaves of the top-level tree and the

@@ -262,9 +262,9 @@ __device__ __forceinline__ f4 shade_one(const S &sc, const PlaneDev &pl, const r
 // The kernels over an rt_ray_batch (trace_rays_kernel, trace_instances_kernel)
 // trace one ray per lane, the work chosen at compile time. kRaysAny: any hit,
 // one word per ray; kRaysClosest: closest hit, no normal is computed;
-// kRaysNormal: closest hit with the normal. Each kernel keeps its own ray load
-// and hit store: behind shared functions both compiled to other code
-// (profiles/r17/README.md).
+// kRaysNormal: closest hit with the normal. The ray load and the store tails
+// are rt_ray_io.h's; trace_rays_kernel keeps its own ray load (behind the
+// shared one its any-hit kernels compiled to other loops, profiles/r24/README.md).
 enum { kRaysAny = 0, kRaysClosest = 1, kRaysNormal = 2 };
 
 }  // namespace

@@ -7,8 +7,8 @@
 // RT_INSTANCED_TLAS, applied to every ray shade_one traces); DESIGN.md
 // section 4b.
 //
-// A translation unit of its own, as rt_instances.hip and rt_tlas.hip: nothing
-// instantiated here moves a block of a kernel that existed before.
+// A translation unit of its own, as rt_instances.hip and rt_tlas.hip; the
+// per-lane helpers and the winner's Hit are rt_instance_dev.h's.
 //
 // shade_one calls intersect and occluded inside lane-divergent branches (the
 // shadow ray exists on lanes that hit, the reflection ray on lanes that hit
@@ -26,67 +26,12 @@
 
 #include "rt_dispatch.h"
 #include "rt_error.h"
-#include "rt_instances.h"
-#include "rt_layout.h"
-#include "rt_math.h"
-#include "rt_scenes.h"
+#include "rt_instance_dev.h"
 #include "rt_shade_rays.h"
-#include "rt_tlas.h"
 
 using namespace rtd;
 
 namespace {
-
-// world -> object, with the operation order of include/rtamd.h (no fusing)
-__device__ __forceinline__ f3 xf_point(const float *m, f3 p) {
-  return f3{((m[0] * p.x + m[1] * p.y) + m[2] * p.z) + m[3], ((m[4] * p.x + m[5] * p.y) + m[6] * p.z) + m[7],
-            ((m[8] * p.x + m[9] * p.y) + m[10] * p.z) + m[11]};
-}
-__device__ __forceinline__ f3 xf_dir(const float *m, f3 d) {
-  return f3{(m[0] * d.x + m[1] * d.y) + m[2] * d.z, (m[4] * d.x + m[5] * d.y) + m[6] * d.z,
-            (m[8] * d.x + m[9] * d.y) + m[10] * d.z};
-}
-
-// as rt_instances.hip: the traversal's own root test, ahead of the traversal
-__device__ __forceinline__ bool root_passes(const MeshDev &md, f3 o, f3 d, float tn, float tf) {
-  if (md.root & rtl::kLeafBit) return true;
-  const f3 inv{1.0f / d.x, 1.0f / d.y, 1.0f / d.z};
-  return !root_box_miss(md.rbox, o, inv, tn, tf);
-}
-
-// a lane's own copy of a record's matrix and of a table entry (vector loads)
-__device__ __forceinline__ void load_m(const rti::InstRec *r, float m[12]) {
-  const float4 *q = reinterpret_cast<const float4 *>(r->m);
-  const float4 a = q[0], b = q[1], c = q[2];
-  m[0] = a.x; m[1] = a.y; m[2] = a.z; m[3] = a.w;
-  m[4] = b.x; m[5] = b.y; m[6] = b.z; m[7] = b.w;
-  m[8] = c.x; m[9] = c.y; m[10] = c.z; m[11] = c.w;
-}
-__device__ __forceinline__ MeshDev load_md(const MeshDev *e) {
-  MeshDev md{e->nodes, e->tris, e->root, {}, e->coop, e->dmax2};
-#pragma unroll
-  for (int k = 0; k < 6; ++k) md.rbox[k] = e->rbox[k];
-  return md;
-}
-
-// The winner's Hit, per lane (lanes differ in wi): the object-space normal
-// under the inverse transpose of the object-to-world map, M^T n, normalised;
-// prim = (instance << 32) | original triangle index.
-__device__ __forceinline__ Hit winner_hit(const rti::InstRec *inst, const MeshDev *tab, int32_t wi, uint32_t wk,
-                                          float best) {
-  Hit h = miss_hit();
-  if (wi >= 0) {
-    const float *m = inst[wi].m;
-    const rtl::GTri *tris = tab[inst[wi].blas].tris;
-    const f3 n = tri_normal(tris, wk);  // object space
-    h.hit = true;
-    h.t = best;
-    h.n = normalize(f3{(m[0] * n.x + m[4] * n.y) + m[8] * n.z, (m[1] * n.x + m[5] * n.y) + m[9] * n.z,
-                       (m[2] * n.x + m[6] * n.y) + m[10] * n.z});
-    h.prim = (int64_t)(((uint64_t)(uint32_t)wi << 32) | (uint64_t)tris[wk].orig_id);
-  }
-  return h;
-}
 
 // The flat list: the header's loop, the body of trace_instances_kernel's with
 // the per-lane traversal. `go`-less lanes of the call wait in the loop, so k
@@ -118,7 +63,7 @@ struct InstFlatS {
         wk = tri;
       }
     }
-    return winner_hit(inst, tab, wi, wk, best);
+    return mesh_winner_hit<true>(inst, tab, best, wi, wk, true);
   }
   // OR over the instances of the bottom-level any hit under the full tFar (the
   // closest-hit flag, include/rtamd.h); a lane that has its hit waits, the
@@ -150,21 +95,6 @@ struct InstTlasS {
   const MeshDev *__restrict__ tab;
   const rtt::TNode *__restrict__ nodes;
   uint32_t P;
-  // a lane's walk to its next candidate: rtt::walk_next on 16-byte loads
-  __device__ __forceinline__ uint32_t next(uint32_t n, f3 o, f3 inv, float tn, float tf) const {
-    while (n != 0u) {
-      const float4 *q = reinterpret_cast<const float4 *>(nodes + n);
-      const float4 a = q[0], c = q[1];
-      const float bx[6] = {a.x, a.y, a.z, a.w, c.x, c.y};
-      if (rtt::box_pass_inv(bx, o.x, o.y, o.z, inv.x, inv.y, inv.z, tn, tf)) {
-        if (n >= P) return n;
-        n = 2u * n;
-      } else {
-        n = rtt::walk_skip(n);
-      }
-    }
-    return 0u;
-  }
   template <int B, class CT>
   __device__ __forceinline__ Hit intersect(f3 o, f3 d, float tn, float tf, LdsStack<B, kFields> st, CT &cnt) const {
     const f3 inv{1.0f / d.x, 1.0f / d.y, 1.0f / d.z};  // of the WORLD ray: the tree's test
@@ -174,7 +104,7 @@ struct InstTlasS {
     uint32_t n = 1u;
     for (;;) {
       const float tfi = best < tf ? best : tf;
-      n = next(n, o, inv, tn, tfi);
+      n = lane_next(nodes, P, n, o, inv, tn, tfi);
       if (n == 0u) break;
       const uint32_t cand = n - P;
       const rti::InstRec *rp = inst + cand;
@@ -194,7 +124,7 @@ struct InstTlasS {
       }
       n = rtt::walk_skip(n);
     }
-    return winner_hit(inst, tab, wi, wk, best);
+    return mesh_winner_hit<true>(inst, tab, best, wi, wk, true);
   }
   // the candidates under the full tFar; a lane stops at its first hit
   template <int B, class CT>
@@ -202,7 +132,7 @@ struct InstTlasS {
     const f3 inv{1.0f / d.x, 1.0f / d.y, 1.0f / d.z};
     uint32_t n = 1u;
     for (;;) {
-      n = next(n, o, inv, tn, tf);
+      n = lane_next(nodes, P, n, o, inv, tn, tf);
       if (n == 0u) return false;
       const rti::InstRec *rp = inst + (n - P);
       const uint32_t off = (rp->flags & RT_INSTANCE_DISABLED) | rp->skipped;

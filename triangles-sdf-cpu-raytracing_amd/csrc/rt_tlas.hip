@@ -5,8 +5,8 @@
 // (rt_instance_world_box, rtx_tlas_candidates). The definition itself is
 // rt_tlas.h.
 //
-// A translation unit of its own, as rt_instances.hip: nothing instantiated
-// here moves a block of a kernel that existed before.
+// A translation unit of its own, as rt_instances.hip, whose shared pieces
+// (rt_instance_dev.h, rt_ray_io.h, rt_dispatch.h) it uses as well.
 //
 // Each lane owns a cursor into the heap-ordered tree and walks it without a
 // stack (rtt::walk_next / walk_skip), so the only LDS is the mesh stacks. A
@@ -24,11 +24,8 @@
 
 #include "rt_dispatch.h"
 #include "rt_error.h"
-#include "rt_instances.h"
-#include "rt_layout.h"
-#include "rt_math.h"
-#include "rt_scenes.h"
-#include "rt_tlas.h"
+#include "rt_instance_dev.h"
+#include "rt_ray_io.h"
 
 using namespace rtd;
 
@@ -44,65 +41,6 @@ std::atomic<int> g_umin{kUniformMinDefault};
 // diagnostic: BLAS traversals per ray of the next traces (rtx_set_tlas_count)
 std::atomic<uint32_t *> g_count{nullptr};
 
-// world -> object, with the operation order of include/rtamd.h (no fusing)
-__device__ __forceinline__ f3 xf_point(const float *m, f3 p) {
-  return f3{((m[0] * p.x + m[1] * p.y) + m[2] * p.z) + m[3], ((m[4] * p.x + m[5] * p.y) + m[6] * p.z) + m[7],
-            ((m[8] * p.x + m[9] * p.y) + m[10] * p.z) + m[11]};
-}
-__device__ __forceinline__ f3 xf_dir(const float *m, f3 d) {
-  return f3{(m[0] * d.x + m[1] * d.y) + m[2] * d.z, (m[4] * d.x + m[5] * d.y) + m[6] * d.z,
-            (m[8] * d.x + m[9] * d.y) + m[10] * d.z};
-}
-
-// as rt_instances.hip: the traversal's own root test, ahead of the traversal
-__device__ __forceinline__ bool root_passes(const MeshDev &md, f3 o, f3 d, float tn, float tf) {
-  if (md.root & rtl::kLeafBit) return true;
-  const f3 inv{1.0f / d.x, 1.0f / d.y, 1.0f / d.z};
-  return !root_box_miss(md.rbox, o, inv, tn, tf);
-}
-
-// a lane's own copy of a record's matrix and of a table entry (vector loads)
-__device__ __forceinline__ void load_m(const rti::InstRec *r, float m[12]) {
-  const float4 *q = reinterpret_cast<const float4 *>(r->m);
-  const float4 a = q[0], b = q[1], c = q[2];
-  m[0] = a.x; m[1] = a.y; m[2] = a.z; m[3] = a.w;
-  m[4] = b.x; m[5] = b.y; m[6] = b.z; m[7] = b.w;
-  m[8] = c.x; m[9] = c.y; m[10] = c.z; m[11] = c.w;
-}
-__device__ __forceinline__ MeshDev load_md(const MeshDev *e) {
-  MeshDev md{e->nodes, e->tris, e->root, {}, e->coop, e->dmax2};
-#pragma unroll
-  for (int k = 0; k < 6; ++k) md.rbox[k] = e->rbox[k];
-  return md;
-}
-
-// the smallest value of the wave (all 64 lanes call it)
-__device__ __forceinline__ uint32_t wave_min(uint32_t v) {
-#pragma unroll
-  for (int s = 32; s >= 1; s >>= 1) {
-    const uint32_t w = (uint32_t)__shfl_xor((int)v, s, 64);
-    v = w < v ? w : v;
-  }
-  return v;
-}
-
-// a lane's walk to its next candidate: rtt::walk_next on 16-byte loads
-__device__ __forceinline__ uint32_t lane_next(const rtt::TNode *__restrict__ nodes, uint32_t P, uint32_t n, f3 o,
-                                              f3 inv, float tn, float tf) {
-  while (n != 0u) {
-    const float4 *q = reinterpret_cast<const float4 *>(nodes + n);
-    const float4 a = q[0], c = q[1];
-    const float bx[6] = {a.x, a.y, a.z, a.w, c.x, c.y};
-    if (rtt::box_pass_inv(bx, o.x, o.y, o.z, inv.x, inv.y, inv.z, tn, tf)) {
-      if (n >= P) return n;
-      n = 2u * n;
-    } else {
-      n = rtt::walk_skip(n);
-    }
-  }
-  return 0u;
-}
-
 template <int SLOTS, int MODE>
 __global__ __launch_bounds__(kTBlock) void trace_tlas_kernel(const rti::InstRec *__restrict__ inst,
                                                              const MeshDev *__restrict__ tab,
@@ -115,14 +53,9 @@ __global__ __launch_bounds__(kTBlock) void trace_tlas_kernel(const rti::InstRec 
   // need the whole wave): their cursor starts at 0 and they touch no memory
   const bool active = i < b.n;
   LdsStack<kTBlock, MeshS::kFields> st{stk + threadIdx.x};
-  f3 o{0.0f, 0.0f, 0.0f}, d{0.0f, 0.0f, 1.0f};
-  float tn = b.tnear, tf = b.tfar;
-  if (active) {
-    o = f3{b.d_origin[3 * i], b.d_origin[3 * i + 1], b.d_origin[3 * i + 2]};
-    d = f3{b.d_dir[3 * i], b.d_dir[3 * i + 1], b.d_dir[3 * i + 2]};
-    if (b.d_tnear) tn = b.d_tnear[i];
-    if (b.d_tfar) tf = b.d_tfar[i];
-  }
+  const RayIn ray = load_ray(b, i, active);
+  const f3 o = ray.o, d = ray.d;
+  const float tn = ray.tn, tf = ray.tf;
   const f3 inv{1.0f / d.x, 1.0f / d.y, 1.0f / d.z};  // of the WORLD ray: the tree's test
   NoCnt cnt;
   constexpr bool kAny = MODE == kRaysAny;
@@ -208,54 +141,43 @@ __global__ __launch_bounds__(kTBlock) void trace_tlas_kernel(const rti::InstRec 
   }
   if (!active) return;
   if (count) count[i] = ntrav;
-  if constexpr (kAny) {
-    if (!occ && pl.on) {  // HitInfo::hitten of the union: the OR of both
-      float tp, ap;
-      occ = plane_hit(pl, o, d, tn, tf, tp, ap);
-    }
-    b.d_hit[i] = occ ? 1 : 0;
-  } else {
-    Hit h = miss_hit();
-    if (wi >= 0) {
-      // the winner's record and triangle, per lane (lanes differ in wi)
-      const float *m = inst[wi].m;
-      const rtl::GTri *tris = tab[inst[wi].blas].tris;
-      h.hit = true;
-      h.t = best;
-      if constexpr (MODE == kRaysNormal) {
-        const f3 nn = tri_normal(tris, wk);  // object space
-        // the inverse transpose of the object-to-world map: M^T n
-        h.n = normalize(f3{(m[0] * nn.x + m[4] * nn.y) + m[8] * nn.z, (m[1] * nn.x + m[5] * nn.y) + m[9] * nn.z,
-                           (m[2] * nn.x + m[6] * nn.y) + m[10] * nn.z});
-      }
-      if (b.d_prim) h.prim = (int64_t)(((uint64_t)(uint32_t)wi << 32) | (uint64_t)tris[wk].orig_id);
-    }
-    if (pl.on) {  // SceneUnion::intersect, as trace_rays_kernel
-      float tp = kInf, ap = 1.0f;
-      const bool ph = plane_hit(pl, o, d, tn, tf, tp, ap);
-      if (!(h.t < (ph ? tp : kInf))) h = ph ? Hit{true, tp, pl.n, -2} : miss_hit();
-    }
-    if (b.d_hit) b.d_hit[i] = h.hit ? 1 : 0;
-    if (b.d_t) b.d_t[i] = h.t;
-    if constexpr (MODE == kRaysNormal) {
-      b.d_normal[3 * i] = h.n.x;
-      b.d_normal[3 * i + 1] = h.n.y;
-      b.d_normal[3 * i + 2] = h.n.z;
-    }
-    if (b.d_prim) b.d_prim[i] = h.hit ? h.prim : -1;
-  }
+  if constexpr (kAny)
+    store_any(b, i, pl, ray, occ);
+  else
+    store_closest<MODE>(b, i, pl, ray, mesh_winner_hit<MODE == kRaysNormal>(inst, tab, best, wi, wk, b.d_prim));
 }
 
-// Leaves first .. first + count - 1 (< P), one per lane. A leaf of an instance
-// (index < ninst): with xsrc, its object-to-world matrix is first taken over
-// from xsrc[12 j ..] into the scene's own array; then the box is world_box of
-// the matrix and the BLAS's root box as the table holds it, the unbounded box
-// for a leaf-root BLAS, the empty box for a disabled or skipped instance or an
-// empty BLAS. only_blas >= 0: the instances of other BLAS are left alone. A
-// leaf past the instances is the empty box.
+// The object box of one table entry: what kind it is and, for kBoxObject, the
+// box itself. A mesh: its root box as the table holds it, unbounded for a
+// leaf root (no root box to test), empty for an empty mesh. A grid or an
+// octree of the mixed table: the cube (-1,-1,-1, 1,1,1).
+enum { kBoxEmpty = 0, kBoxUnbounded = 1, kBoxObject = 2 };
+__device__ __forceinline__ int object_box(const MeshDev *e, float ob[6]) {
+  const uint32_t root = e->root;
+  if (root == rtl::kInvalidChild) return kBoxEmpty;
+  if (root & rtl::kLeafBit) return kBoxUnbounded;
+#pragma unroll
+  for (int k = 0; k < 6; ++k) ob[k] = e->rbox[k];
+  return kBoxObject;
+}
+__device__ __forceinline__ int object_box(const rti::BlasRec *e, float ob[6]) {
+  ob[0] = ob[1] = ob[2] = -1.0f;
+  ob[3] = ob[4] = ob[5] = 1.0f;
+  return e->kind == (uint32_t)RT_SCENE_MESH ? object_box(&e->mesh, ob) : kBoxObject;
+}
+
+// Leaves first .. first + count - 1 (< P), one per lane, over a table of
+// MeshDev or of BlasRec. A leaf of an instance (index < ninst): with xsrc, its
+// object-to-world matrix is first taken over from xsrc[12 j ..] into the
+// scene's own array; then the box is world_box of the matrix and object_box
+// of the instance's table entry (the unbounded box for an unbounded one), the
+// empty box for a disabled or skipped instance or an empty entry.
+// only_blas >= 0: the instances of other BLAS are left alone. A leaf past the
+// instances is the empty box.
+template <class Rec>
 __global__ __launch_bounds__(64) void tlas_box_kernel(rtt::TNode *nodes, uint32_t P, int32_t ninst,
                                                       const rti::InstRec *__restrict__ inst, float *xform,
-                                                      const MeshDev *__restrict__ tab, int32_t first, int32_t count,
+                                                      const Rec *__restrict__ tab, int32_t first, int32_t count,
                                                       const float *__restrict__ xsrc, int32_t only_blas) {
   const int32_t j = (int32_t)(blockIdx.x * 64u + threadIdx.x);
   if (j >= count) return;
@@ -275,18 +197,12 @@ __global__ __launch_bounds__(64) void tlas_box_kernel(rtt::TNode *nodes, uint32_
     const rti::InstRec *r = inst + i;
     if (only_blas >= 0 && r->blas != only_blas) return;
     if (!((r->flags & RT_INSTANCE_DISABLED) || r->skipped)) {
-      const MeshDev *e = tab + r->blas;
-      const uint32_t root = e->root;
-      if (root != rtl::kInvalidChild) {
-        if (root & rtl::kLeafBit) {
-          rtt::unbounded_box(wb);
-        } else {
-          float ob[6];
-#pragma unroll
-          for (int k = 0; k < 6; ++k) ob[k] = e->rbox[k];
-          rtt::world_box(x, ob, wb);
-        }
-      }
+      float ob[6];
+      const int kind = object_box(tab + r->blas, ob);
+      if (kind == kBoxUnbounded)
+        rtt::unbounded_box(wb);
+      else if (kind == kBoxObject)
+        rtt::world_box(x, ob, wb);
     }
   }
   float4 *q = reinterpret_cast<float4 *>(nodes + P + (uint32_t)i);
@@ -330,17 +246,19 @@ void launch_t(const rti::InstArgs &a, const PlaneDev &pl, const rt_ray_batch &b,
   const int32_t umin = g_umin.load();
   uint32_t *count = g_count.load();
   const uint32_t P = (uint32_t)a.tlas_leaves;
-  switch (mode) {
-    case kRaysAny:
-      trace_tlas_kernel<SLOTS, kRaysAny><<<blocks, kTBlock, 0, st>>>(a.inst, a.blas, a.tlas, P, umin, count, pl, b);
-      break;
-    case kRaysClosest:
-      trace_tlas_kernel<SLOTS, kRaysClosest><<<blocks, kTBlock, 0, st>>>(a.inst, a.blas, a.tlas, P, umin, count, pl, b);
-      break;
-    default:
-      trace_tlas_kernel<SLOTS, kRaysNormal><<<blocks, kTBlock, 0, st>>>(a.inst, a.blas, a.tlas, P, umin, count, pl, b);
-      break;
-  }
+  with_mode(mode, [&](auto m) {
+    trace_tlas_kernel<SLOTS, decltype(m)::value><<<blocks, kTBlock, 0, st>>>(a.inst, a.blas, a.tlas, P, umin, count, pl, b);
+  });
+}
+
+template <class Rec>
+int boxes_launch(const rti::TlasArgs &t, const Rec *tab, int32_t first, int32_t count, const float *d_xsrc,
+                 int32_t only_blas, hipStream_t st) {
+  if (count <= 0) return RT_OK;
+  tlas_box_kernel<Rec><<<(unsigned)((count + 63) / 64), 64, 0, st>>>(t.nodes, (uint32_t)t.leaves, t.ninst, t.inst,
+                                                                   t.xform, tab, first, count, d_xsrc, only_blas);
+  HIP_TRY(hipGetLastError());
+  return RT_OK;
 }
 
 }  // namespace
@@ -355,11 +273,12 @@ int trace_tlas_launch(const InstArgs &a, const PlaneDev &pl, const rt_ray_batch 
 
 int tlas_boxes_launch(const TlasArgs &t, int32_t first, int32_t count, const float *d_xsrc, int32_t only_blas,
                       hipStream_t st) {
-  if (count <= 0) return RT_OK;
-  tlas_box_kernel<<<(unsigned)((count + 63) / 64), 64, 0, st>>>(t.nodes, (uint32_t)t.leaves, t.ninst, t.inst, t.xform,
-                                                              t.blas, first, count, d_xsrc, only_blas);
-  HIP_TRY(hipGetLastError());
-  return RT_OK;
+  return boxes_launch(t, t.blas, first, count, d_xsrc, only_blas, st);
+}
+
+int mixed_boxes_launch(const TlasArgs &t, const BlasRec *tab, int32_t first, int32_t count, const float *d_xsrc,
+                       int32_t only_blas, hipStream_t st) {
+  return boxes_launch(t, tab, first, count, d_xsrc, only_blas, st);
 }
 
 int tlas_refit_launch(const TlasArgs &t, hipStream_t st) {
