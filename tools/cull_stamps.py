@@ -18,6 +18,10 @@ beforehand, so a culled tile and a missed pixel store nothing: the all-culled
 launch is then the pure claim cost of its items, and the difference to
 --flags clear (the default) is what the background's stores cost
 (profiles/r09/README.md).
+
+The launches run on the whole frame's item grid (rtx_set_queue_grid(0)): the
+tool measures what the items outside the rectangle cost, and with the item
+rectangle on the all-culled launch has no items at all.
 """
 import ctypes as C
 import os
@@ -70,6 +74,8 @@ def main():
         return
     import torch
     L.rtx_set_persist_stamps.argtypes = [C.c_void_p, C.c_int64]
+    if hasattr(L, "rtx_set_queue_grid"):  # (a library from before the item rectangle has no such switch)
+        rtamd._lib.check(L.rtx_set_queue_grid(0))
     L.rt_set_device(0)
     sc = rtamd.BVHBuilder(mesh)
     sc.set_plane(None)

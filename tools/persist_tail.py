@@ -10,6 +10,10 @@ The stamps exist only in a diagnostic build of the library:
   bash tools/build_variant.sh stamps -DRT_PERSIST_STAMPS
   RTAMD_LIB=triangles-sdf-cpu-raytracing_amd/lib/var_stamps.so python tools/persist_tail.py bunny
 usage: python tools/persist_tail.py [workload ...]   (keys of bench.WORKLOADS)
+
+The launches run on the whole frame's item grid (rtx_set_queue_grid(0)): a
+stamped item index is mapped back to its frame and pixel by where(), which
+knows nothing of a launch's item rectangle.
 """
 import ctypes as C
 import os
@@ -28,6 +32,8 @@ from rtamd import workloads as WL  # noqa: E402
 
 L = rtamd.lib()
 L.rtx_set_persist_stamps.argtypes = [C.c_void_p, C.c_int64]
+if hasattr(L, "rtx_set_queue_grid"):  # (a library from before the item rectangle has no such switch)
+    rtamd._lib.check(L.rtx_set_queue_grid(0))
 CAP = 1 << 16
 
 

@@ -557,7 +557,15 @@ struct PersistQ {
   // start, end (s_memrealtime, 100 MHz), items traced | XCD << 32, end of its
   // last item, start of its last item, last item, longest item's duration, longest item
   unsigned long long *stamps;
+  // first item column / row: a launch of mesh primary frames queues items over
+  // its item rectangle only (rtq::grid, make_queue; tiles_x and per_frame are
+  // the rectangle's). 0, 0 with the whole frame's grid. Only the kernels that
+  // read a frame's cull rectangle (kQueueOrigin) add it; the words come last,
+  // so the other kernels' argument offsets and code are what they were
+  uint32_t ox, oy;
 };
+template <class S, bool GENERAL>
+constexpr bool kQueueOrigin = S::kCoop && !GENERAL;
 // 4 KiB + 256 B apart: every head on its own memory channel's lines, so the
 // memory-side atomics of different heads do not queue behind each other
 // (RTAMD_QSTRIDE=<words> overrides it for A/B runs, at most kHeadStrideMax)
@@ -651,7 +659,11 @@ void render_persist_kernel(S sc_arg, PlaneDev pl, FrameBatch fb, PersistQ q) {
       k = knext;
       continue;
     }
-    const uint32_t ty = r / q.tiles_x, tx = r - ty * q.tiles_x;
+    uint32_t ty = r / q.tiles_x, tx = r - ty * q.tiles_x;
+    if constexpr (kQueueOrigin<S, GENERAL>) {  // (after tx: ty is still the rectangle's row there)
+      tx += q.ox;
+      ty += q.oy;
+    }
 #ifdef RT_PERSIST_STAMPS
     const unsigned long long t_begin = __builtin_amdgcn_s_memrealtime();
 #endif
@@ -938,6 +950,38 @@ __global__ void clear_kernel(uint32_t *c, float *t, int64_t n) {
       c[j] = 0u;
       t[j] = kInf;
     }
+  }
+}
+
+// The cleared background of a multi-frame launch outside its item rectangle
+// (rtq::grid): the persistent launch that follows on the stream queues items
+// over the rectangle only, and with RT_FLAG_CLEAR (without HITS_ONLY) the
+// pixels outside it are a miss's words, colour 0 and t = +inf, written here.
+// One wave per workgroup (it takes single wave slots beside the other stream's
+// resident waves) writes 64 consecutive pixels of 8 rows: block x = 64-pixel
+// column segment, y = 8-row band, z = frame. The rectangle [x0, x1) x [y0, y1)
+// is in pixels, its edges multiples of 8: a lane inside it, or past W x H,
+// stores nothing. fb_store's agent-scope stores: the lines do not stay in L2.
+struct ClearOutside {
+  uint32_t *color[kMaxBatch];
+  float *t[kMaxBatch];
+  uint32_t W, H;
+  uint32_t x0, x1, y0, y1;
+};
+__global__ __launch_bounds__(64) void clear_outside_kernel(ClearOutside a) {
+  const uint32_t x = blockIdx.x * 64u + threadIdx.x, yb = blockIdx.y * 8u;
+  if (x >= a.W) return;
+  const bool in_x = x >= a.x0 && x < a.x1;
+  if (in_x && yb >= a.y0 && yb + 8u <= a.y1) return;  // (the rectangle's rows start and end on bands)
+  uint32_t *c = a.color[blockIdx.z];
+  float *t = a.t[blockIdx.z];
+#pragma unroll
+  for (uint32_t j = 0; j < 8u; ++j) {
+    const uint32_t y = yb + j;
+    if (y >= a.H || (in_x && y >= a.y0 && y < a.y1)) continue;
+    const uint32_t idx = y * a.W + x;  // (check_params caps W * H at 2^31)
+    fb_store(c + idx, 0u, false);
+    fb_store(t + idx, kInf, false);
   }
 }
 
@@ -1297,11 +1341,40 @@ int queue_heads_env() {
 }
 std::atomic<int> g_queue_heads{queue_heads_env()};
 
+// Item rectangle (rtq::grid) on / off: RTAMD_QGRID=0 keeps every launch on the
+// whole frame's item grid (A/B switch); rtx_set_queue_grid switches inside one
+// process.
+bool queue_grid_env() {
+  static const bool on = !ab_off("RTAMD_QGRID");
+  return on;
+}
+std::atomic<bool> g_queue_grid{queue_grid_env()};
+static_assert(rtq::kWhole == kCullWhole, "rtq::grid's whole-frame word is FrameArgs'");
+namespace grid_check {  // tile columns 3..6 and row 1 of a 250 x 131 frame, an empty frame, 2x1 items
+constexpr uint32_t cx[2] = {3u | (7u << 16), 0u}, cy[2] = {1u | (2u << 16), 0u};
+constexpr rtq::Grid g = rtq::grid(cx, cy, 2, 250, 131, 2, 1);
+static_assert(g.ox == 1 && g.oy == 1 && g.tiles_x == 3 && g.tiles_y == 1, "rtq::grid");
+}  // namespace grid_check
+
+// Whether a launch's items may cover its item rectangle only: whole frames in
+// device memory, rows stored at their own place. Row bands, peer and host
+// frames keep the whole grid.
+bool takes_queue_grid(const FrameBatch &fb, int n) {
+  if (!g_queue_grid.load(std::memory_order_relaxed)) return false;
+  for (int i = 0; i < n; ++i)
+    if (fb.f[i].nranks != 1 || (fb.f[i].flags & (kSysStoreFlags | kFlagNatural | kFlagHostFrame)) != 0 ||
+        fb.f[i].W != fb.f[0].W || fb.f[i].rows_local != fb.f[0].rows_local || fb.f[i].flags != fb.f[0].flags)
+      return false;
+  return true;
+}
+
 // Work queue of one multi-frame launch: items of `group` 8x8 wave tiles
 // (1: 1x1, 2: 2x1, 4: 2x2) of n frames, the stream's head set; *grid = the
-// launch's workgroups (the resident ones, fewer for a small batch).
+// launch's workgroups (the resident ones, fewer for a small batch; 0: the
+// launch has no items). shrink: the items cover the launch's item rectangle
+// (rtq::grid) instead of the whole frame.
 int make_queue(const FrameBatch &fb, int n, int group, int blocks, hipStream_t stream, PersistQ &q,
-               uint32_t &grid, int block = kBlock) {
+               uint32_t &grid, int block = kBlock, bool shrink = false) {
   uint32_t *heads = nullptr;
   if (const int rc = stream_queue(stream, &heads)) return rc;
   q.heads = heads;
@@ -1312,8 +1385,16 @@ int make_queue(const FrameBatch &fb, int n, int group, int blocks, hipStream_t s
     return set_err(RT_E_INVALID, "work queue: RTAMD_QSTRIDE x the head count does not fit the stream's head set");
   q.gx = group >= 2 ? 2 : 1;
   q.gy = group >= 4 ? 2 : 1;
-  q.tiles_x = (uint32_t)((fb.f[0].W + 8 * q.gx - 1) / (8 * q.gx));
-  q.per_frame = q.tiles_x * (uint32_t)((fb.f[0].rows_local + 8 * q.gy - 1) / (8 * q.gy));
+  uint32_t cx[kMaxBatch], cy[kMaxBatch];
+  for (int i = 0; i < n; ++i) {
+    cx[i] = shrink ? fb.f[i].cull_x : rtq::kWhole;
+    cy[i] = shrink ? (uint32_t)fb.f[i].P.reserved : rtq::kWhole;
+  }
+  const rtq::Grid g = rtq::grid(cx, cy, (uint32_t)n, (uint32_t)fb.f[0].W, (uint32_t)fb.f[0].rows_local, q.gx, q.gy);
+  q.ox = g.ox;
+  q.oy = g.oy;
+  q.tiles_x = g.tiles_x;
+  q.per_frame = g.tiles_x * g.tiles_y;
   q.items = q.per_frame * (uint32_t)n;
   q.cpf = q.nper = 0;  // interleaved order (PersistQ::cpf)
   const uint32_t wpb = (uint32_t)block / 64;  // waves per workgroup
@@ -1330,7 +1411,28 @@ int launch_persist_t(rt_scene *s, const S &sc, const PlaneDev &pl, const FrameBa
   if (const int rc = resident_blocks(render_persist_kernel<S, MAXD, GENERAL>, blocks, dev_cached, kPBlock)) return rc;
   PersistQ q;
   uint32_t grid = 0;
-  if (const int rc = make_queue(fb, n, group, blocks, stream, q, grid, kPBlock)) return rc;
+  const bool shrink = kQueueOrigin<S, GENERAL> && takes_queue_grid(fb, n);
+  if (const int rc = make_queue(fb, n, group, blocks, stream, q, grid, kPBlock, shrink)) return rc;
+  // Items over the launch's item rectangle only: what lies outside it is every
+  // frame's background, which a cleared frame gets from one fill launch ahead
+  // of the queue (HITS_ONLY and tPrev frames already hold it)
+  const uint32_t W = (uint32_t)fb.f[0].W, H = (uint32_t)fb.f[0].rows_local;
+  ClearOutside co;
+  co.W = W;
+  co.H = H;
+  co.x0 = std::min(W, q.ox * q.gx * 8u);
+  co.x1 = std::min(W, (q.ox + q.tiles_x) * q.gx * 8u);
+  co.y0 = std::min(H, q.oy * q.gy * 8u);
+  co.y1 = q.tiles_x ? std::min(H, (q.oy + q.per_frame / q.tiles_x) * q.gy * 8u) : co.y0;
+  const bool whole = co.x0 == 0 && co.y0 == 0 && co.x1 == W && co.y1 == H;
+  if (!whole && (fb.f[0].flags & RT_FLAG_CLEAR) && !(fb.f[0].flags & RT_FLAG_HITS_ONLY)) {
+    for (int i = 0; i < kMaxBatch; ++i) {
+      co.color[i] = i < n ? fb.f[i].color : nullptr;
+      co.t[i] = i < n ? fb.f[i].t : nullptr;
+    }
+    clear_outside_kernel<<<dim3((W + 63u) / 64u, (H + 7u) / 8u, (uint32_t)n), 64, 0, stream>>>(co);
+  }
+  if (grid == 0) return RT_OK;  // every frame's rectangle is empty: the heads stay zero
   render_persist_kernel<S, MAXD, GENERAL><<<grid, kPBlock, 0, stream>>>(sc, pl, fb, q);
   return RT_OK;
 }
@@ -1902,6 +2004,31 @@ int rtx_queue_item(uint32_t items, uint32_t heads, uint32_t head, uint32_t k, ui
 int64_t rtx_queue_cap(uint32_t items, uint32_t heads, uint32_t head) {
   if (!rtq::heads_ok(heads) || head >= heads) return -1;
   return (int64_t)rtq::cap(items, heads, head);
+}
+
+// The item rectangle of a launch for tests (host only, rtq::grid): `frames`
+// pairs of cull words (tile columns in cull_x, tile rows in cull_y, as
+// FrameArgs::cull_x and P.reserved), a W x rows frame, items of gx x gy tiles
+// -> out[4] = first item column, first item row, columns, rows (in items).
+// Not part of include/rtamd.h.
+int rtx_queue_grid(const uint32_t *cull_x, const uint32_t *cull_y, int32_t frames, int32_t W, int32_t rows,
+                   uint32_t gx, uint32_t gy, uint32_t out[4]) {
+  if (!cull_x || !cull_y || !out || frames < 0 || W <= 0 || rows <= 0 || gx < 1 || gx > 2 || gy < 1 || gy > 2)
+    return set_err(RT_E_INVALID, "bad queue grid");
+  const rtq::Grid g = rtq::grid(cull_x, cull_y, (uint32_t)frames, (uint32_t)W, (uint32_t)rows, gx, gy);
+  out[0] = g.ox;
+  out[1] = g.oy;
+  out[2] = g.tiles_x;
+  out[3] = g.tiles_y;
+  return RT_OK;
+}
+
+// Item rectangle of the persistent launches on (1) / off (0: the whole frame's
+// item grid) from now on; < 0 restores the RTAMD_QGRID setting. Not part of
+// include/rtamd.h.
+int rtx_set_queue_grid(int on) {
+  g_queue_grid.store(on < 0 ? queue_grid_env() : (on != 0));
+  return RT_OK;
 }
 
 // Heavy-first band order on (1) / off (0) from now on; < 0 restores the

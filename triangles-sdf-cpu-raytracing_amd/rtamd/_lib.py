@@ -198,6 +198,10 @@ EXPORTED = tuple(_SIGS)
 _XSIGS = {
     "rtx_set_tile_cull": (C.c_int, [C.c_int]),
     "rtx_cull_rect": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    # the persistent launches' item rectangle: its switch and the host-only function
+    "rtx_set_queue_grid": (C.c_int, [C.c_int]),
+    "rtx_queue_grid": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_uint32, C.c_uint32,
+                                 C.c_void_p]),
     # the refit's diagnostics: a mesh scene's device tree and host constants,
     # and the host restatement of build + refit (no GPU)
     "rtx_scene_mesh_download": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_void_p,
