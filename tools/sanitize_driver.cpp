@@ -14,6 +14,7 @@
 
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <random>
 #include <string>
 #include <tuple>
@@ -132,6 +133,24 @@ int main(int argc, char **argv) {
   rth::OctGpu og;
   check(rth::flatten_octree(nodes.data(), (int64_t)nodes.size() / 36, og, err), "flatten: " + err);
   std::printf("loaders: grid %ux%ux%u, octree %zu nodes\n", size[0], size[1], size[2], nodes.size() / 36);
+  // flatten_octree on what no file holds: 24 blocks, every node of a block the
+  // parent of the next one (8^24 paths over 193 nodes), then the same with
+  // the last block pointing back at the first (a cycle)
+  {
+    const size_t n = 1 + 8 * 24;
+    std::vector<uint8_t> t(36 * n, 0);
+    auto set = [&](size_t i, float v, uint32_t off) {
+      for (int k = 0; k < 8; ++k) std::memcpy(&t[36 * i + 4 * k], &v, 4);
+      std::memcpy(&t[36 * i + 32], &off, 4);
+    };
+    set(0, 0.0f, 1);
+    for (size_t b = 0; b < 24; ++b)
+      for (size_t k = 0; k < 8; ++k) set(1 + 8 * b + k, -1.0f, b < 23 ? (uint32_t)(9 + 8 * b) : 0u);
+    check(rth::flatten_octree(t.data(), (int64_t)n, og, err) && og.max_depth == 24, "shared blocks: " + err);
+    set(n - 1, -1.0f, 1);
+    check(!rth::flatten_octree(t.data(), (int64_t)n, og, err), "a cyclic octree was accepted");
+    std::printf("octree with shared blocks: depth 24, its cyclic variant refused (%s)\n", err.c_str());
+  }
   std::printf("%s\n", g_fail ? "SANITIZE DRIVER FAILED" : "sanitize driver ok");
   return g_fail ? 1 : 0;
 }

@@ -741,47 +741,51 @@ bool flatten_octree(const uint8_t *nodes36, int64_t count, OctGpu &out, std::str
       out.child[(size_t)i] = rtl::OctWord{off, 0u};
     }
   }
-  // depth (levels of inner nodes on the deepest path), with a cycle guard
-  std::vector<std::pair<uint32_t, int32_t>> st{{0u, 0}};
-  int64_t visited = 0;
-  while (!st.empty()) {
-    auto [n, d] = st.back();
-    st.pop_back();
-    if (++visited > count || d > 24) { err = "octree is cyclic or deeper than 24 levels"; return false; }
-    const uint32_t c = out.child[n].child;
-    if (c != 0 && c != rtl::kOctNeverHits) {
-      out.max_depth = std::max(out.max_depth, d + 1);
-      for (int k = 0; k < 8; ++k) st.push_back({c + (uint32_t)k, d + 1});
-    }
-  }
-  // child masks (rtl::OctWord), bottom-up: can_hit(node) = a leaf that can hit,
-  // or an inner node with a child that can hit. Post-order over the (acyclic,
-  // checked above) node graph; nodes reachable along several paths are computed once.
-  std::vector<int8_t> can((size_t)count, -1);
+  // One post-order pass over the node graph from the root, every node once
+  // however many parents share its children block (so linear in the node
+  // count), for three things:
+  //  - a cycle: a node met again while it is still open (kOpen: expanded, its
+  //    children not all done) is its own descendant;
+  //  - depth: height(leaf) = 0, height(inner) = 1 + the largest of its
+  //    children's; max_depth = height(root), the levels of inner nodes on the
+  //    longest path, refused above 24;
+  //  - child masks (rtl::OctWord): can_hit(node) = a leaf that can hit, or an
+  //    inner node with a child that can hit.
+  constexpr int8_t kUnseen = -1, kOpen = -2;
+  std::vector<int8_t> can((size_t)count, kUnseen);
+  std::vector<int8_t> height((size_t)count, 0);
   std::vector<std::pair<uint32_t, bool>> post{{0u, false}};
   while (!post.empty()) {
     auto [n, expanded] = post.back();
     post.pop_back();
-    if (can[n] >= 0) continue;
     const uint32_t c = out.child[n].child;
-    if (c == 0 || c == rtl::kOctNeverHits) {
-      can[n] = c == 0 ? 1 : 0;
-      continue;
-    }
     if (!expanded) {
+      if (can[n] >= 0) continue;  // done along another path
+      // everything above an open node's second entry is its descendant
+      if (can[n] == kOpen) { err = "octree is cyclic"; return false; }
+      if (c == 0 || c == rtl::kOctNeverHits) {
+        can[n] = c == 0 ? 1 : 0;
+        continue;
+      }
+      can[n] = kOpen;
       post.push_back({n, true});
       for (int k = 0; k < 8; ++k)
         if (can[c + k] < 0) post.push_back({c + (uint32_t)k, false});
       continue;
     }
     uint32_t m = 0;
+    int h = 0;
     for (int k = 0; k < 8; ++k) {
       if (can[c + k] > 0) m |= 1u << k;
       if (out.child[c + k].child == 0) m |= 1u << (8 + k);
+      h = std::max(h, (int)height[c + k]);
     }
+    if (h + 1 > 24) { err = "octree is deeper than 24 levels"; return false; }
+    height[n] = (int8_t)(h + 1);
     out.child[n].masks = m;
     can[n] = (m & 0xFFu) ? 1 : 0;
   }
+  out.max_depth = height[0];
   return true;
 }
 

@@ -919,6 +919,30 @@ int rtx_dispatch_probe(int kind, int maxd, int gmode, int out[3]) {
   return RT_OK;
 }
 
+// Diagnostic (not part of include/rtamd.h; host only, touches no device): what
+// rt_scene_create_octree makes of `count` 36-byte nodes before it uploads
+// anything. rth::flatten_octree's verdict is the return value (RT_E_INVALID
+// with its message); on success *max_depth is the tree's depth, *maxd the
+// stack slot count pick_maxd grants it (what the scene would carry into the
+// dispatch), and words, if given, receives the count rtl::OctWord {child,
+// masks} pairs as 2 * count uint32.
+int rtx_octree_flatten(const void *nodes36, int64_t count, int32_t *max_depth, int32_t *maxd, uint32_t *words) {
+  if (!nodes36 || count <= 0) return set_err(RT_E_INVALID, "empty octree");
+  rth::OctGpu g;
+  std::string err;
+  if (!rth::flatten_octree((const uint8_t *)nodes36, count, g, err)) return set_err(RT_E_INVALID, err);
+  int32_t m = 0;
+  if (int rc = pick_maxd(g.max_depth, m)) return rc;
+  if (max_depth) *max_depth = g.max_depth;
+  if (maxd) *maxd = m;
+  if (words)
+    for (int64_t i = 0; i < count; ++i) {
+      words[2 * i] = g.child[(size_t)i].child;
+      words[2 * i + 1] = g.child[(size_t)i].masks;
+    }
+  return RT_OK;
+}
+
 }  // extern "C"
 
 namespace rti {

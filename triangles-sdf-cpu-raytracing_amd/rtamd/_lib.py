@@ -216,6 +216,9 @@ _XSIGS = {
     # the scene dispatch's mapping (scene kind, stack slots, grid mode) ->
     # kernel template arguments, host only
     "rtx_dispatch_probe": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    # rth::flatten_octree on 36-byte nodes, host only: its verdict, the depth,
+    # the stack slots granted and the {child, masks} words
+    "rtx_octree_flatten": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p]),
     # the top-level tree of RT_INSTANCED_TLAS scenes: the shared path's lane
     # threshold, the per-ray traversal counter, and the host restatements of
     # the box test, the tree and the kernel's cursor walk (no GPU)
