@@ -34,6 +34,24 @@ def test_library_exports_every_header_symbol(rt):
     assert rt.lib().rt_abi_version() == 8
 
 
+def test_live_resources_exported_and_declared(rt):
+    """rtx_live_resources (the live owners of csrc/rt_mem.h) is exported and
+    bound like the other rtx_* diagnostics, and is no part of the public header."""
+    import ctypes as C
+    from rtamd import _lib
+    out = subprocess.run(["nm", "-D", "--defined-only", rt.LIB_PATH], capture_output=True, text=True,
+                         check=True).stdout
+    assert re.search(r"\bT rtx_live_resources$", out, flags=re.M)
+    res, args = _lib._XSIGS["rtx_live_resources"]
+    assert res is C.c_int and args == [C.POINTER(C.c_int64)]
+    assert "rtx_live_resources" not in open(HEADER).read()
+    assert "rtx_live_resources" not in rt.EXPORTED
+    assert rt.lib().rt_abi_version() == 8
+    counts = (C.c_int64 * 4)(-1, -1, -1, -1)
+    assert rt.lib().rtx_live_resources(counts) == 0 and min(counts) >= 0
+    assert rt.lib().rtx_live_resources(None) == -1
+
+
 def test_library_build_id_matches_tree(rt):
     """librtamd.so (the binary the GPU box runs) was built from this tree's
     sources: rt_build_id() equals the hash of csrc/ + include/rtamd.h."""

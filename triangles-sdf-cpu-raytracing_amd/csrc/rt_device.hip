@@ -1023,22 +1023,17 @@ __global__ __launch_bounds__(1024) void order_kernel(uint32_t *cost, uint32_t *o
 namespace rti {
 
 int ensure_events(rt_scene *s) {
-  if (!s->ev0) HIP_TRY(hipEventCreate(&s->ev0));
-  if (!s->ev1) HIP_TRY(hipEventCreate(&s->ev1));
-  if (!s->ev_host) HIP_TRY(hipEventCreateWithFlags(&s->ev_host, hipEventDisableTiming));
-  return RT_OK;
+  if (int rc = s->fb.ev0.create_timing()) return rc;
+  if (int rc = s->fb.ev1.create_timing()) return rc;
+  return s->drop.ev_host.create(hipEventDisableTiming);
 }
 
 int ensure_fb(rt_scene *s, size_t px) {
-  if (px <= s->fb_cap) return RT_OK;
-  if (s->d_color) HIP_NOTE(hipFree(s->d_color));
-  if (s->d_t) HIP_NOTE(hipFree(s->d_t));
-  s->d_color = nullptr;
-  s->d_t = nullptr;
-  s->fb_cap = 0;
-  HIP_TRY(hipMalloc(&s->d_color, px * 4));
-  HIP_TRY(hipMalloc(&s->d_t, px * 4));
-  s->fb_cap = px;
+  if (px <= s->fb.cap) return RT_OK;
+  s->fb.cap = 0;
+  if (int rc = s->fb.color.alloc(px)) return rc;
+  if (int rc = s->fb.t.alloc(px)) return rc;
+  s->fb.cap = px;
   return RT_OK;
 }
 
@@ -1085,41 +1080,36 @@ int schedule_begin(rt_scene *s, FrameArgs &fa, uint32_t gx, uint32_t gy, hipStre
   // Frames of this scene arriving on alternating streams are frames in flight:
   // each one's tail is filled by the next frame's tiles. Such frames render in
   // blockIdx order and leave the schedule state alone.
-  const bool same_stream = stream == s->last_stream;
-  s->last_stream = stream;
-  if (!s->sched_on || !same_stream) return RT_OK;
+  const bool same_stream = stream == s->sched.last_stream;
+  s->sched.last_stream = stream;
+  if (!s->info.sched_on || !same_stream) return RT_OK;
   const uint32_t nb = gx * gy;
-  if (!s->sched_os) {
-    HIP_TRY(hipStreamCreateWithFlags(&s->sched_os, hipStreamNonBlocking));
+  if (!s->sched.os.s) {
     char label[64];
     std::snprintf(label, sizeof label, "scene %p schedule stream", (void *)s);
-    rterr::stream_add(s->sched_os, s->device, label);
-    for (hipEvent_t &e : s->ord_ev) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    HIP_TRY(hipEventCreateWithFlags(&s->frame_ev, hipEventDisableTiming));
+    if (int rc = s->sched.os.create(s->device, label)) return rc;
+    for (rtmem::Event &e : s->sched.ord_ev)
+      if (int rc = e.create(hipEventDisableTiming)) return rc;
+    if (int rc = s->sched.frame_ev.create(hipEventDisableTiming)) return rc;
   }
-  if (nb > s->sched_cap) {
-    HIP_TRY(hipStreamSynchronize(s->sched_os));  // (no order kernel still reads the old buffers)
+  if (nb > s->sched.cap) {
+    HIP_TRY(hipStreamSynchronize(s->sched.os.s));  // (no order kernel still reads the old buffers)
+    s->sched.cap = 0;
+    s->sched.key[0] = s->sched.key[1] = 0;
     for (int b = 0; b < 2; ++b) {
-      if (s->d_cost[b]) HIP_NOTE(hipFree(s->d_cost[b]));
-      if (s->d_order[b]) HIP_NOTE(hipFree(s->d_order[b]));
-      s->d_cost[b] = s->d_order[b] = nullptr;
-      s->sched_key[b] = 0;
+      if (int rc = s->sched.cost[b].alloc(nb)) return rc;
+      if (int rc = s->sched.order[b].alloc(nb)) return rc;
+      HIP_TRY(hipMemsetAsync(s->sched.cost[b].p, 0, (size_t)nb * 4, stream));  // (in the frame's stream order)
     }
-    s->sched_cap = 0;
-    for (int b = 0; b < 2; ++b) {
-      HIP_TRY(hipMalloc(&s->d_cost[b], (size_t)nb * 4));
-      HIP_TRY(hipMalloc(&s->d_order[b], (size_t)nb * 4));
-      HIP_TRY(hipMemsetAsync(s->d_cost[b], 0, (size_t)nb * 4, stream));  // (in the frame's stream order)
-    }
-    s->sched_cap = nb;
+    s->sched.cap = nb;
   }
-  const int p = s->sched_par;
-  if (s->ord_rec[p]) {
+  const int p = s->sched.par;
+  if (s->sched.rec[p]) {
     // usually long done (it ran beside the previous frame): then no
     // cross-stream barrier goes into the frame's stream
-    const hipError_t q = hipEventQuery(s->ord_ev[p]);
+    const hipError_t q = hipEventQuery(s->sched.ord_ev[p].e);
     if (q == hipErrorNotReady) {
-      HIP_TRY(hipStreamWaitEvent(stream, s->ord_ev[p], 0));
+      HIP_TRY(hipStreamWaitEvent(stream, s->sched.ord_ev[p].e, 0));
     } else if (q != hipSuccess) {
       HIP_TRY(q);
     }
@@ -1130,28 +1120,28 @@ int schedule_begin(rt_scene *s, FrameArgs &fa, uint32_t gx, uint32_t gy, hipStre
   // Renderer::draw loop) -- else the one two frames old. The previous frame's
   // order buffer is rewritten only by the next frame's order kernel, which
   // runs after the next frame, so after this one.
-  if (RT_SCHED_FRESH && s->ord_rec[p ^ 1] && s->sched_key[p ^ 1] == key &&
-      hipEventQuery(s->ord_ev[p ^ 1]) == hipSuccess) {
-    fa.order = s->d_order[p ^ 1];
-  } else if (s->sched_key[p] == key) {
-    fa.order = s->d_order[p];
+  if (RT_SCHED_FRESH && s->sched.rec[p ^ 1] && s->sched.key[p ^ 1] == key &&
+      hipEventQuery(s->sched.ord_ev[p ^ 1].e) == hipSuccess) {
+    fa.order = s->sched.order[p ^ 1].p;
+  } else if (s->sched.key[p] == key) {
+    fa.order = s->sched.order[p].p;
   }
-  fa.cost = s->d_cost[p];
+  fa.cost = s->sched.cost[p].p;
   return RT_OK;
 }
 
 // the frame's order kernel on the side stream, after the frame
 int schedule_end(rt_scene *s, const FrameArgs &fa, uint32_t gx, uint32_t gy, hipStream_t stream) {
   if (!fa.cost) return RT_OK;
-  const int p = s->sched_par;
-  HIP_TRY(hipEventRecord(s->frame_ev, stream));
-  HIP_TRY(hipStreamWaitEvent(s->sched_os, s->frame_ev, 0));
-  order_kernel<<<1, 1024, 0, s->sched_os>>>(s->d_cost[p], s->d_order[p], gx * gy);
+  const int p = s->sched.par;
+  HIP_TRY(hipEventRecord(s->sched.frame_ev.e, stream));
+  HIP_TRY(hipStreamWaitEvent(s->sched.os.s, s->sched.frame_ev.e, 0));
+  order_kernel<<<1, 1024, 0, s->sched.os.s>>>(s->sched.cost[p].p, s->sched.order[p].p, gx * gy);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(s->ord_ev[p], s->sched_os));
-  s->ord_rec[p] = true;
-  s->sched_key[p] = (gx << 16) | gy;
-  s->sched_par = p ^ 1;
+  HIP_TRY(hipEventRecord(s->sched.ord_ev[p].e, s->sched.os.s));
+  s->sched.rec[p] = true;
+  s->sched.key[p] = (gx << 16) | gy;
+  s->sched.par = p ^ 1;
   return RT_OK;
 }
 
@@ -1162,7 +1152,7 @@ namespace rti {
 int launch_render(rt_scene *s, const FrameArgs &fa_in, hipStream_t stream, unsigned long long *counters, int diag,
                   bool sched) {
   FrameArgs fa = fa_in;
-  const bool general = s->plane.on || fa.P.shading_mode != RT_SHADING_NORMAL;
+  const bool general = s->info.plane.on || fa.P.shading_mode != RT_SHADING_NORMAL;
   const uint32_t gx = (fa.W + kFTile - 1) / kFTile, gy = (fa.rows_local + kFTile - 1) / kFTile;
   fa.order = nullptr;
   fa.cost = nullptr;
@@ -1171,7 +1161,7 @@ int launch_render(rt_scene *s, const FrameArgs &fa_in, hipStream_t stream, unsig
     if (rc) return rc;
   }
   if (!dispatch_scene(s, [&](const auto &sc, auto slots) {
-        launch_render_t<std::decay_t<decltype(sc)>, decltype(slots)::value>(sc, s->plane, fa, general, stream,
+        launch_render_t<std::decay_t<decltype(sc)>, decltype(slots)::value>(sc, s->info.plane, fa, general, stream,
                                                                             counters, diag);
       }))
     return set_err(RT_E_STATE, "scene has no geometry");
@@ -1488,7 +1478,7 @@ int launch_batch_t(rt_scene *s, const S &sc, const PlaneDev &pl, const FrameBatc
   // a million pixels take the block dispatch (band_takes_queue).
   const int group = persist_group(S::kQueueGroup);
   if constexpr (PumpOf<S>::kHas) {
-    if (!general && (pump_env() || (s && s->pump_on)) && persist_enabled() && band_takes_queue(fb.f[0]))
+    if (!general && (pump_env() || (s && s->info.pump_on)) && persist_enabled() && band_takes_queue(fb.f[0]))
       return launch_pump_t<typename PumpOf<S>::P, MAXD>(PumpOf<S>::make(sc), fb, n,
                                                         persist_group(S::kQueueGroup ? S::kQueueGroup : kPumpGroup),
                                                         stream);
@@ -1531,16 +1521,16 @@ namespace rti {
 
 // One launch for n <= kMaxBatch frames of equal size / tile (blockIdx order).
 int launch_batch(rt_scene *s, FrameBatch &fb, int n, hipStream_t stream) {
-  const bool general = s->plane.on || fb.f[0].P.shading_mode != RT_SHADING_NORMAL;
+  const bool general = s->info.plane.on || fb.f[0].P.shading_mode != RT_SHADING_NORMAL;
   for (int i = 0; i < n; ++i) {
-    if (general != (s->plane.on || fb.f[i].P.shading_mode != RT_SHADING_NORMAL))
+    if (general != (s->info.plane.on || fb.f[i].P.shading_mode != RT_SHADING_NORMAL))
       return set_err(RT_E_INVALID, "frames of one batch must share the shading path");
     fb.f[i].order = nullptr;
     fb.f[i].cost = nullptr;
   }
   int rc = RT_OK;
   if (!dispatch_scene(s, [&](const auto &sc, auto slots) {
-        rc = launch_batch_t<std::decay_t<decltype(sc)>, decltype(slots)::value>(s, sc, s->plane, fb, n, general,
+        rc = launch_batch_t<std::decay_t<decltype(sc)>, decltype(slots)::value>(s, sc, s->info.plane, fb, n, general,
                                                                                 stream);
       }))
     return set_err(RT_E_STATE, "scene has no geometry");
@@ -1765,10 +1755,10 @@ int fill_frame(FrameArgs &fa, const rt_scene *s, const rt_render_params *p, uint
   // octrees never read it
   fa.cull_x = kCullWhole;
   fa.P.reserved = (int32_t)kCullWhole;
-  if (g_tile_cull.load(std::memory_order_relaxed) && s && s->kind == RT_SCENE_MESH && !s->plane.on &&
-      p->shading_mode == RT_SHADING_NORMAL && s->root != rtl::kInvalidChild && !(s->root & rtl::kLeafBit)) {
+  if (g_tile_cull.load(std::memory_order_relaxed) && s && s->info.kind == RT_SCENE_MESH && !s->info.plane.on &&
+      p->shading_mode == RT_SHADING_NORMAL && s->mesh.root != rtl::kInvalidChild && !(s->mesh.root & rtl::kLeafBit)) {
     int32_t r[4];
-    if (cull_rect(p, W, H, s->root_box, s->root_child, 8, r)) {
+    if (cull_rect(p, W, H, s->mesh.root_box, s->mesh.root_child, 8, r)) {
       fa.cull_x = (uint32_t)r[0] | ((uint32_t)r[1] << 16);
       fa.P.reserved = (int32_t)((uint32_t)r[2] | ((uint32_t)r[3] << 16));
     }
@@ -1886,18 +1876,17 @@ static int count_frames(rt_scene *s, const rt_render_params *params, int32_t fra
   if ((rc = check_params(params, W, H))) return rc;
   const size_t px = (size_t)W * H;
   if ((rc = ensure_fb(s, px))) return rc;
-  unsigned long long *d = nullptr;
-  HIP_TRY(hipMalloc(&d, C_ALL * sizeof(unsigned long long)));
-  hipError_t e = hipMemset(d, 0, C_ALL * sizeof(unsigned long long));
-  if (e == hipSuccess) HIP_NOTE(hipMemset(s->d_t, 0x7f, px * 4));
+  rtmem::DevArray<unsigned long long> d;
+  if ((rc = d.alloc(C_ALL))) return rc;
+  hipError_t e = hipMemset(d.p, 0, d.bytes());
+  if (e == hipSuccess) HIP_NOTE(hipMemset(s->fb.t.p, 0x7f, px * 4));
   for (int32_t f = 0; f < frames && e == hipSuccess && rc == RT_OK; ++f) {
     FrameArgs fa;
     if (!(rc = check_params(params + f, W, H)) &&
-        !(rc = fill_frame(fa, s, params + f, s->d_color, s->d_t, W, H, flags, tile)))
-      rc = launch_render(s, fa, 0, d, 1);
+        !(rc = fill_frame(fa, s, params + f, s->fb.color.p, s->fb.t.p, W, H, flags, tile)))
+      rc = launch_render(s, fa, 0, d.p, 1);
   }
-  if (e == hipSuccess && rc == RT_OK) e = hipMemcpy(h, d, sizeof(h), hipMemcpyDeviceToHost);
-  HIP_NOTE(hipFree(d));
+  if (e == hipSuccess && rc == RT_OK) e = hipMemcpy(h, d.p, sizeof(h), hipMemcpyDeviceToHost);
   if (rc) return rc;
   if (e != hipSuccess) return set_err(RT_E_DEVICE, std::string("rt_count_work: ") + hipGetErrorString(e));
   return RT_OK;
@@ -1941,13 +1930,12 @@ int rtx_wave_stamps(rt_scene *s, const rt_render_params *params, int32_t W, int3
   if (*nwaves < nw) { *nwaves = nw; return set_err(RT_E_INVALID, "buffer too small"); }
   const size_t px = (size_t)W * H;
   if ((rc = ensure_fb(s, px))) return rc;
-  unsigned long long *d = nullptr;
-  HIP_TRY(hipMalloc(&d, nw * 4 * sizeof(unsigned long long)));
+  rtmem::DevArray<unsigned long long> d;
+  if ((rc = d.alloc((size_t)nw * 4))) return rc;
   FrameArgs fa;
-  if (!(rc = fill_frame(fa, s, params, s->d_color, s->d_t, W, H, flags, nullptr)))
-    rc = launch_render(s, fa, 0, d, 2);
-  hipError_t e = rc ? hipSuccess : hipMemcpy(out, d, nw * 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost);
-  HIP_NOTE(hipFree(d));
+  if (!(rc = fill_frame(fa, s, params, s->fb.color.p, s->fb.t.p, W, H, flags, nullptr)))
+    rc = launch_render(s, fa, 0, d.p, 2);
+  hipError_t e = rc ? hipSuccess : hipMemcpy(out, d.p, d.bytes(), hipMemcpyDeviceToHost);
   if (rc) return rc;
   if (e != hipSuccess) return set_err(RT_E_DEVICE, hipGetErrorString(e));
   *nwaves = nw;
@@ -2050,7 +2038,7 @@ int rtx_set_persist_stamps(void *d_buf, int64_t cap_waves) {
 // Diagnostic A/B switch: cooperative tail of the mesh primary path on (default) / off.
 int rtx_set_coop(rt_scene *s, int on) {
   if (!s) return set_err(RT_E_INVALID, "scene is NULL");
-  s->coop = on != 0;
+  s->info.coop = on != 0;
   return RT_OK;
 }
 
@@ -2065,15 +2053,15 @@ int rtx_set_refill(int32_t lanes) {
 
 int rtx_set_pump(rt_scene *s, int on) {
   if (!s) return set_err(RT_E_INVALID, "scene is NULL");
-  s->pump_on = on != 0;
+  s->info.pump_on = on != 0;
   return RT_OK;
 }
 
 // Diagnostic A/B switch: cost-ordered block schedule on (default) / off.
 int rtx_set_schedule(rt_scene *s, int on) {
   if (!s) return set_err(RT_E_INVALID, "scene is NULL");
-  s->sched_on = on != 0;
-  s->sched_key[0] = s->sched_key[1] = 0;
+  s->info.sched_on = on != 0;
+  s->sched.key[0] = s->sched.key[1] = 0;
   return RT_OK;
 }
 
@@ -2085,20 +2073,20 @@ int rt_bench_frames(rt_scene *s, const rt_render_params *params, int32_t frames,
   if ((rc = check_params(params, W, H))) return rc;
   const size_t px = (size_t)W * H;
   if ((rc = ensure_fb(s, px)) || (rc = ensure_events(s))) return rc;
-  HIP_TRY(hipMemset(s->d_t, 0x7f, px * 4));
+  HIP_TRY(hipMemset(s->fb.t.p, 0x7f, px * 4));
   HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipEventRecord(s->ev0, 0));
+  HIP_TRY(hipEventRecord(s->fb.ev0.e, 0));
   for (int32_t f = 0; f < frames; ++f) {
     FrameArgs fa;
     if ((rc = check_params(params + f, W, H)) ||
-        (rc = fill_frame(fa, s, params + f, s->d_color, s->d_t, W, H, flags, nullptr)) ||
+        (rc = fill_frame(fa, s, params + f, s->fb.color.p, s->fb.t.p, W, H, flags, nullptr)) ||
         (rc = launch_render(s, fa, 0)))
       return rc;
   }
-  HIP_TRY(hipEventRecord(s->ev1, 0));
-  HIP_TRY(hipEventSynchronize(s->ev1));
+  HIP_TRY(hipEventRecord(s->fb.ev1.e, 0));
+  HIP_TRY(hipEventSynchronize(s->fb.ev1.e));
   float ms = 0.0f;
-  HIP_TRY(hipEventElapsedTime(&ms, s->ev0, s->ev1));
+  HIP_TRY(hipEventElapsedTime(&ms, s->fb.ev0.e, s->fb.ev1.e));
   if (total_ms) *total_ms = ms;
   if (mean_ms) *mean_ms = ms / (float)frames;
   return RT_OK;
@@ -2266,17 +2254,17 @@ void launch_trace_t(const S &sc, const PlaneDev &pl, const rt_ray_batch &b, int 
 // rt_trace_rays_device's launch: an instanced scene goes to rt_instances.hip,
 // every other one through the scene dispatch
 int launch_trace(rt_scene *s, const rt_ray_batch &b, int mode, hipStream_t stream) {
-  if (s->kind == RT_SCENE_INSTANCED) {
+  if (s->info.kind == RT_SCENE_INSTANCED) {
     // a bottom-level scene refitted since its table entry was written: the
     // entry (and a top-level tree) catch up in stream order ahead of the trace
     if (int rc = rti::instanced_sync(s, stream)) return rc;
-    const rti::InstArgs a{s->d_inst, s->d_blas, s->ninst, s->maxd, s->d_tlas, s->tlas_leaves};
-    if (s->d_mixed) return rti::trace_mixed_launch(rti::MixedArgs{a, s->d_mixed}, s->plane, b, mode, stream);
-    return s->d_tlas ? rti::trace_tlas_launch(a, s->plane, b, mode, stream)
-                     : rti::trace_instances_launch(a, s->plane, b, mode, stream);
+    const rti::InstArgs a{s->inst.recs.p, s->inst.tab.p, s->inst.n, s->info.maxd, s->inst.tlas.p, s->inst.tlas_leaves};
+    if (s->inst.mixed.p) return rti::trace_mixed_launch(rti::MixedArgs{a, s->inst.mixed.p}, s->info.plane, b, mode, stream);
+    return s->inst.tlas.p ? rti::trace_tlas_launch(a, s->info.plane, b, mode, stream)
+                     : rti::trace_instances_launch(a, s->info.plane, b, mode, stream);
   }
   if (!dispatch_scene(s, [&](const auto &sc, auto slots) {
-        launch_trace_t<std::decay_t<decltype(sc)>, decltype(slots)::value>(sc, s->plane, b, mode, stream);
+        launch_trace_t<std::decay_t<decltype(sc)>, decltype(slots)::value>(sc, s->info.plane, b, mode, stream);
       }))
     return set_err(RT_E_STATE, "scene has no geometry");
   HIP_TRY(hipGetLastError());
@@ -2291,32 +2279,27 @@ int rt_intersect_rays(rt_scene *s, const float *o, const float *d, int64_t n, fl
                       int32_t *hit, float *t, float *normal, int64_t *prim) {
   if (!s || !o || !d || !hit || !t || !normal || !prim) return set_err(RT_E_INVALID, "NULL argument");
   if (n <= 0) return RT_OK;
-  float *dO = nullptr, *dD = nullptr, *dT = nullptr, *dN = nullptr;
-  int32_t *dH = nullptr;
-  int64_t *dP = nullptr;
-  auto cleanup = [&]() {
-    void *ps[] = {dO, dD, dT, dN, dH, dP};
-    for (void *q : ps)
-      if (q) HIP_NOTE(hipFree(q));
-  };
+  const size_t m = (size_t)n;
+  rtmem::DevArray<float> aO, aD, aT, aN;
+  rtmem::DevArray<int32_t> aH;
+  rtmem::DevArray<int64_t> aP;
   hipError_t e = hipSuccess;
   do {
-    if ((e = hipMalloc(&dO, n * 12)) || (e = hipMalloc(&dD, n * 12)) || (e = hipMalloc(&dT, n * 4)) ||
-        (e = hipMalloc(&dN, n * 12)) || (e = hipMalloc(&dH, n * 4)) || (e = hipMalloc(&dP, n * 8)))
+    if ((e = aO.alloc_e(3 * m)) || (e = aD.alloc_e(3 * m)) || (e = aT.alloc_e(m)) || (e = aN.alloc_e(3 * m)) ||
+        (e = aH.alloc_e(m)) || (e = aP.alloc_e(m)))
       break;
+    float *const dO = aO.p, *const dD = aD.p, *const dT = aT.p, *const dN = aN.p;
+    int32_t *const dH = aH.p;
+    int64_t *const dP = aP.p;
     if ((e = rtdma::h2d(dO, o, n * 12, nullptr)) || (e = rtdma::h2d(dD, d, n * 12, nullptr))) break;
-    if (s->kind == RT_SCENE_INSTANCED) {
+    if (s->info.kind == RT_SCENE_INSTANCED) {
       // the device entry's kernel on the staged buffers (the same values)
       const rt_ray_batch b{n, dO, dD, nullptr, nullptr, tnear, tfar, dH, dT, dN, dP};
-      if (const int rc = launch_trace(s, b, kRaysNormal, nullptr)) {
-        cleanup();
-        return rc;
-      }
+      if (const int rc = launch_trace(s, b, kRaysNormal, nullptr)) return rc;
     } else if (!dispatch_scene(s, [&](const auto &sc, auto slots) {
-                 launch_rays_t<std::decay_t<decltype(sc)>, decltype(slots)::value>(sc, s->plane, dO, dD, n, tnear,
+                 launch_rays_t<std::decay_t<decltype(sc)>, decltype(slots)::value>(sc, s->info.plane, dO, dD, n, tnear,
                                                                                    tfar, dH, dT, dN, dP);
                })) {
-      cleanup();
       return set_err(RT_E_STATE, "rt_intersect_rays: scene has no geometry");
     }
     if ((e = hipGetLastError())) break;
@@ -2324,7 +2307,6 @@ int rt_intersect_rays(rt_scene *s, const float *o, const float *d, int64_t n, fl
         (e = rtdma::d2h(normal, dN, n * 12, nullptr)) || (e = rtdma::d2h(prim, dP, n * 8, nullptr)))
       break;
   } while (0);
-  cleanup();
   if (e != hipSuccess) return set_err(RT_E_DEVICE, std::string("rt_intersect_rays: ") + hipGetErrorString(e));
   return RT_OK;
 }

@@ -91,7 +91,7 @@ GridS<kMode> make_adapter(AdapterTag<GridS<kMode>>, const rt_scene *, const Grid
 }
 template <bool PACK>
 OctS<PACK> make_adapter(AdapterTag<OctS<PACK>>, const rt_scene *s, const GridDev &) {
-  return OctS<PACK>{OctDev{s->d_child, s->d_ovals}};
+  return OctS<PACK>{OctDev{s->geo.child.p, s->geo.ovals.p}};
 }
 
 // f(adapter value, Slots<N>{}) for scene s; false, f not called, when s has no
@@ -100,11 +100,11 @@ template <class F>
 bool dispatch_scene(const rt_scene *s, F &&f) {
   GridDev gd{};
   int gmode = 0;
-  if (s->kind == RT_SCENE_GRID) {
+  if (s->info.kind == RT_SCENE_GRID) {
     gd = rti::grid_dev(s);
     gmode = rti::grid_mode(s, gd);
   }
-  return dispatch_types(s->kind, s->maxd, gmode,
+  return dispatch_types(s->info.kind, s->info.maxd, gmode,
                         [&](auto adapter, auto n) { f(make_adapter(adapter, s, gd), n); });
 }
 

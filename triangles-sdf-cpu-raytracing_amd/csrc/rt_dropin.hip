@@ -65,18 +65,15 @@ __global__ void untile_kernel(const uint32_t *pc, const float *pt, int64_t per_r
 // the null stream) and the event that orders the uploads before the kernel
 int ensure_copy_streams(rt_scene *s) {
   for (int k = 0; k < 2; ++k)
-    if (!s->xs[k]) {
-      HIP_TRY(hipStreamCreateWithFlags(&s->xs[k], hipStreamNonBlocking));
+    if (!s->drop.xs[k].s) {
       char label[64];
       std::snprintf(label, sizeof label, "scene %p stream %s", (void *)s, k ? "t" : "render/colour");
-      rterr::stream_add(s->xs[k], s->device, label);
+      if (int rc = s->drop.xs[k].create(s->device, label)) return rc;
     }
-  if (!s->xev) HIP_TRY(hipEventCreateWithFlags(&s->xev, hipEventDisableTiming));
-  if (!s->d_hit_box) HIP_TRY(hipMalloc(&s->d_hit_box, 4 * sizeof(int32_t)));
-  if (!s->h_hit_box_dev) {  // (guarded on the device address: a failed lookup is retried next call)
-    if (!s->h_hit_box) HIP_TRY(hipHostMalloc(&s->h_hit_box, 4 * sizeof(int32_t), hipHostMallocMapped));
-    HIP_TRY(hipHostGetDevicePointer((void **)&s->h_hit_box_dev, s->h_hit_box, 0));
-  }
+  if (int rc = s->drop.xev.create(hipEventDisableTiming)) return rc;
+  if (!s->drop.hit_box.p)
+    if (int rc = s->drop.hit_box.alloc(4)) return rc;
+  if (!s->drop.h_hit_box.dev) return s->drop.h_hit_box.alloc(4, hipHostMallocMapped);
   return RT_OK;
 }
 
@@ -84,10 +81,10 @@ int ensure_copy_streams(rt_scene *s) {
 // rt_render on pageable caller buffers (host copies on one side, DMA on the
 // other). Its streams are synchronised before a smaller frame is replaced.
 int ensure_stage(rt_scene *s, size_t px) {
-  if (px <= s->stage.cap) return RT_OK;
-  if (s->xs[0]) HIP_TRY(hipStreamSynchronize(s->xs[0]));  // (the previous frame's work on the old frame)
-  if (s->xs[1]) HIP_TRY(hipStreamSynchronize(s->xs[1]));
-  if (const hipError_t e = s->stage.ensure(px))
+  if (px <= s->drop.stage.cap) return RT_OK;
+  if (s->drop.xs[0].s) HIP_TRY(hipStreamSynchronize(s->drop.xs[0].s));  // (the previous frame's work on the old frame)
+  if (s->drop.xs[1].s) HIP_TRY(hipStreamSynchronize(s->drop.xs[1].s));
+  if (const hipError_t e = s->drop.stage.ensure(px))
     return set_err(RT_E_DEVICE, std::string("staging frame: ") + hipGetErrorString(e));
   return RT_OK;
 }
@@ -143,7 +140,7 @@ bool host_sys_stores() {
 int render_cleared_zero_copy(rt_scene *s, FrameArgs fa, uint32_t *color, float *t, int32_t W, int32_t H,
                              float *ms) {
   const size_t px = (size_t)W * H;
-  hipStream_t a = s->xs[0];
+  hipStream_t a = s->drop.xs[0].s;
   rterr::stream_mark(a, "rt_render (zero-copy cleared frame)");
   // every return waits for stream a while it may still touch the caller's
   // buffers; the span-word reset (below) is the library's own and
@@ -165,80 +162,76 @@ int render_cleared_zero_copy(rt_scene *s, FrameArgs fa, uint32_t *color, float *
       g_render_fault.fetch_sub(1);
       return set_err(RT_E_DEVICE, "injected rt_render failure (rtx_render_inject_failure)");
     }
-    HIP_TRY(hipEventRecord(s->ev0, a));
+    HIP_TRY(hipEventRecord(s->fb.ev0.e, a));
     // (the frame's tile-order kernel runs on the schedule's side stream: not waited for)
     if (int rc = launch_render(s, fa, a)) return rc;
-    HIP_TRY(hipEventRecord(s->ev1, a));
-    HIP_TRY(hipEventSynchronize(s->ev1));
+    HIP_TRY(hipEventRecord(s->fb.ev1.e, a));
+    HIP_TRY(hipEventSynchronize(s->fb.ev1.e));
     drain.on = false;
-    if (ms) HIP_TRY(hipEventElapsedTime(ms, s->ev0, s->ev1));
+    if (ms) HIP_TRY(hipEventElapsedTime(ms, s->fb.ev0.e, s->fb.ev1.e));
     return RT_OK;
   }
   if (int rc = ensure_stage(s, px)) return rc;
   void *sc = nullptr, *st = nullptr;
-  HIP_TRY(hipHostGetDevicePointer(&sc, s->stage.c, 0));
-  HIP_TRY(hipHostGetDevicePointer(&st, s->stage.t, 0));
-  if (H > s->span_cap) {
+  HIP_TRY(hipHostGetDevicePointer(&sc, s->drop.stage.c, 0));
+  HIP_TRY(hipHostGetDevicePointer(&st, s->drop.stage.t, 0));
+  if (H > s->drop.span_cap) {
     HIP_TRY(hipStreamSynchronize(a));  // (the previous frame's span clear reads d_row_span)
-    if (s->d_row_span) HIP_NOTE(hipFree(s->d_row_span));
-    if (s->h_row_span) HIP_NOTE(hipHostFree(s->h_row_span));
-    s->d_row_span = s->h_row_span = s->h_row_span_dev = nullptr;
-    s->span_cap = 0;
-    HIP_TRY(hipMalloc(&s->d_row_span, (size_t)H * 2 * sizeof(int32_t)));
-    HIP_TRY(hipHostMalloc(&s->h_row_span, (size_t)H * 2 * sizeof(int32_t), hipHostMallocMapped));
-    HIP_TRY(hipHostGetDevicePointer((void **)&s->h_row_span_dev, s->h_row_span, 0));
-    s->span_cap = H;
-    s->stage.mark_dirty();  // (the spans of the frame in the staging frame are gone)
+    s->drop.span_cap = 0;
+    if (int rc = s->drop.row_span.alloc((size_t)H * 2)) return rc;
+    if (int rc = s->drop.h_row_span.alloc((size_t)H * 2, hipHostMallocMapped)) return rc;
+    s->drop.span_cap = H;
+    s->drop.stage.mark_dirty();  // (the spans of the frame in the staging frame are gone)
   }
   // (otherwise the previous frame's span reset left both the staging
   // frame and the span words reset)
-  if (s->stage.clear_for(W, H)) {
-    s->stage.mark_dirty();  // (a failed reset of the span words leaves the next frame to redo both)
-    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)s->d_row_span, 0x7FFFFFFF, (size_t)H * 2, a));
-    s->stage.mark_clean();
+  if (s->drop.stage.clear_for(W, H)) {
+    s->drop.stage.mark_dirty();  // (a failed reset of the span words leaves the next frame to redo both)
+    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)s->drop.row_span.p, 0x7FFFFFFF, (size_t)H * 2, a));
+    s->drop.stage.mark_clean();
   }
   fa.color = (uint32_t *)sc;
   fa.t = (float *)st;
-  fa.hit_box = s->d_row_span;
+  fa.hit_box = s->drop.row_span.p;
   fa.flags |= kFlagRowSpan;
   if (g_render_fault.load() > 0) {
     g_render_fault.fetch_sub(1);
     return set_err(RT_E_DEVICE, "injected rt_render failure (rtx_render_inject_failure)");
   }
   const auto h0 = std::chrono::steady_clock::now();
-  HIP_TRY(hipEventRecord(s->ev0, a));
-  s->stage.mark_dirty();  // until its spans are cleared again below
+  HIP_TRY(hipEventRecord(s->fb.ev0.e, a));
+  s->drop.stage.mark_dirty();  // until its spans are cleared again below
   if (int rc = launch_render(s, fa, a)) return rc;
-  HIP_TRY(hipEventRecord(s->ev1, a));
-  box_out_kernel<<<(unsigned)((2 * H + 255) / 256), 256, 0, a>>>(s->d_row_span, s->h_row_span_dev, 2 * H);
+  HIP_TRY(hipEventRecord(s->fb.ev1.e, a));
+  box_out_kernel<<<(unsigned)((2 * H + 255) / 256), 256, 0, a>>>(s->drop.row_span.p, s->drop.h_row_span.dev, 2 * H);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(s->ev_host, a));
+  HIP_TRY(hipEventRecord(s->drop.ev_host.e, a));
   const auto h1 = std::chrono::steady_clock::now();
-  HIP_TRY(hipEventSynchronize(s->ev_host));
+  HIP_TRY(hipEventSynchronize(s->drop.ev_host.e));
   const auto h2 = std::chrono::steady_clock::now();
-  if (ms) HIP_TRY(hipEventElapsedTime(ms, s->ev0, s->ev1));
+  if (ms) HIP_TRY(hipEventElapsedTime(ms, s->fb.ev0.e, s->fb.ev1.e));
   // the stored spans to the caller (host threads; every other pixel of the
   // caller's cleared frame already holds the staging frame's 0 / +inf); the
   // host resets the same spans of the staging frame as it goes (the GPU only
   // stores into it, from the next call on), and the span words are reset in
   // stream order before the next frame's kernel; the call does not wait for that
   const bool host_clear = host_clears_stage();
-  rth::copy_spans(color, t, s->stage.c, s->stage.t, W, H, s->h_row_span, 0, host_clear);
+  rth::copy_spans(color, t, s->drop.stage.c, s->drop.stage.t, W, H, s->drop.h_row_span.h, 0, host_clear);
   const auto h3 = std::chrono::steady_clock::now();
   drain.on = false;
   if (host_clear) {
-    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)s->d_row_span, 0x7FFFFFFF, (size_t)H * 2, a));
+    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)s->drop.row_span.p, 0x7FFFFFFF, (size_t)H * 2, a));
   } else {
-    clear_spans_kernel<<<(unsigned)H, 256, 0, a>>>((uint32_t *)sc, (float *)st, s->d_row_span, W);
+    clear_spans_kernel<<<(unsigned)H, 256, 0, a>>>((uint32_t *)sc, (float *)st, s->drop.row_span.p, W);
     HIP_TRY(hipGetLastError());
   }
-  s->stage.mark_clean();
+  s->drop.stage.mark_clean();
   if (dropin_trace()) {  // RTAMD_DROPIN_TRACE=1: host-side phases of this call (dev switch)
     const auto h4 = std::chrono::steady_clock::now();
     auto us = [](auto x, auto y) { return std::chrono::duration<double, std::micro>(y - x).count(); };
     int64_t pxs = 0;
     for (int32_t y = 0; y < H; ++y)
-      if (s->h_row_span[2 * y] <= -s->h_row_span[2 * y + 1]) pxs += -s->h_row_span[2 * y + 1] - s->h_row_span[2 * y] + 1;
+      if (s->drop.h_row_span.h[2 * y] <= -s->drop.h_row_span.h[2 * y + 1]) pxs += -s->drop.h_row_span.h[2 * y + 1] - s->drop.h_row_span.h[2 * y] + 1;
     std::fprintf(stderr, "dropin: issue %.1f, wait %.1f, copy %.1f (%lld px), clear issue %.1f us; kernel %.1f us\n",
                  us(h0, h1), us(h1, h2), us(h2, h3), (long long)pxs, us(h3, h4), ms ? *ms * 1e3 : -1.0);
   }
@@ -266,21 +259,21 @@ int rt_render(rt_scene *s, const rt_render_params *p, uint32_t *color, float *t,
     return render_cleared_zero_copy(s, fa, color, t, W, H, ms);
   }
   if ((rc = ensure_fb(s, px)) || (rc = ensure_events(s)) || (rc = ensure_copy_streams(s))) return rc;
-  fa.color = s->d_color;
-  fa.t = s->d_t;
+  fa.color = s->fb.color.p;
+  fa.t = s->fb.t.p;
   // The DMA engines only ever see pinned memory (rtdma):
   // buffers pinned by rt_host_pin are copied directly; pageable ones go through
   // the scene's staging frame, host threads copying between it and the caller's
   // buffers on the host side of each DMA (hc / ht: where the DMAs read / write).
   const bool direct = rtdma::pinned(color, px * 4) && rtdma::pinned(t, px * 4);
   if (!direct && (rc = ensure_stage(s, px))) return rc;
-  uint32_t *hc = direct ? color : s->stage.c;
-  float *ht = direct ? t : s->stage.t;
+  uint32_t *hc = direct ? color : s->drop.stage.c;
+  float *ht = direct ? t : s->drop.stage.t;
   // colour and t move on two streams (two DMA engines, concurrent). Once a copy
   // is queued, every return -- an error included -- first waits for both
   // streams, so the caller may unpin or free its buffers as soon as the call
   // returns.
-  hipStream_t a = s->xs[0], b = s->xs[1];
+  hipStream_t a = s->drop.xs[0].s, b = s->drop.xs[1].s;
   rterr::stream_mark(a, "rt_render (render + colour copies)");
   rterr::stream_mark(b, "rt_render (t copies)");
   struct Drain {
@@ -302,48 +295,48 @@ int rt_render(rt_scene *s, const rt_render_params *p, uint32_t *color, float *t,
   // written whole (a cleared frame) or uploaded whole (tPrev), so the box
   // holds exactly the caller's values outside the hits.
   const bool boxed = !(flags & RT_FLAG_CLEAR) || (flags & RT_FLAG_HITS_ONLY);
-  if (!direct) s->stage.mark_dirty();  // (the zero-copy path's cleared staging frame is overwritten)
+  if (!direct) s->drop.stage.mark_dirty();  // (the zero-copy path's cleared staging frame is overwritten)
   if (!(flags & RT_FLAG_CLEAR)) {
     if (!direct) rth::copy_rect(hc, ht, color, t, W, 0, W - 1, 0, H - 1, 0);
-    HIP_TRY(hipMemcpyAsync(s->d_color, hc, px * 4, hipMemcpyHostToDevice, a));
-    HIP_TRY(hipMemcpyAsync(s->d_t, ht, px * 4, hipMemcpyHostToDevice, b));
-    HIP_TRY(hipEventRecord(s->xev, b));
-    HIP_TRY(hipStreamWaitEvent(a, s->xev, 0));
+    HIP_TRY(hipMemcpyAsync(s->fb.color.p, hc, px * 4, hipMemcpyHostToDevice, a));
+    HIP_TRY(hipMemcpyAsync(s->fb.t.p, ht, px * 4, hipMemcpyHostToDevice, b));
+    HIP_TRY(hipEventRecord(s->drop.xev.e, b));
+    HIP_TRY(hipStreamWaitEvent(a, s->drop.xev.e, 0));
   }
   if (g_render_fault.load() > 0) {
     g_render_fault.fetch_sub(1);
     return set_err(RT_E_DEVICE, "injected rt_render failure (rtx_render_inject_failure)");
   }
   if (boxed) {
-    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)s->d_hit_box, 0x7FFFFFFF, 4, a));
-    fa.hit_box = s->d_hit_box;
+    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)s->drop.hit_box.p, 0x7FFFFFFF, 4, a));
+    fa.hit_box = s->drop.hit_box.p;
   }
-  HIP_TRY(hipEventRecord(s->ev0, a));
+  HIP_TRY(hipEventRecord(s->fb.ev0.e, a));
   if ((rc = launch_render(s, fa, a))) return rc;
-  HIP_TRY(hipEventRecord(s->ev1, a));
+  HIP_TRY(hipEventRecord(s->fb.ev1.e, a));
   int32_t x0 = 0, x1 = W - 1, y0 = 0, y1 = H - 1;  // the region copied back
   if (!boxed) {
-    HIP_TRY(hipStreamWaitEvent(b, s->ev1, 0));
-    HIP_TRY(hipMemcpyAsync(ht, s->d_t, px * 4, hipMemcpyDeviceToHost, b));
-    HIP_TRY(hipMemcpyAsync(hc, s->d_color, px * 4, hipMemcpyDeviceToHost, a));
+    HIP_TRY(hipStreamWaitEvent(b, s->fb.ev1.e, 0));
+    HIP_TRY(hipMemcpyAsync(ht, s->fb.t.p, px * 4, hipMemcpyDeviceToHost, b));
+    HIP_TRY(hipMemcpyAsync(hc, s->fb.color.p, px * 4, hipMemcpyDeviceToHost, a));
   } else {
-    box_out_kernel<<<1, 64, 0, a>>>(s->d_hit_box, s->h_hit_box_dev, 4);
+    box_out_kernel<<<1, 64, 0, a>>>(s->drop.hit_box.p, s->drop.h_hit_box.dev, 4);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(a));
-    x0 = s->h_hit_box[0], x1 = -s->h_hit_box[1], y0 = s->h_hit_box[2], y1 = -s->h_hit_box[3];
+    x0 = s->drop.h_hit_box.h[0], x1 = -s->drop.h_hit_box.h[1], y0 = s->drop.h_hit_box.h[2], y1 = -s->drop.h_hit_box.h[3];
     if (x0 <= x1 && y0 <= y1) {  // else: no hit, nothing changed
-      HIP_TRY(hipStreamWaitEvent(b, s->ev1, 0));
+      HIP_TRY(hipStreamWaitEvent(b, s->fb.ev1.e, 0));
       const size_t off = (size_t)y0 * W + x0, rows = (size_t)(y1 - y0 + 1), w = (size_t)(x1 - x0 + 1);
       if (w * 2 > (size_t)W) {  // wide box: whole rows, one contiguous copy per buffer
         x0 = 0;
         x1 = W - 1;
-        HIP_TRY(hipMemcpyAsync(ht + (size_t)y0 * W, s->d_t + (size_t)y0 * W, rows * W * 4, hipMemcpyDeviceToHost, b));
-        HIP_TRY(hipMemcpyAsync(hc + (size_t)y0 * W, s->d_color + (size_t)y0 * W, rows * W * 4,
+        HIP_TRY(hipMemcpyAsync(ht + (size_t)y0 * W, s->fb.t.p + (size_t)y0 * W, rows * W * 4, hipMemcpyDeviceToHost, b));
+        HIP_TRY(hipMemcpyAsync(hc + (size_t)y0 * W, s->fb.color.p + (size_t)y0 * W, rows * W * 4,
                                hipMemcpyDeviceToHost, a));
       } else {
-        HIP_TRY(hipMemcpy2DAsync(ht + off, (size_t)W * 4, s->d_t + off, (size_t)W * 4, w * 4, rows,
+        HIP_TRY(hipMemcpy2DAsync(ht + off, (size_t)W * 4, s->fb.t.p + off, (size_t)W * 4, w * 4, rows,
                                  hipMemcpyDeviceToHost, b));
-        HIP_TRY(hipMemcpy2DAsync(hc + off, (size_t)W * 4, s->d_color + off, (size_t)W * 4, w * 4, rows,
+        HIP_TRY(hipMemcpy2DAsync(hc + off, (size_t)W * 4, s->fb.color.p + off, (size_t)W * 4, w * 4, rows,
                                  hipMemcpyDeviceToHost, a));
       }
     }
@@ -351,7 +344,7 @@ int rt_render(rt_scene *s, const rt_render_params *p, uint32_t *color, float *t,
   HIP_TRY(hipStreamSynchronize(a));
   HIP_TRY(hipStreamSynchronize(b));
   if (!direct && x0 <= x1 && y0 <= y1) rth::copy_rect(color, t, hc, ht, W, x0, x1, y0, y1, 0);
-  if (ms) HIP_TRY(hipEventElapsedTime(ms, s->ev0, s->ev1));
+  if (ms) HIP_TRY(hipEventElapsedTime(ms, s->fb.ev0.e, s->fb.ev1.e));
   return RT_OK;
 }
 

@@ -85,6 +85,10 @@ struct HostStage {
   // for another size (returns true), else left as the span resets kept it
   bool clear_for(int32_t W, int32_t H);
   void release();  // the owner has synchronised the streams that use it
+  // (so has whoever destroys it: a handle's destroy entry drains, then deletes)
+  ~HostStage() { release(); }
+  HostStage(const HostStage &) = delete;
+  HostStage &operator=(const HostStage &) = delete;
 
  private:
   unsigned flags_;

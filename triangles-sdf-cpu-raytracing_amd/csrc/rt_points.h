@@ -15,12 +15,14 @@
 #include "rt_host.h"
 #include "rt_layout.h"
 #include "rt_math.h"
+#include "rt_mem.h"
 
+// rt_sdf_mesh_destroy makes `device` current, drains qs and deletes: after
+// that the order in which the owners (rt_mem.h) release is immaterial.
 struct rt_sdf_mesh {
   rth::SdfMeshHost host;
-  rtl::GNode *d_nodes = nullptr;
-  float4 *d_tri = nullptr;
-  float4 *d_pn = nullptr;
+  rtmem::DevArray<rtl::GNode> d_nodes;
+  rtmem::DevArray<float4> d_tri, d_pn;
   uint32_t root = rtl::kInvalidChild;
   int32_t stack_cap = 0;
   int device = 0;
@@ -28,9 +30,9 @@ struct rt_sdf_mesh {
   std::vector<uint8_t> oct_nodes;
   // point queries: the handle's own non-blocking stream, and pinned host /
   // device staging for up to q_cap points, reused across calls
-  hipStream_t qs = nullptr;
-  float *h_stage = nullptr;  // q_cap * 4 floats: points (3 per point), then distances
-  float *d_p3 = nullptr, *d_out = nullptr;
+  rtmem::Stream qs;
+  rtmem::Pinned<float> h_stage;  // q_cap * 4 floats: points (3 per point), then distances
+  rtmem::DevArray<float> d_p3, d_out;
   int64_t q_cap = 0;
   // RT_MESH_DYNAMIC only (rt_sdf_mesh_update_vertices*, rt_sdf_refit.hip): the
   // creation topology on the device, scratch, and the event every update
@@ -39,12 +41,11 @@ struct rt_sdf_mesh {
   bool dynamic = false;
   int64_t nverts = 0, ntri = 0;
   uint32_t n_wverts = 0, n_wedges = 0;
-  uint32_t *d_idx = nullptr, *d_weld = nullptr, *d_tri_edge = nullptr;
-  uint32_t *d_v_off = nullptr, *d_v_inc = nullptr, *d_e_off = nullptr, *d_e_inc = nullptr;
-  float4 *d_vstage = nullptr, *d_fn = nullptr, *d_vn = nullptr, *d_en = nullptr;
-  double *d_ang = nullptr;
+  rtmem::DevArray<uint32_t> d_idx, d_weld, d_tri_edge, d_v_off, d_v_inc, d_e_off, d_e_inc;
+  rtmem::DevArray<float4> d_vstage, d_fn, d_vn, d_en;
+  rtmem::DevArray<double> d_ang;  // 3 per triangle
   std::vector<uint32_t> level_first;
-  hipEvent_t updated = nullptr;
+  rtmem::Event updated;
   int64_t dev_bytes = 0;  // what the handle's mesh arrays hold on the device (rt_sdf_mesh_device_bytes)
 };
 
@@ -62,7 +63,7 @@ struct SdfDev {
   uint32_t root;
 };
 
-inline SdfDev dev_of(const rt_sdf_mesh *m) { return SdfDev{m->d_nodes, m->d_tri, m->d_pn, m->root}; }
+inline SdfDev dev_of(const rt_sdf_mesh *m) { return SdfDev{m->d_nodes.p, m->d_tri.p, m->d_pn.p, m->root}; }
 
 // Dynamic LDS of one 64-lane workgroup: stack_cap entries of (box distance^2,
 // child word) per lane, lane-interleaved.

@@ -3,6 +3,13 @@
 // (creation, update, destruction, the device views of a scene), rt_device.hip
 // (the renderer and the ray queries) and rt_dropin.hip (rt_render on host
 // buffers).
+//
+// A scene is grouped by what owns what. Its description is plain data
+// (rts::Common and one struct per geometry kind): rt_scene_replicate assigns
+// it. Everything on the device, in pinned host memory, every event and every
+// stream sits in an owner of rt_mem.h inside one of the owning parts below,
+// each next to the state that says what it holds. No part lists what it has
+// to free: rt_scene_destroy drains the scene's own streams and deletes.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -14,15 +21,25 @@
 #include "rt_frame.h"
 #include "rt_instances.h"
 #include "rt_layout.h"
+#include "rt_mem.h"
 #include "rt_scenes.h"
 
-struct rt_scene {
+namespace rts {
+
+// ---- the description: plain, assignable ------------------------------------
+struct Common {
   int kind = 0;
-  int device = 0;
   int32_t maxd = 1;  // LDS stack frames the kernel is instantiated for
-  // mesh
-  rtl::GNode *d_nodes = nullptr;
-  rtl::GTri *d_tris = nullptr;
+  rtd::PlaneDev plane{};
+  uint64_t version = 0;   // counts the updates (rt_multi re-copies its replicas when it moves)
+  int64_t dev_bytes = 0;  // rt_scene_device_bytes: the geometry, the dynamic part and the instanced tables
+  // diagnostic switches
+  bool sched_on = true;  // false renders in plain blockIdx order (rts::Schedule)
+  bool coop = true;      // mesh primary rays: cooperative tail (rtx_set_coop)
+  bool pump_on = false;  // primary-ray batches on the ray pump (rtx_set_pump)
+};
+
+struct MeshDesc {
   uint32_t root = rtl::kInvalidChild;
   float root_box[6] = {0, 0, 0, 0, 0, 0};
   // the root node's eight child boxes (xMin xMax yMin yMax zMin zMax each; an
@@ -31,96 +48,133 @@ struct rt_scene {
   int64_t host_nodes = 0, host_inner = 0;
   uint32_t n_inner = 0;  // inner nodes on the device
   float dmax2 = 0.0f;    // MeshDev::dmax2 (mesh_dmax2; 0: every ray takes the division)
-  int32_t bvh_depth = 0;
-  uint32_t n_tris = 0;   // triangle slots in d_tris (8 zero triangles follow)
+  int32_t depth = 0;
+  uint32_t n_tris = 0;       // triangle slots in Geometry::tris (8 zero triangles follow)
   uint32_t root_nchild = 0;  // children of an inner root (slots 0 .. root_nchild-1)
-  // a mesh created with RT_MESH_DYNAMIC (rt_scene_update_vertices*): the
-  // creation index array and a vertex staging buffer on the device, the first
-  // node index of every depth level (+ the node count), the edge-bound word of
-  // tri_edge_bound_kernel and the pinned host words the update reads back
-  // (48 root child box floats, then the edge bound)
-  bool dynamic = false;
-  int64_t nverts = 0;
-  uint32_t *d_idx = nullptr;
-  float *d_vstage = nullptr;
-  uint32_t *d_edge = nullptr;
-  uint32_t *h_refit = nullptr;
-  std::vector<uint32_t> level_first;
-  int64_t dyn_bytes = 0;  // what `dynamic` added to dev_bytes
-  uint64_t version = 0;   // counts the updates (rt_multi re-copies its replicas when it moves)
-  // grid
-  float *d_vals = nullptr;
+};
+
+struct GridDesc {
   uint32_t size[3] = {0, 0, 0};
-  bool grid_bricked = false;  // device layout (rt_scenes.h GridDev): bricked, or the reference's linear
-  // octree
-  rtl::OctWord *d_child = nullptr;
-  rtl::OctVals *d_ovals = nullptr;
-  int32_t oct_depth = 0;
-  // instanced (RT_SCENE_INSTANCED): the instance records and the table of the
-  // bottom-level scenes' MeshDev on the device; the scenes themselves (not
-  // owned) and the update counter each table entry was written from. Nothing
-  // here depends on a pose.
-  rti::InstRec *d_inst = nullptr;
-  rtd::MeshDev *d_blas = nullptr;
-  int32_t ninst = 0;
+  bool bricked = false;  // device layout (rt_scenes.h GridDev): bricked, or the reference's linear
+};
+
+struct OctDesc {
+  int32_t depth = 0;
+};
+
+// ---- the owning parts -------------------------------------------------------
+// The arrays of the scene's kind; the others stay empty. Each remembers its
+// size (with the triangles' zero pad), which is what a replica copies.
+struct Geometry {
+  rtmem::DevArray<rtl::GNode> nodes;  // mesh
+  rtmem::DevArray<rtl::GTri> tris;
+  rtmem::DevArray<float> vals;  // grid
+  rtmem::DevArray<rtl::OctWord> child;  // octree
+  rtmem::DevArray<rtl::OctVals> ovals;
+};
+
+// A mesh created with RT_MESH_DYNAMIC (rt_scene_update_vertices*): the
+// creation index array and a vertex staging buffer on the device, the first
+// node index of every depth level (+ the node count), the edge-bound word of
+// tri_edge_bound_kernel and the pinned host words the update reads back
+// (48 root child box floats, then the edge bound).
+struct Dynamic {
+  bool on = false;
+  int64_t nverts = 0;
+  rtmem::DevArray<uint32_t> idx;
+  rtmem::DevArray<float> vstage;
+  rtmem::DevArray<uint32_t> edge;
+  rtmem::Pinned<uint32_t> h_refit;
+  std::vector<uint32_t> level_first;
+  int64_t bytes = 0;  // what this part added to Common::dev_bytes
+};
+
+// RT_SCENE_INSTANCED: the instance records and the table of the bottom-level
+// scenes' MeshDev on the device; the scenes themselves (not owned) and the
+// update counter each table entry was written from. Nothing here depends on a
+// pose.
+struct Instanced {
+  rtmem::DevArray<rti::InstRec> recs;
+  rtmem::DevArray<rtd::MeshDev> tab;
+  int32_t n = 0;
   std::vector<rt_scene *> blas;
   std::vector<uint64_t> blas_seen;
   // a mixed scene (rt_scene_create_instanced_any with a grid or an octree among
-  // its bottom-level scenes): the table of tagged records instead of d_blas,
-  // which stays NULL (rt_instances_mixed.hip)
-  rti::BlasRec *d_mixed = nullptr;
+  // its bottom-level scenes): the table of tagged records instead of tab,
+  // which stays empty (rt_instances_mixed.hip)
+  rtmem::DevArray<rti::BlasRec> mixed;
   // created with RT_INSTANCED_TLAS: the top-level tree (2 * tlas_leaves nodes,
   // rt_tlas.h) and the object-to-world matrices (12 floats per instance) its
   // leaves are recomputed from when a BLAS's root box moves. Both live on the
   // device only: the host keeps nothing that depends on a pose.
-  rtt::TNode *d_tlas = nullptr;
-  float *d_xform = nullptr;
+  rtmem::DevArray<rtt::TNode> tlas;
+  rtmem::DevArray<float> xform;
   int32_t tlas_leaves = 0;
-  rtd::PlaneDev plane{};
-  int64_t dev_bytes = 0;
-  // cached buffers for host-buffer entry points
-  uint32_t *d_color = nullptr;
-  float *d_t = nullptr;
-  size_t fb_cap = 0;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  hipEvent_t ev_host = nullptr;  // rt_render's pageable cleared frame: the spans are on the host
-  hipStream_t xs[2] = {nullptr, nullptr};  // rt_render: colour / t copy streams (render on xs[0])
-  hipEvent_t xev = nullptr;
-  // rt_render: FrameArgs::hit_box of its frame (4 words) and a pinned,
-  // mapped host copy (h_hit_box_dev: its device address, box_out_kernel)
-  int32_t *d_hit_box = nullptr;
-  int32_t *h_hit_box = nullptr;
-  int32_t *h_hit_box_dev = nullptr;
+};
+
+// The cached device frame of the host-buffer entry points, for cap pixels,
+// and their timing events.
+struct Frame {
+  rtmem::DevArray<uint32_t> color;
+  rtmem::DevArray<float> t;
+  size_t cap = 0;
+  rtmem::Event ev0, ev1;
+};
+
+// Cost-ordered block schedule (see launch_render), double-buffered: frame k
+// of the scene's one-frame kernel records its tiles' costs into cost[k & 1]
+// and dispatches in the order order[k & 1] that frame k - 2's costs gave;
+// frame k's own order is computed by order_kernel on the side stream os as
+// soon as frame k is done (frame_ev), beside frame k + 1, and ord_ev[k & 1]
+// marks it done. key[b] = the grid (gx << 16 | gy) whose order order[b] holds
+// (0: none).
+struct Schedule {
+  rtmem::DevArray<uint32_t> cost[2], order[2];
+  uint32_t key[2] = {0, 0};
+  bool rec[2] = {false, false};
+  int par = 0;
+  uint32_t cap = 0;
+  hipStream_t last_stream = nullptr;  // stream of the previous frame (scheduled or not)
+  rtmem::Stream os;                   // side stream of the order kernels
+  rtmem::Event ord_ev[2], frame_ev;
+};
+
+// rt_render on host buffers (rt_dropin.hip).
+struct Dropin {
+  rtmem::Stream xs[2];  // colour / t copy streams (render on xs[0])
+  rtmem::Event xev;
+  rtmem::Event ev_host;  // the pageable cleared frame: the spans are on the host
+  // FrameArgs::hit_box of its frame (4 words) and a pinned, mapped host copy
+  // (box_out_kernel)
+  rtmem::DevArray<int32_t> hit_box;
+  rtmem::Pinned<int32_t> h_hit_box;
   // the pageable zero-copy path: FrameArgs::row_span (2 words per row) and its
   // pinned, mapped host copy, for span_cap rows
-  int32_t *d_row_span = nullptr;
-  int32_t *h_row_span = nullptr;
-  int32_t *h_row_span_dev = nullptr;
+  rtmem::DevArray<int32_t> row_span;
+  rtmem::Pinned<int32_t> h_row_span;
   int32_t span_cap = 0;
-  // rt_render's staging frame for a cleared frame on pageable buffers: pinned
-  // host memory the kernel stores its hits into (zero-copy), kept cleared
+  // the staging frame for a cleared frame on pageable buffers: pinned host
+  // memory the kernel stores its hits into (zero-copy), kept cleared
   rtdma::HostStage stage{hipHostMallocDefault};
-  // cost-ordered block schedule (see launch_render), double-buffered: frame k
-  // of the scene's one-frame kernel records its tiles' costs into d_cost[k & 1]
-  // and dispatches in the order d_order[k & 1] that frame k - 2's costs gave;
-  // frame k's own order is computed by order_kernel on the side stream
-  // sched_os as soon as frame k is done (frame_ev), beside frame k + 1, and
-  // ord_ev[k & 1] marks it done. sched_key[b] = the grid (gx << 16 | gy) whose
-  // order d_order[b] holds (0: none). sched_on = false renders in plain
-  // blockIdx order
-  uint32_t *d_cost[2] = {nullptr, nullptr};
-  uint32_t *d_order[2] = {nullptr, nullptr};
-  uint32_t sched_key[2] = {0, 0};
-  bool ord_rec[2] = {false, false};
-  int sched_par = 0;
-  uint32_t sched_cap = 0;
-  bool sched_on = true;
-  bool coop = true;  // mesh primary rays: cooperative tail (rtx_set_coop)
-  hipStream_t last_stream = nullptr;   // stream of the previous frame (scheduled or not)
-  hipStream_t sched_os = nullptr;      // side stream of the order kernels
-  hipEvent_t ord_ev[2] = {nullptr, nullptr};
-  hipEvent_t frame_ev = nullptr;
-  bool pump_on = false;  // primary-ray batches on the ray pump (rtx_set_pump)
+};
+
+}  // namespace rts
+
+// rt_scene_destroy makes `device` current and drains drop.xs and sched.os
+// before it deletes; after that nothing of the scene is in use, so the order
+// in which the members below release is immaterial.
+struct rt_scene {
+  int device = 0;
+  rts::Common info;
+  rts::MeshDesc mesh;
+  rts::GridDesc grid;
+  rts::OctDesc oct;
+  rts::Geometry geo;
+  rts::Dynamic dyn;
+  rts::Instanced inst;
+  rts::Frame fb;
+  rts::Schedule sched;
+  rts::Dropin drop;
 };
 
 namespace rti {

@@ -32,9 +32,9 @@ uint64_t grid_bricked_samples(const uint32_t size[3]) {
   return (uint64_t)grid_bricks(size[0]) * grid_bricks(size[1]) * grid_bricks(size[2]) * 64u;
 }
 
-// device samples of a grid scene (s->grid_bricked picks the layout)
+// device samples of a grid scene (s->grid.bricked picks the layout)
 uint64_t grid_samples(const rt_scene *s) {
-  return s->grid_bricked ? grid_bricked_samples(s->size) : (uint64_t)s->size[0] * s->size[1] * s->size[2];
+  return s->grid.bricked ? grid_bricked_samples(s->grid.size) : (uint64_t)s->grid.size[0] * s->grid.size[1] * s->grid.size[2];
 }
 
 // diagnostic (rtx_set_grid_force): bit 0 = grids created from now on take the
@@ -52,16 +52,16 @@ GridDev grid_dev(const rt_scene *s) {
   // 4 GiB (a grid of exactly 2^32 bytes would put its last sample past a
   // saturated num_records) -- larger ones take the 64-bit address path
   const uint32_t bytes = 4 * n < (1ull << 32) ? (uint32_t)(4 * n) : 0u;
-  if (!s->grid_bricked) return GridDev{s->d_vals, s->size[0], s->size[1], s->size[2], s->size[2],
-                                       s->size[1] * s->size[2], bytes};
-  const uint32_t ys = grid_bricks(s->size[2]) * 64u;
-  return GridDev{s->d_vals, s->size[0], s->size[1], s->size[2], ys, grid_bricks(s->size[1]) * ys, bytes};
+  if (!s->grid.bricked) return GridDev{s->geo.vals.p, s->grid.size[0], s->grid.size[1], s->grid.size[2], s->grid.size[2],
+                                       s->grid.size[1] * s->grid.size[2], bytes};
+  const uint32_t ys = grid_bricks(s->grid.size[2]) * 64u;
+  return GridDev{s->geo.vals.p, s->grid.size[0], s->grid.size[1], s->grid.size[2], ys, grid_bricks(s->grid.size[1]) * ys, bytes};
 }
 
 int grid_mode(const rt_scene *s, const GridDev &gd) {
   // buffer mode: 32-bit byte offsets and 24-bit stride multiplies (grid_mul)
   const bool buf = gd.bytes != 0 && gd.xs < (1u << 24) && gd.ys < (1u << 24) && !(g_grid_force & 2);
-  return (buf ? kGridBuf : 0) | (s->grid_bricked ? kGridBricked : 0);
+  return (buf ? kGridBuf : 0) | (s->grid.bricked ? kGridBricked : 0);
 }
 
 }  // namespace rti
@@ -87,32 +87,32 @@ __global__ __launch_bounds__(256) void brick_kernel(const float *__restrict__ sr
 namespace rti {
 
 MeshDev mesh_dev(const rt_scene *s) {
-  MeshDev m{s->d_nodes, s->d_tris, s->root, {}, s->coop, s->dmax2};
-  for (int k = 0; k < 6; ++k) m.rbox[k] = s->root_box[k];
+  MeshDev m{s->geo.nodes.p, s->geo.tris.p, s->mesh.root, {}, s->info.coop, s->mesh.dmax2};
+  for (int k = 0; k < 6; ++k) m.rbox[k] = s->mesh.root_box[k];
   return m;
 }
 
 // the entries that render frames or copy a scene take no instanced scene
 int no_instanced(const rt_scene *s, const char *who) {
-  if (s && s->kind == RT_SCENE_INSTANCED)
+  if (s && s->info.kind == RT_SCENE_INSTANCED)
     return set_err(RT_E_STATE, std::string(who) + ": not available for an instanced scene");
   return RT_OK;
 }
 
 int instanced_sync(rt_scene *s, hipStream_t stream) {
-  for (size_t j = 0; j < s->blas.size(); ++j) {
+  for (size_t j = 0; j < s->inst.blas.size(); ++j) {
     // (only a dynamic mesh's version ever moves: SDF scenes are immutable)
-    if (s->blas[j]->version == s->blas_seen[j]) continue;
+    if (s->inst.blas[j]->info.version == s->inst.blas_seen[j]) continue;
     // (a mixed table: the mesh view of the record; kind and variant stay)
-    rtd::MeshDev *entry = s->d_mixed ? &(s->d_mixed + j)->mesh : s->d_blas + j;
-    if (int rc = rti::blas_entry_launch(entry, mesh_dev(s->blas[j]), stream)) return rc;
-    s->blas_seen[j] = s->blas[j]->version;
-    if (!s->d_tlas) continue;
+    rtd::MeshDev *entry = s->inst.mixed.p ? &(s->inst.mixed.p + j)->mesh : s->inst.tab.p + j;
+    if (int rc = rti::blas_entry_launch(entry, mesh_dev(s->inst.blas[j]), stream)) return rc;
+    s->inst.blas_seen[j] = s->inst.blas[j]->info.version;
+    if (!s->inst.tlas.p) continue;
     // its root box moved: that BLAS's leaves of the top-level tree and the
     // tree above them, behind the entry
     const rti::TlasArgs t = rti::tlas_args(s);
-    if (int rc = s->d_mixed ? rti::mixed_boxes_launch(t, s->d_mixed, 0, s->ninst, nullptr, (int32_t)j, stream)
-                            : rti::tlas_boxes_launch(t, 0, s->ninst, nullptr, (int32_t)j, stream))
+    if (int rc = s->inst.mixed.p ? rti::mixed_boxes_launch(t, s->inst.mixed.p, 0, s->inst.n, nullptr, (int32_t)j, stream)
+                            : rti::tlas_boxes_launch(t, 0, s->inst.n, nullptr, (int32_t)j, stream))
       return rc;
     if (int rc = rti::tlas_refit_launch(t, stream)) return rc;
   }
@@ -120,7 +120,7 @@ int instanced_sync(rt_scene *s, hipStream_t stream) {
 }
 
 rti::TlasArgs tlas_args(const rt_scene *s) {
-  return rti::TlasArgs{s->d_tlas, s->tlas_leaves, s->ninst, s->d_inst, s->d_xform, s->d_blas};
+  return rti::TlasArgs{s->inst.tlas.p, s->inst.tlas_leaves, s->inst.n, s->inst.recs.p, s->inst.xform.p, s->inst.tab.p};
 }
 
 }  // namespace rti
@@ -187,34 +187,9 @@ int new_scene(rt_scene **out) {
   HIP_TRY(hipGetDevice(&dev));
   rt_scene *s = new rt_scene();
   s->device = dev;
-  s->plane.on = 0;
-  s->plane.n = f3{0.0f, 1.0f, 0.0f};
+  s->info.plane.on = 0;
+  s->info.plane.n = f3{0.0f, 1.0f, 0.0f};
   *out = s;
-  return RT_OK;
-}
-
-// upload + `pad` zeroed trailing elements (kernels may read past the end).
-template <class T>
-int upload_padded(T **dst, const T *src, size_t n, size_t pad, int64_t &bytes) {
-  HIP_TRY(hipMalloc(dst, (n + pad) * sizeof(T)));
-  HIP_TRY(hipMemset(*dst, 0, (n + pad) * sizeof(T)));
-  if (n) HIP_TRY(rtdma::h2d(*dst, src, n * sizeof(T), nullptr));
-  bytes += (int64_t)((n + pad) * sizeof(T));
-  return RT_OK;
-}
-
-template <class T>
-int upload(T **dst, const T *src, size_t n, int64_t &bytes) {
-  if (n == 0) n = 1;  // keep a valid pointer
-  HIP_TRY(hipMalloc(dst, n * sizeof(T)));
-  if (src) HIP_TRY(rtdma::h2d(*dst, src, n * sizeof(T), nullptr));
-  bytes += (int64_t)(n * sizeof(T));
-  return RT_OK;
-}
-
-// the pinned host words a dynamic mesh's update reads its constants into
-int dynamic_host_words(rt_scene *s) {
-  HIP_TRY(hipHostMalloc((void **)&s->h_refit, 64 * sizeof(uint32_t), hipHostMallocDefault));
   return RT_OK;
 }
 
@@ -278,19 +253,19 @@ float dmax2_of(uint32_t edge_bits) {
                                                           : std::nextafter((float)r2, 0.0f);
 }
 int mesh_dmax2(rt_scene *s, uint32_t n_tris) {
-  s->dmax2 = 0.0f;
+  s->mesh.dmax2 = 0.0f;
   if (n_tris == 0) return RT_OK;
-  uint32_t *d = nullptr, h = 0;
-  HIP_TRY(hipMalloc(&d, 4));
-  hipError_t e = hipMemset(d, 0, 4);
+  rtmem::DevArray<uint32_t> d;
+  uint32_t h = 0;
+  if (int rc = d.alloc(1)) return rc;
+  hipError_t e = hipMemset(d.p, 0, 4);
   if (e == hipSuccess) {
-    tri_edge_bound_kernel<<<(n_tris + 255) / 256, 256>>>(s->d_tris, n_tris, d);
+    tri_edge_bound_kernel<<<(n_tris + 255) / 256, 256>>>(s->geo.tris.p, n_tris, d.p);
     e = hipGetLastError();
   }
-  if (e == hipSuccess) e = hipMemcpy(&h, d, 4, hipMemcpyDeviceToHost);
-  HIP_NOTE(hipFree(d));
+  if (e == hipSuccess) e = hipMemcpy(&h, d.p, 4, hipMemcpyDeviceToHost);
   if (e != hipSuccess) return set_err(RT_E_DEVICE, std::string("triangle edge bound: ") + hipGetErrorString(e));
-  s->dmax2 = dmax2_of(h);
+  s->mesh.dmax2 = dmax2_of(h);
   return RT_OK;
 }
 
@@ -310,41 +285,42 @@ int rt_scene_create_mesh_ex(const float *vpos4, int64_t nverts, const uint32_t *
   if (rc) return rc;
   rt_scene *s;
   if ((rc = new_scene(&s))) return rc;
-  s->kind = RT_SCENE_MESH;
-  s->maxd = maxd;
-  s->root = b.root_word;
-  std::memcpy(s->root_box, b.root_box, sizeof(s->root_box));
+  s->info.kind = RT_SCENE_MESH;
+  s->info.maxd = maxd;
+  s->mesh.root = b.root_word;
+  std::memcpy(s->mesh.root_box, b.root_box, sizeof(s->mesh.root_box));
   if (!(b.root_word & rtl::kLeafBit) && b.root_word < b.nodes.size())
-    std::memcpy(s->root_child, b.nodes[b.root_word].box, sizeof(s->root_child));
-  s->host_nodes = b.host_nodes;
-  s->host_inner = b.host_inner;
-  s->bvh_depth = b.max_depth;
-  s->n_inner = (uint32_t)b.nodes.size();
+    std::memcpy(s->mesh.root_child, b.nodes[b.root_word].box, sizeof(s->mesh.root_child));
+  s->mesh.host_nodes = b.host_nodes;
+  s->mesh.host_inner = b.host_inner;
+  s->mesh.depth = b.max_depth;
+  s->mesh.n_inner = (uint32_t)b.nodes.size();
   if (b.dev_tris.p) {  // the device builder left the triangles on the device (with the zero pad)
-    s->dev_bytes += (int64_t)b.dev_tris.bytes;
-    s->d_tris = static_cast<rtl::GTri *>(b.dev_tris.take());
+    s->info.dev_bytes += (int64_t)b.dev_tris.bytes;
+    s->geo.tris.adopt(b.dev_tris);
   }
-  if ((rc = upload(&s->d_nodes, b.nodes.data(), b.nodes.size(), s->dev_bytes)) ||
-      (!s->d_tris && (rc = upload_padded(&s->d_tris, b.tris.data(), b.tris.size(), 8, s->dev_bytes))) ||
+  if ((rc = s->geo.nodes.upload(b.nodes.data(), b.nodes.size(), s->info.dev_bytes)) ||
+      (!s->geo.tris.p && (rc = s->geo.tris.upload_padded(b.tris.data(), b.tris.size(), 8, s->info.dev_bytes))) ||
       (rc = mesh_dmax2(s, b.n_tris))) {
     rt_scene_destroy(s);
     return rc;
   }
-  s->n_tris = b.n_tris;
+  s->mesh.n_tris = b.n_tris;
   if (!b.nodes.empty())
-    for (uint32_t w : b.nodes[0].child) s->root_nchild += w != rtl::kInvalidChild;
+    for (uint32_t w : b.nodes[0].child) s->mesh.root_nchild += w != rtl::kInvalidChild;
   if (flags & RT_MESH_DYNAMIC) {
-    const int64_t before = s->dev_bytes;
-    s->nverts = nverts;
-    s->level_first = rth::bvh_level_first(b.nodes);
-    if ((rc = upload(&s->d_idx, idx, (size_t)nidx, s->dev_bytes)) ||
-        (rc = upload(&s->d_vstage, (const float *)nullptr, 4 * (size_t)nverts, s->dev_bytes)) ||
-        (rc = upload(&s->d_edge, (const uint32_t *)nullptr, 1, s->dev_bytes)) || (rc = dynamic_host_words(s))) {
+    const int64_t before = s->info.dev_bytes;
+    s->dyn.nverts = nverts;
+    s->dyn.level_first = rth::bvh_level_first(b.nodes);
+    if ((rc = s->dyn.idx.upload(idx, (size_t)nidx, s->info.dev_bytes)) ||
+        (rc = s->dyn.vstage.upload(nullptr, 4 * (size_t)nverts, s->info.dev_bytes)) ||
+        (rc = s->dyn.edge.upload(nullptr, 1, s->info.dev_bytes)) ||
+        (rc = s->dyn.h_refit.alloc(64, hipHostMallocDefault))) {
       rt_scene_destroy(s);
       return rc;
     }
-    s->dyn_bytes = s->dev_bytes - before;
-    s->dynamic = true;
+    s->dyn.bytes = s->info.dev_bytes - before;
+    s->dyn.on = true;
   }
   *out = s;
   return RT_OK;
@@ -354,34 +330,34 @@ int rt_scene_create_mesh_ex(const float *vpos4, int64_t nverts, const uint32_t *
 // device) is read in stream order on `stream`; returns after the constants
 // are back on the host.
 static int update_vertices_device(rt_scene *s, const float *d_vpos4, hipStream_t st) {
-  const rti::RefitArgs a{s->d_nodes, s->d_tris, s->root, d_vpos4, s->d_idx, s->level_first.data(),
-                         s->level_first.empty() ? 0 : (int32_t)s->level_first.size() - 1};
+  const rti::RefitArgs a{s->geo.nodes.p, s->geo.tris.p, s->mesh.root, d_vpos4, s->dyn.idx.p, s->dyn.level_first.data(),
+                         s->dyn.level_first.empty() ? 0 : (int32_t)s->dyn.level_first.size() - 1};
   if (int rc = rti::refit_launch(a, st)) return rc;
   // the constants the host keeps: the triangles' edge bound (dmax2) and, for
   // an inner root, its eight child boxes (root_child, root_box)
   const bool inner = a.levels > 0;
-  HIP_TRY(hipMemsetAsync(s->d_edge, 0, 4, st));
-  if (s->n_tris) {
-    tri_edge_bound_kernel<<<(s->n_tris + 255) / 256, 256, 0, st>>>(s->d_tris, s->n_tris, s->d_edge);
+  HIP_TRY(hipMemsetAsync(s->dyn.edge.p, 0, 4, st));
+  if (s->mesh.n_tris) {
+    tri_edge_bound_kernel<<<(s->mesh.n_tris + 255) / 256, 256, 0, st>>>(s->geo.tris.p, s->mesh.n_tris, s->dyn.edge.p);
     HIP_TRY(hipGetLastError());
   }
-  if (inner) HIP_TRY(hipMemcpyAsync(s->h_refit, s->d_nodes[0].box, 192, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(s->h_refit + 48, s->d_edge, 4, hipMemcpyDeviceToHost, st));
+  if (inner) HIP_TRY(hipMemcpyAsync(s->dyn.h_refit.h, s->geo.nodes.p[0].box, 192, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(s->dyn.h_refit.h + 48, s->dyn.edge.p, 4, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   if (inner) {
-    std::memcpy(s->root_child, s->h_refit, 192);
+    std::memcpy(s->mesh.root_child, s->dyn.h_refit.h, 192);
     const float inf = std::numeric_limits<float>::infinity();
     float mn[3] = {inf, inf, inf}, mx[3] = {-inf, -inf, -inf};
-    for (uint32_t c = 0; c < s->root_nchild; ++c) {  // bvh_layout's root box: the union over c = 0 .. nchild-1
+    for (uint32_t c = 0; c < s->mesh.root_nchild; ++c) {  // bvh_layout's root box: the union over c = 0 .. nchild-1
       for (int k = 0; k < 3; ++k) {
-        mn[k] = std::min(mn[k], s->root_child[6 * c + 2 * k]);
-        mx[k] = std::max(mx[k], s->root_child[6 * c + 2 * k + 1]);
+        mn[k] = std::min(mn[k], s->mesh.root_child[6 * c + 2 * k]);
+        mx[k] = std::max(mx[k], s->mesh.root_child[6 * c + 2 * k + 1]);
       }
     }
-    for (int k = 0; k < 3; ++k) { s->root_box[k] = mn[k]; s->root_box[3 + k] = mx[k]; }
+    for (int k = 0; k < 3; ++k) { s->mesh.root_box[k] = mn[k]; s->mesh.root_box[3 + k] = mx[k]; }
   }
-  s->dmax2 = s->n_tris ? dmax2_of(s->h_refit[48]) : 0.0f;
-  ++s->version;
+  s->mesh.dmax2 = s->mesh.n_tris ? dmax2_of(s->dyn.h_refit.h[48]) : 0.0f;
+  ++s->info.version;
   return RT_OK;
 }
 
@@ -393,10 +369,10 @@ int rt_scene_create_grid(const uint32_t size[3], const float *values, rt_scene *
   rt_scene *s;
   int rc = new_scene(&s);
   if (rc) return rc;
-  s->kind = RT_SCENE_GRID;
-  s->size[0] = size[0]; s->size[1] = size[1]; s->size[2] = size[2];
+  s->info.kind = RT_SCENE_GRID;
+  s->grid.size[0] = size[0]; s->grid.size[1] = size[1]; s->grid.size[2] = size[2];
   if ((uint64_t)n * 4 <= kGridLinearMaxBytes && !(g_grid_force & 1)) {  // fits one XCD's L2: the reference layout
-    if ((rc = upload(&s->d_vals, values, (size_t)n, s->dev_bytes))) {
+    if ((rc = s->geo.vals.upload(values, (size_t)n, s->info.dev_bytes))) {
       rt_scene_destroy(s);
       return rc;
     }
@@ -408,21 +384,19 @@ int rt_scene_create_grid(const uint32_t size[3], const float *values, rt_scene *
     rt_scene_destroy(s);
     return set_err(RT_E_INVALID, "bad grid size");
   }
-  s->grid_bricked = true;
-  float *d_ref = nullptr;  // the reference array, staged for the device-side bricking
-  if ((rc = upload(&d_ref, values, (size_t)n, s->dev_bytes)) ||
-      (rc = upload(&s->d_vals, (const float *)nullptr, (size_t)nb, s->dev_bytes))) {
-    if (d_ref) HIP_NOTE(hipFree(d_ref));
+  s->grid.bricked = true;
+  rtmem::DevArray<float> ref;  // the reference array, staged for the device-side bricking
+  int64_t staged = 0;          // (not part of the scene's device bytes)
+  if ((rc = ref.upload(values, (size_t)n, staged)) ||
+      (rc = s->geo.vals.upload(nullptr, (size_t)nb, s->info.dev_bytes))) {
     rt_scene_destroy(s);
     return rc;
   }
-  s->dev_bytes -= (int64_t)(n * sizeof(float));
-  brick_kernel<<<(unsigned)((nb + 255) / 256), 256>>>(d_ref, s->d_vals, size[0], size[1], size[2], nb);
-  const hipError_t e1 = hipGetLastError(), e2 = hipDeviceSynchronize(), e3 = hipFree(d_ref);
-  if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess) {
+  brick_kernel<<<(unsigned)((nb + 255) / 256), 256>>>(ref.p, s->geo.vals.p, size[0], size[1], size[2], nb);
+  const hipError_t e1 = hipGetLastError(), e2 = hipDeviceSynchronize();
+  if (e1 != hipSuccess || e2 != hipSuccess) {
     rt_scene_destroy(s);
-    return set_err(RT_E_DEVICE, std::string("grid bricking: ") +
-                                    hipGetErrorString(e1 != hipSuccess ? e1 : e2 != hipSuccess ? e2 : e3));
+    return set_err(RT_E_DEVICE, std::string("grid bricking: ") + hipGetErrorString(e1 != hipSuccess ? e1 : e2));
   }
   *out = s;
   return RT_OK;
@@ -438,11 +412,11 @@ int rt_scene_create_octree(const void *nodes36, int64_t count, rt_scene **out) {
   if (rc) return rc;
   rt_scene *s;
   if ((rc = new_scene(&s))) return rc;
-  s->kind = RT_SCENE_OCTREE;
-  s->maxd = maxd;
-  s->oct_depth = g.max_depth;
-  if ((rc = upload(&s->d_child, g.child.data(), g.child.size(), s->dev_bytes)) ||
-      (rc = upload(&s->d_ovals, g.vals.data(), g.vals.size(), s->dev_bytes))) {
+  s->info.kind = RT_SCENE_OCTREE;
+  s->info.maxd = maxd;
+  s->oct.depth = g.max_depth;
+  if ((rc = s->geo.child.upload(g.child.data(), g.child.size(), s->info.dev_bytes)) ||
+      (rc = s->geo.ovals.upload(g.vals.data(), g.vals.size(), s->info.dev_bytes))) {
     rt_scene_destroy(s);
     return rc;
   }
@@ -461,42 +435,27 @@ int rt_scene_replicate(const rt_scene *src, int device, rt_scene **out) {
   HIP_TRY(hipGetDevice(&prev));
   HIP_TRY(hipSetDevice(device));
   rt_scene *s = new rt_scene();
-  // the scene's description (kind, tree shape, plane, kernel instantiation)
-  s->kind = src->kind;
+  // the scene's description (kind, tree shape, plane, kernel instantiation, switches)
   s->device = device;
-  s->maxd = src->maxd;
-  s->root = src->root;
-  std::memcpy(s->root_box, src->root_box, sizeof s->root_box);
-  std::memcpy(s->root_child, src->root_child, sizeof s->root_child);
-  s->host_nodes = src->host_nodes;
-  s->host_inner = src->host_inner;
-  s->n_inner = src->n_inner;
-  s->dmax2 = src->dmax2;
-  s->bvh_depth = src->bvh_depth;
-  std::memcpy(s->size, src->size, sizeof s->size);
-  s->grid_bricked = src->grid_bricked;
-  s->oct_depth = src->oct_depth;
-  s->plane = src->plane;
-  s->n_tris = src->n_tris;
-  s->root_nchild = src->root_nchild;
-  s->version = src->version;
-  s->dev_bytes = src->dev_bytes - src->dyn_bytes;  // (a plain snapshot: not dynamic)
-  s->sched_on = src->sched_on;
-  s->coop = src->coop;
-  s->pump_on = src->pump_on;
-  // the device arrays, copied device to device (over xGMI between GPUs)
-  void *const from[] = {src->d_nodes, src->d_tris, src->d_vals, src->d_child, src->d_ovals};
-  void **to[] = {(void **)&s->d_nodes, (void **)&s->d_tris, (void **)&s->d_vals, (void **)&s->d_child,
-                 (void **)&s->d_ovals};
+  s->info = src->info;
+  s->mesh = src->mesh;
+  s->grid = src->grid;
+  s->oct = src->oct;
+  s->info.dev_bytes = src->info.dev_bytes - src->dyn.bytes;  // (a plain snapshot: not dynamic)
+  // the device arrays, copied device to device (over xGMI between GPUs) at the
+  // size their owner holds (the triangles with their zero pad)
   hipError_t e = hipSuccess;
   const char *step = "";
-  for (int i = 0; i < 5 && e == hipSuccess; ++i) {
-    if (!from[i]) continue;
-    size_t bytes = 0;
-    if ((e = hipMemPtrGetInfo(from[i], &bytes)) != hipSuccess) { step = "hipMemPtrGetInfo"; break; }
-    if ((e = hipMalloc(to[i], bytes)) != hipSuccess) { step = "hipMalloc"; break; }
-    if ((e = hipMemcpyPeer(*to[i], device, from[i], src->device, bytes)) != hipSuccess) step = "hipMemcpyPeer";
-  }
+  auto copy = [&](auto &to, const auto &from) {
+    if (!from.p || e != hipSuccess) return;
+    if ((e = to.alloc_e(from.n)) != hipSuccess) { step = "hipMalloc"; return; }
+    if ((e = hipMemcpyPeer(to.p, device, from.p, src->device, from.bytes())) != hipSuccess) step = "hipMemcpyPeer";
+  };
+  copy(s->geo.nodes, src->geo.nodes);
+  copy(s->geo.tris, src->geo.tris);
+  copy(s->geo.vals, src->geo.vals);
+  copy(s->geo.child, src->geo.child);
+  copy(s->geo.ovals, src->geo.ovals);
   HIP_NOTE(hipSetDevice(prev));
   if (e != hipSuccess) {
     rt_scene_destroy(s);
@@ -512,12 +471,12 @@ static int check_update(const rt_scene *s, const float *vpos4, int64_t nverts, c
   if (!s) return set_err(RT_E_INVALID, std::string(who) + ": scene is NULL");
   if (!vpos4) return set_err(RT_E_INVALID, std::string(who) + ": vertex pointer is NULL");
   if (nverts <= 0) return set_err(RT_E_INVALID, std::string(who) + ": nverts must be positive");
-  if (s->kind != RT_SCENE_MESH) return set_err(RT_E_STATE, std::string(who) + ": not a mesh scene");
-  if (!s->dynamic)
+  if (s->info.kind != RT_SCENE_MESH) return set_err(RT_E_STATE, std::string(who) + ": not a mesh scene");
+  if (!s->dyn.on)
     return set_err(RT_E_STATE, std::string(who) + ": the mesh was not created with RT_MESH_DYNAMIC");
-  if (nverts != s->nverts)
+  if (nverts != s->dyn.nverts)
     return set_err(RT_E_INVALID, std::string(who) + ": nverts is " + std::to_string(nverts) + ", the mesh was created with " +
-                                     std::to_string(s->nverts));
+                                     std::to_string(s->dyn.nverts));
   return RT_OK;
 }
 
@@ -539,9 +498,9 @@ int instance_record(const rt_instance &in, int32_t nblas, int64_t index, const c
 
 int instance_range(const rt_scene *s, int32_t first, int32_t count, const char *who) {
   if (!s) return set_err(RT_E_INVALID, std::string(who) + ": scene is NULL");
-  if (s->kind != RT_SCENE_INSTANCED) return set_err(RT_E_STATE, std::string(who) + ": not an instanced scene");
-  if (first < 0 || count < 0 || (int64_t)first + count > s->ninst)
-    return set_err(RT_E_INVALID, std::string(who) + ": range outside the scene's " + std::to_string(s->ninst) +
+  if (s->info.kind != RT_SCENE_INSTANCED) return set_err(RT_E_STATE, std::string(who) + ": not an instanced scene");
+  if (first < 0 || count < 0 || (int64_t)first + count > s->inst.n)
+    return set_err(RT_E_INVALID, std::string(who) + ": range outside the scene's " + std::to_string(s->inst.n) +
                                      " instances");
   return RT_OK;
 }
@@ -553,7 +512,7 @@ int instance_range(const rt_scene *s, int32_t first, int32_t count, const char *
 static int tlas_update(const rt_scene *s, int32_t first, int32_t count, const float *d_xsrc, int32_t only_blas,
                        hipStream_t st) {
   const rti::TlasArgs t = rti::tlas_args(s);
-  if (int rc = s->d_mixed ? rti::mixed_boxes_launch(t, s->d_mixed, first, count, d_xsrc, only_blas, st)
+  if (int rc = s->inst.mixed.p ? rti::mixed_boxes_launch(t, s->inst.mixed.p, first, count, d_xsrc, only_blas, st)
                           : rti::tlas_boxes_launch(t, first, count, d_xsrc, only_blas, st))
     return rc;
   return rti::tlas_refit_launch(t, st);
@@ -562,15 +521,15 @@ static int tlas_update(const rt_scene *s, int32_t first, int32_t count, const fl
 // the record of the mixed table for one bottom-level scene (rt_instances.h)
 static rti::BlasRec blas_rec(const rt_scene *bl) {
   rti::BlasRec e{};
-  e.kind = (uint32_t)bl->kind;
-  if (bl->kind == RT_SCENE_MESH) {
+  e.kind = (uint32_t)bl->info.kind;
+  if (bl->info.kind == RT_SCENE_MESH) {
     e.mesh = mesh_dev(bl);
-  } else if (bl->kind == RT_SCENE_GRID) {
+  } else if (bl->info.kind == RT_SCENE_GRID) {
     e.grid = grid_dev(bl);
     e.var = (uint32_t)grid_mode(bl, e.grid);
   } else {
-    e.oct = OctDev{bl->d_child, bl->d_ovals};
-    e.var = bl->maxd <= 7 ? 1u : 0u;  // rt_dispatch.h: packed node coordinates for trees of up to 7 slots
+    e.oct = OctDev{bl->geo.child.p, bl->geo.ovals.p};
+    e.var = bl->info.maxd <= 7 ? 1u : 0u;  // rt_dispatch.h: packed node coordinates for trees of up to 7 slots
   }
   return e;
 }
@@ -589,7 +548,7 @@ static int create_instanced(const char *who, rt_scene *const *blas, int32_t nbla
   bool mixed = false;
   for (int32_t j = 0; j < nblas; ++j) {
     if (!blas[j]) return set_err(RT_E_INVALID, std::string(who) + ": BLAS " + std::to_string(j) + " is NULL");
-    const int kind = blas[j]->kind;
+    const int kind = blas[j]->info.kind;
     if (any && (kind == RT_SCENE_GRID || kind == RT_SCENE_OCTREE))
       mixed = true;
     else if (kind != RT_SCENE_MESH)
@@ -598,7 +557,7 @@ static int create_instanced(const char *who, rt_scene *const *blas, int32_t nbla
     if (blas[j]->device != dev)
       return set_err(RT_E_INVALID, std::string(who) + ": BLAS " + std::to_string(j) + " lives on device " +
                                        std::to_string(blas[j]->device) + ", the current device is " + std::to_string(dev));
-    maxd = std::max(maxd, blas[j]->maxd);  // (a grid keeps the default 1: it has no stack)
+    maxd = std::max(maxd, blas[j]->info.maxd);  // (a grid keeps the default 1: it has no stack)
   }
   if (mixed) maxd = std::max(maxd, 4);  // the smallest slot option (rt_dispatch.h) when only grids are there
   std::vector<rti::InstRec> recs((size_t)ninst);
@@ -614,26 +573,26 @@ static int create_instanced(const char *who, rt_scene *const *blas, int32_t nbla
   }
   rt_scene *s = nullptr;
   if (int rc = new_scene(&s)) return rc;
-  s->kind = RT_SCENE_INSTANCED;
-  s->maxd = maxd;  // the LDS stack of the deepest bottom-level tree
-  s->ninst = ninst;
-  s->blas.assign(blas, blas + nblas);
-  for (int32_t j = 0; j < nblas; ++j) s->blas_seen.push_back(blas[j]->version);
-  int rc = upload(&s->d_inst, recs.data(), recs.size(), s->dev_bytes);
-  if (!rc) rc = mixed ? upload(&s->d_mixed, mtab.data(), mtab.size(), s->dev_bytes)
-                      : upload(&s->d_blas, tab.data(), tab.size(), s->dev_bytes);
+  s->info.kind = RT_SCENE_INSTANCED;
+  s->info.maxd = maxd;  // the LDS stack of the deepest bottom-level tree
+  s->inst.n = ninst;
+  s->inst.blas.assign(blas, blas + nblas);
+  for (int32_t j = 0; j < nblas; ++j) s->inst.blas_seen.push_back(blas[j]->info.version);
+  int rc = s->inst.recs.upload(recs.data(), recs.size(), s->info.dev_bytes);
+  if (!rc) rc = mixed ? s->inst.mixed.upload(mtab.data(), mtab.size(), s->info.dev_bytes)
+                      : s->inst.tab.upload(tab.data(), tab.size(), s->info.dev_bytes);
   if (!rc && (flags & RT_INSTANCED_TLAS)) {
     // the matrices as given, the node array zeroed (node 0 and the pad words
     // stay zero), every leaf (the empty ones past ninst too) and the inner
     // nodes by the kernels that also serve the updates; done when this returns
     std::vector<float> xf(12 * (size_t)ninst);
     for (int32_t i = 0; i < ninst; ++i) std::memcpy(&xf[12 * (size_t)i], inst[i].xform, sizeof inst[i].xform);
-    s->tlas_leaves = rtt::leaf_count(ninst);
-    rc = upload(&s->d_xform, xf.data(), xf.size(), s->dev_bytes);
-    if (!rc) rc = upload(&s->d_tlas, (const rtt::TNode *)nullptr, 2 * (size_t)s->tlas_leaves, s->dev_bytes);
+    s->inst.tlas_leaves = rtt::leaf_count(ninst);
+    rc = s->inst.xform.upload(xf.data(), xf.size(), s->info.dev_bytes);
+    if (!rc) rc = s->inst.tlas.upload(nullptr, 2 * (size_t)s->inst.tlas_leaves, s->info.dev_bytes);
     if (!rc) {
-      hipError_t e = hipMemset(s->d_tlas, 0, 2 * (size_t)s->tlas_leaves * sizeof(rtt::TNode));
-      if (e == hipSuccess) rc = tlas_update(s, 0, s->tlas_leaves, nullptr, -1, nullptr);
+      hipError_t e = hipMemset(s->inst.tlas.p, 0, 2 * (size_t)s->inst.tlas_leaves * sizeof(rtt::TNode));
+      if (e == hipSuccess) rc = tlas_update(s, 0, s->inst.tlas_leaves, nullptr, -1, nullptr);
       if (e == hipSuccess && !rc) e = hipStreamSynchronize(nullptr);
       if (e != hipSuccess) rc = set_err(RT_E_DEVICE, rterr::hip_fail((std::string(who) + ": top-level tree").c_str(), e));
     }
@@ -668,16 +627,16 @@ int rt_scene_update_instances(rt_scene *s, int32_t first, int32_t count, const r
   if (count == 0) return RT_OK;
   std::vector<rti::InstRec> recs((size_t)count);
   for (int32_t i = 0; i < count; ++i)
-    if (int rc = instance_record(inst[i], (int32_t)s->blas.size(), (int64_t)first + i, who, recs[(size_t)i])) return rc;
+    if (int rc = instance_record(inst[i], (int32_t)s->inst.blas.size(), (int64_t)first + i, who, recs[(size_t)i])) return rc;
   int prev = 0;
   HIP_TRY(hipGetDevice(&prev));
   HIP_TRY(hipSetDevice(s->device));
-  hipError_t e = rtdma::h2d(s->d_inst + first, recs.data(), recs.size() * sizeof(rti::InstRec), nullptr);
+  hipError_t e = rtdma::h2d(s->inst.recs.p + first, recs.data(), recs.size() * sizeof(rti::InstRec), nullptr);
   int rc = RT_OK;
-  if (e == hipSuccess && s->d_tlas) {  // the matrices as given, then the leaves and the tree; done on return
+  if (e == hipSuccess && s->inst.tlas.p) {  // the matrices as given, then the leaves and the tree; done on return
     std::vector<float> xf(12 * (size_t)count);
     for (int32_t i = 0; i < count; ++i) std::memcpy(&xf[12 * (size_t)i], inst[i].xform, sizeof inst[i].xform);
-    e = rtdma::h2d(s->d_xform + 12 * (size_t)first, xf.data(), xf.size() * sizeof(float), nullptr);
+    e = rtdma::h2d(s->inst.xform.p + 12 * (size_t)first, xf.data(), xf.size() * sizeof(float), nullptr);
     if (e == hipSuccess) rc = tlas_update(s, first, count, nullptr, -1, nullptr);
     if (e == hipSuccess && !rc) e = hipStreamSynchronize(nullptr);
   }
@@ -692,18 +651,18 @@ int rt_scene_update_instances_device(rt_scene *s, int32_t first, int32_t count, 
   if (int rc = instance_range(s, first, count, who)) return rc;
   if (!d_xform12) return set_err(RT_E_INVALID, std::string(who) + ": matrix pointer is NULL");
   if (count == 0) return RT_OK;
-  if (int rc = rti::pose_launch(s->d_inst, first, count, d_xform12, (hipStream_t)stream)) return rc;
+  if (int rc = rti::pose_launch(s->inst.recs.p, first, count, d_xform12, (hipStream_t)stream)) return rc;
   // a top-level tree: the box kernel takes the matrices over and redoes these
   // leaves behind the pose kernel, then the refit; still only launches
-  return s->d_tlas ? tlas_update(s, first, count, d_xform12, -1, (hipStream_t)stream) : RT_OK;
+  return s->inst.tlas.p ? tlas_update(s, first, count, d_xform12, -1, (hipStream_t)stream) : RT_OK;
 }
 
 int rt_scene_get_tlas(const rt_scene *s, float *leaf_boxes, float *node_boxes, int32_t *leaves) {
   const char *who = "rt_scene_get_tlas";
   if (!s) return set_err(RT_E_INVALID, std::string(who) + ": scene is NULL");
-  if (s->kind != RT_SCENE_INSTANCED || !s->d_tlas)
+  if (s->info.kind != RT_SCENE_INSTANCED || !s->inst.tlas.p)
     return set_err(RT_E_STATE, std::string(who) + ": not an instanced scene created with RT_INSTANCED_TLAS");
-  const int32_t P = s->tlas_leaves;
+  const int32_t P = s->inst.tlas_leaves;
   if (leaves) *leaves = P;
   if (!leaf_boxes && !node_boxes) return RT_OK;
   std::vector<rtt::TNode> nd(2 * (size_t)P);
@@ -711,11 +670,11 @@ int rt_scene_get_tlas(const rt_scene *s, float *leaf_boxes, float *node_boxes, i
   HIP_TRY(hipGetDevice(&prev));
   HIP_TRY(hipSetDevice(s->device));
   hipError_t e = hipDeviceSynchronize();  // updates queued on any stream
-  if (e == hipSuccess) e = rtdma::d2h(nd.data(), s->d_tlas, nd.size() * sizeof(rtt::TNode), nullptr);
+  if (e == hipSuccess) e = rtdma::d2h(nd.data(), s->inst.tlas.p, nd.size() * sizeof(rtt::TNode), nullptr);
   HIP_NOTE(hipSetDevice(prev));
   if (e != hipSuccess) return set_err(RT_E_DEVICE, rterr::hip_fail(who, e));
   if (leaf_boxes)
-    for (int32_t i = 0; i < s->ninst; ++i) std::memcpy(leaf_boxes + 6 * (size_t)i, nd[(size_t)P + i].b, 6 * sizeof(float));
+    for (int32_t i = 0; i < s->inst.n; ++i) std::memcpy(leaf_boxes + 6 * (size_t)i, nd[(size_t)P + i].b, 6 * sizeof(float));
   if (node_boxes)
     for (int32_t n = 0; n < 2 * P; ++n) std::memcpy(node_boxes + 6 * (size_t)n, nd[(size_t)n].b, 6 * sizeof(float));
   return RT_OK;
@@ -730,7 +689,7 @@ int rt_scene_get_instances(const rt_scene *s, int32_t first, int32_t count, rt_i
   HIP_TRY(hipGetDevice(&prev));
   HIP_TRY(hipSetDevice(s->device));
   hipError_t e = hipDeviceSynchronize();  // pose updates queued on any stream
-  if (e == hipSuccess) e = rtdma::d2h(recs.data(), s->d_inst + first, recs.size() * sizeof(rti::InstRec), nullptr);
+  if (e == hipSuccess) e = rtdma::d2h(recs.data(), s->inst.recs.p + first, recs.size() * sizeof(rti::InstRec), nullptr);
   HIP_NOTE(hipSetDevice(prev));
   if (e != hipSuccess) return set_err(RT_E_DEVICE, rterr::hip_fail("rt_scene_get_instances", e));
   for (int32_t i = 0; i < count; ++i) {
@@ -758,9 +717,9 @@ int rt_scene_update_vertices(rt_scene *s, const float *vpos4, int64_t nverts) {
   HIP_TRY(hipGetDevice(&prev));
   HIP_TRY(hipSetDevice(s->device));
   int rc = RT_OK;
-  if (const hipError_t e = rtdma::h2d(s->d_vstage, vpos4, 16 * (size_t)nverts, nullptr))
+  if (const hipError_t e = rtdma::h2d(s->dyn.vstage.p, vpos4, 16 * (size_t)nverts, nullptr))
     rc = set_err(RT_E_DEVICE, rterr::hip_fail("rt_scene_update_vertices: vertex upload", e));
-  if (!rc) rc = update_vertices_device(s, s->d_vstage, nullptr);
+  if (!rc) rc = update_vertices_device(s, s->dyn.vstage.p, nullptr);
   HIP_NOTE(hipSetDevice(prev));
   return rc;
 }
@@ -771,21 +730,21 @@ int rt_scene_update_vertices(rt_scene *s, const float *vpos4, int64_t nverts) {
 // are returned; else *n_inner / *n_tris are the buffers' capacities.
 int rtx_scene_mesh_download(rt_scene *s, void *nodes224, int64_t *n_inner, void *tris48, int64_t *n_tris) {
   if (!s || !n_inner || !n_tris) return set_err(RT_E_INVALID, "rtx_scene_mesh_download: NULL argument");
-  if (s->kind != RT_SCENE_MESH) return set_err(RT_E_STATE, "rtx_scene_mesh_download: not a mesh scene");
+  if (s->info.kind != RT_SCENE_MESH) return set_err(RT_E_STATE, "rtx_scene_mesh_download: not a mesh scene");
   if (nodes224 || tris48) {
-    if (!nodes224 || !tris48 || *n_inner < (int64_t)s->n_inner || *n_tris < (int64_t)s->n_tris)
+    if (!nodes224 || !tris48 || *n_inner < (int64_t)s->mesh.n_inner || *n_tris < (int64_t)s->mesh.n_tris)
       return set_err(RT_E_INVALID, "rtx_scene_mesh_download: buffers too small");
     int prev = 0;
     HIP_TRY(hipGetDevice(&prev));
     HIP_TRY(hipSetDevice(s->device));
     hipError_t e = hipDeviceSynchronize();
-    if (e == hipSuccess) e = rtdma::d2h(nodes224, s->d_nodes, (size_t)s->n_inner * sizeof(rtl::GNode), nullptr);
-    if (e == hipSuccess) e = rtdma::d2h(tris48, s->d_tris, (size_t)s->n_tris * sizeof(rtl::GTri), nullptr);
+    if (e == hipSuccess) e = rtdma::d2h(nodes224, s->geo.nodes.p, (size_t)s->mesh.n_inner * sizeof(rtl::GNode), nullptr);
+    if (e == hipSuccess) e = rtdma::d2h(tris48, s->geo.tris.p, (size_t)s->mesh.n_tris * sizeof(rtl::GTri), nullptr);
     HIP_NOTE(hipSetDevice(prev));
     if (e != hipSuccess) return set_err(RT_E_DEVICE, rterr::hip_fail("rtx_scene_mesh_download", e));
   }
-  *n_inner = s->n_inner;
-  *n_tris = s->n_tris;
+  *n_inner = s->mesh.n_inner;
+  *n_tris = s->mesh.n_tris;
   return RT_OK;
 }
 
@@ -793,24 +752,24 @@ int rtx_scene_mesh_download(rt_scene *s, void *nodes224, int64_t *n_inner, void 
 // mesh scene: root_box[6], the root's child boxes root_child[48], dmax2.
 int rtx_scene_mesh_constants(const rt_scene *s, float root_box[6], float root_child[48], float *dmax2) {
   if (!s) return set_err(RT_E_INVALID, "rtx_scene_mesh_constants: scene is NULL");
-  if (s->kind != RT_SCENE_MESH) return set_err(RT_E_STATE, "rtx_scene_mesh_constants: not a mesh scene");
-  if (root_box) std::memcpy(root_box, s->root_box, sizeof s->root_box);
-  if (root_child) std::memcpy(root_child, s->root_child, sizeof s->root_child);
-  if (dmax2) *dmax2 = s->dmax2;
+  if (s->info.kind != RT_SCENE_MESH) return set_err(RT_E_STATE, "rtx_scene_mesh_constants: not a mesh scene");
+  if (root_box) std::memcpy(root_box, s->mesh.root_box, sizeof s->mesh.root_box);
+  if (root_child) std::memcpy(root_child, s->mesh.root_child, sizeof s->mesh.root_child);
+  if (dmax2) *dmax2 = s->mesh.dmax2;
   return RT_OK;
 }
 
 int rt_scene_get_plane(const rt_scene *s, int *enabled, float normal[3], float *offset) {
   if (!s) return set_err(RT_E_INVALID, "scene is NULL");
-  if (enabled) *enabled = s->plane.on;
-  if (normal) { normal[0] = s->plane.n.x; normal[1] = s->plane.n.y; normal[2] = s->plane.n.z; }
-  if (offset) *offset = s->plane.off;
+  if (enabled) *enabled = s->info.plane.on;
+  if (normal) { normal[0] = s->info.plane.n.x; normal[1] = s->info.plane.n.y; normal[2] = s->info.plane.n.z; }
+  if (offset) *offset = s->info.plane.off;
   return RT_OK;
 }
 
 int rt_scene_set_plane(rt_scene *s, int enabled, const float normal[3], float offset) {
   if (!s) return set_err(RT_E_INVALID, "scene is NULL");
-  PlaneDev &p = s->plane;
+  PlaneDev &p = s->info.plane;
   p.on = enabled ? 1 : 0;
   if (!enabled) return RT_OK;
   if (!normal) return set_err(RT_E_INVALID, "normal is NULL");
@@ -834,15 +793,15 @@ int rt_scene_set_plane(rt_scene *s, int enabled, const float normal[3], float of
   return RT_OK;
 }
 
-int rt_scene_kind(const rt_scene *s) { return s ? s->kind : RT_E_INVALID; }
-int64_t rt_scene_device_bytes(const rt_scene *s) { return s ? s->dev_bytes : 0; }
+int rt_scene_kind(const rt_scene *s) { return s ? s->info.kind : RT_E_INVALID; }
+int64_t rt_scene_device_bytes(const rt_scene *s) { return s ? s->info.dev_bytes : 0; }
 
 int rt_scene_bvh_stats(const rt_scene *s, int64_t *nodes, int64_t *inner, int32_t *max_depth) {
   if (!s) return set_err(RT_E_INVALID, "scene is NULL");
-  if (s->kind != RT_SCENE_MESH && s->kind != RT_SCENE_OCTREE) return set_err(RT_E_STATE, "not a tree scene");
-  if (nodes) *nodes = s->host_nodes;
-  if (inner) *inner = s->host_inner;
-  if (max_depth) *max_depth = s->kind == RT_SCENE_MESH ? s->bvh_depth : s->oct_depth;
+  if (s->info.kind != RT_SCENE_MESH && s->info.kind != RT_SCENE_OCTREE) return set_err(RT_E_STATE, "not a tree scene");
+  if (nodes) *nodes = s->mesh.host_nodes;
+  if (inner) *inner = s->mesh.host_inner;
+  if (max_depth) *max_depth = s->info.kind == RT_SCENE_MESH ? s->mesh.depth : s->oct.depth;
   return RT_OK;
 }
 
@@ -854,37 +813,19 @@ int rt_scene_destroy(rt_scene *s) {
   // the scene's own copy/render streams drain before anything they may still
   // read or write is freed (rt_render returns only after both, but a failed
   // call or a caller-stream launch may not have)
-  for (hipStream_t x : s->xs)
-    if (x) HIP_NOTE(hipStreamSynchronize(x));
-  if (s->sched_os) HIP_NOTE(hipStreamSynchronize(s->sched_os));
-  void *ptrs[] = {s->d_nodes, s->d_tris, s->d_vals, s->d_child, s->d_ovals, s->d_color, s->d_t,
-                  s->d_cost[0], s->d_order[0], s->d_cost[1], s->d_order[1], s->d_idx, s->d_vstage, s->d_edge, s->d_inst, s->d_blas, s->d_mixed, s->d_tlas, s->d_xform};
-  for (void *p : ptrs)
-    if (p) HIP_NOTE(hipFree(p));
-  if (s->h_refit) HIP_NOTE(hipHostFree(s->h_refit));
-  for (hipEvent_t e : s->ord_ev)
-    if (e) HIP_NOTE(hipEventDestroy(e));
-  if (s->frame_ev) HIP_NOTE(hipEventDestroy(s->frame_ev));
-  if (s->sched_os) {
-    rterr::stream_remove(s->sched_os);
-    HIP_NOTE(hipStreamDestroy(s->sched_os));
-  }
-  if (s->ev0) HIP_NOTE(hipEventDestroy(s->ev0));
-  if (s->ev1) HIP_NOTE(hipEventDestroy(s->ev1));
-  if (s->ev_host) HIP_NOTE(hipEventDestroy(s->ev_host));
-  if (s->xev) HIP_NOTE(hipEventDestroy(s->xev));
-  if (s->d_hit_box) HIP_NOTE(hipFree(s->d_hit_box));
-  if (s->h_hit_box) HIP_NOTE(hipHostFree(s->h_hit_box));
-  if (s->d_row_span) HIP_NOTE(hipFree(s->d_row_span));
-  if (s->h_row_span) HIP_NOTE(hipHostFree(s->h_row_span));
-  s->stage.release();
-  for (hipStream_t x : s->xs)
-    if (x) {
-      rterr::stream_remove(x);
-      HIP_NOTE(hipStreamDestroy(x));
-    }
-  HIP_NOTE(hipSetDevice(prev));
+  for (const rtmem::Stream &x : s->drop.xs)
+    if (x.s) HIP_NOTE(hipStreamSynchronize(x.s));
+  if (s->sched.os.s) HIP_NOTE(hipStreamSynchronize(s->sched.os.s));
   delete s;
+  HIP_NOTE(hipSetDevice(prev));
+  return RT_OK;
+}
+
+// Diagnostic (not part of include/rtamd.h): the live owners of rt_mem.h, in
+// the order device arrays, pinned host blocks, events, streams.
+int rtx_live_resources(int64_t out[4]) {
+  if (!out) return set_err(RT_E_INVALID, "rtx_live_resources: out is NULL");
+  for (int k = 0; k < 4; ++k) out[k] = rtmem::g_live[k].load(std::memory_order_relaxed);
   return RT_OK;
 }
 
@@ -947,25 +888,25 @@ int rtx_octree_flatten(const void *nodes36, int64_t count, int32_t *max_depth, i
 
 namespace rti {
 
-uint64_t scene_version(const rt_scene *s) { return s ? s->version : 0; }
+uint64_t scene_version(const rt_scene *s) { return s ? s->info.version : 0; }
 
 // A replica (rt_scene_replicate) of mesh scene `src` brought up to src's last
 // update: nodes and triangles copied device to device (the sizes never
 // change), the three host constants taken over. Blocking; the caller has
 // drained the streams that use the replica.
 int scene_refresh_replica(rt_scene *rep, const rt_scene *src) {
-  if (!rep || !src || rep->kind != src->kind) return set_err(RT_E_INVALID, "scene_refresh_replica: bad arguments");
-  if (rep->version == src->version || src->kind != RT_SCENE_MESH) return RT_OK;
-  if (rep->n_inner != src->n_inner || rep->n_tris != src->n_tris)
+  if (!rep || !src || rep->info.kind != src->info.kind) return set_err(RT_E_INVALID, "scene_refresh_replica: bad arguments");
+  if (rep->info.version == src->info.version || src->info.kind != RT_SCENE_MESH) return RT_OK;
+  if (rep->mesh.n_inner != src->mesh.n_inner || rep->mesh.n_tris != src->mesh.n_tris)
     return set_err(RT_E_STATE, "scene_refresh_replica: the replica is not of this scene");
-  if (src->n_inner)
-    HIP_TRY(hipMemcpyPeer(rep->d_nodes, rep->device, src->d_nodes, src->device, (size_t)src->n_inner * sizeof(rtl::GNode)));
-  if (src->n_tris)
-    HIP_TRY(hipMemcpyPeer(rep->d_tris, rep->device, src->d_tris, src->device, (size_t)src->n_tris * sizeof(rtl::GTri)));
-  std::memcpy(rep->root_box, src->root_box, sizeof rep->root_box);
-  std::memcpy(rep->root_child, src->root_child, sizeof rep->root_child);
-  rep->dmax2 = src->dmax2;
-  rep->version = src->version;
+  if (src->mesh.n_inner)
+    HIP_TRY(hipMemcpyPeer(rep->geo.nodes.p, rep->device, src->geo.nodes.p, src->device, (size_t)src->mesh.n_inner * sizeof(rtl::GNode)));
+  if (src->mesh.n_tris)
+    HIP_TRY(hipMemcpyPeer(rep->geo.tris.p, rep->device, src->geo.tris.p, src->device, (size_t)src->mesh.n_tris * sizeof(rtl::GTri)));
+  std::memcpy(rep->mesh.root_box, src->mesh.root_box, sizeof rep->mesh.root_box);
+  std::memcpy(rep->mesh.root_child, src->mesh.root_child, sizeof rep->mesh.root_child);
+  rep->mesh.dmax2 = src->mesh.dmax2;
+  rep->info.version = src->info.version;
   return RT_OK;
 }
 

@@ -141,13 +141,6 @@ __global__ __launch_bounds__(kWave) void sdf_kernel(SdfDev m, const float *p3, i
   out[o] = sdf_query(m, p, st_d, st_w);
 }
 
-template <class T>
-int upload(T **d, const T *h, size_t n) {
-  HIP_TRY(hipMalloc(reinterpret_cast<void **>(d), std::max<size_t>(n, 1) * sizeof(T)));
-  if (n) HIP_TRY(rtdma::h2d(*d, h, n * sizeof(T), nullptr));
-  return RT_OK;
-}
-
 // What an RT_MESH_DYNAMIC handle adds (rt_points.h): the creation topology,
 // the vertex staging buffer, scratch, and the event of the updates.
 int upload_dynamic(rt_sdf_mesh *m, const rth::SdfTopo &t, const uint32_t *idx, int64_t nidx) {
@@ -155,19 +148,19 @@ int upload_dynamic(rt_sdf_mesh *m, const rth::SdfTopo &t, const uint32_t *idx, i
   m->n_wverts = t.n_wverts;
   m->n_wedges = t.n_wedges;
   m->level_first = rth::bvh_level_first(m->host.bvh.nodes);
-  if (int rc = upload(&m->d_idx, idx, (size_t)nidx)) return rc;
-  if (int rc = upload(&m->d_weld, t.weld.data(), t.weld.size())) return rc;
-  if (int rc = upload(&m->d_tri_edge, t.tri_edge.data(), t.tri_edge.size())) return rc;
-  if (int rc = upload(&m->d_v_off, t.v_off.data(), t.v_off.size())) return rc;
-  if (int rc = upload(&m->d_v_inc, t.v_inc.data(), t.v_inc.size())) return rc;
-  if (int rc = upload(&m->d_e_off, t.e_off.data(), t.e_off.size())) return rc;
-  if (int rc = upload(&m->d_e_inc, t.e_inc.data(), t.e_inc.size())) return rc;
-  HIP_TRY(hipMalloc(reinterpret_cast<void **>(&m->d_vstage), std::max<size_t>(nv, 1) * 16));
-  HIP_TRY(hipMalloc(reinterpret_cast<void **>(&m->d_fn), ntri * 16));
-  HIP_TRY(hipMalloc(reinterpret_cast<void **>(&m->d_ang), ntri * 24));
-  HIP_TRY(hipMalloc(reinterpret_cast<void **>(&m->d_vn), (size_t)t.n_wverts * 16));
-  HIP_TRY(hipMalloc(reinterpret_cast<void **>(&m->d_en), (size_t)t.n_wedges * 16));
-  HIP_TRY(hipEventCreateWithFlags(&m->updated, hipEventDisableTiming));
+  if (int rc = m->d_idx.upload(idx, (size_t)nidx)) return rc;
+  if (int rc = m->d_weld.upload(t.weld.data(), t.weld.size())) return rc;
+  if (int rc = m->d_tri_edge.upload(t.tri_edge.data(), t.tri_edge.size())) return rc;
+  if (int rc = m->d_v_off.upload(t.v_off.data(), t.v_off.size())) return rc;
+  if (int rc = m->d_v_inc.upload(t.v_inc.data(), t.v_inc.size())) return rc;
+  if (int rc = m->d_e_off.upload(t.e_off.data(), t.e_off.size())) return rc;
+  if (int rc = m->d_e_inc.upload(t.e_inc.data(), t.e_inc.size())) return rc;
+  if (int rc = m->d_vstage.alloc(std::max<size_t>(nv, 1))) return rc;
+  if (int rc = m->d_fn.alloc(ntri)) return rc;
+  if (int rc = m->d_ang.alloc(3 * ntri)) return rc;
+  if (int rc = m->d_vn.alloc(t.n_wverts)) return rc;
+  if (int rc = m->d_en.alloc(t.n_wedges)) return rc;
+  if (int rc = m->updated.create(hipEventDisableTiming)) return rc;
   m->dev_bytes += (int64_t)(4 * (size_t)nidx + 16 * nv + 4 * nv + 12 * ntri + 4 * ((size_t)t.n_wverts + 1) + 12 * ntri +
                             4 * ((size_t)t.n_wedges + 1) + 12 * ntri + 16 * ntri + 24 * ntri +
                             16 * (size_t)t.n_wverts + 16 * (size_t)t.n_wedges);
@@ -190,22 +183,22 @@ int check_update(const rt_sdf_mesh *m, const float *vpos4, int64_t nverts, const
 // Queues one refit on `st` and records the handle's event behind it. Only launches.
 int update_device(rt_sdf_mesh *m, const float *d_vpos4, hipStream_t st) {
   SdfRefitArgs a{};
-  a.nodes = m->d_nodes;
-  a.tri = m->d_tri;
-  a.pn = m->d_pn;
+  a.nodes = m->d_nodes.p;
+  a.tri = m->d_tri.p;
+  a.pn = m->d_pn.p;
   a.root = m->root;
   a.vpos4 = d_vpos4;
-  a.idx = m->d_idx;
-  a.weld = m->d_weld;
-  a.tri_edge = m->d_tri_edge;
-  a.v_off = m->d_v_off;
-  a.v_inc = m->d_v_inc;
-  a.e_off = m->d_e_off;
-  a.e_inc = m->d_e_inc;
-  a.fn = m->d_fn;
-  a.ang = m->d_ang;
-  a.vn = m->d_vn;
-  a.en = m->d_en;
+  a.idx = m->d_idx.p;
+  a.weld = m->d_weld.p;
+  a.tri_edge = m->d_tri_edge.p;
+  a.v_off = m->d_v_off.p;
+  a.v_inc = m->d_v_inc.p;
+  a.e_off = m->d_e_off.p;
+  a.e_inc = m->d_e_inc.p;
+  a.fn = m->d_fn.p;
+  a.ang = m->d_ang.p;
+  a.vn = m->d_vn.p;
+  a.en = m->d_en.p;
   a.ntri = (uint32_t)m->ntri;
   a.n_wverts = m->n_wverts;
   a.n_wedges = m->n_wedges;
@@ -214,13 +207,13 @@ int update_device(rt_sdf_mesh *m, const float *d_vpos4, hipStream_t st) {
   m->oct_depth = -1;  // the octree cache is of the mesh before
   std::vector<uint8_t>().swap(m->oct_nodes);
   const int rc = sdf_refit_launch(a, st);
-  HIP_TRY(hipEventRecord(m->updated, st));  // (also behind a partly queued refit)
+  HIP_TRY(hipEventRecord(m->updated.e, st));  // (also behind a partly queued refit)
   return rc;
 }
 
 // The handle's own host entries read behind the last update (its event).
 int wait_updated(const rt_sdf_mesh *m, hipStream_t st) {
-  if (m->updated) HIP_TRY(hipStreamWaitEvent(st, m->updated, 0));
+  if (m->updated.e) HIP_TRY(hipStreamWaitEvent(st, m->updated.e, 0));
   return RT_OK;
 }
 
@@ -240,23 +233,16 @@ constexpr int64_t kQueryBatch = 1 << 20;
 
 // The handle's query stream and staging for batches of up to `n` points.
 int query_staging(rt_sdf_mesh *m, int64_t n) {
-  if (!m->qs) {
-    HIP_TRY(hipStreamCreateWithFlags(&m->qs, hipStreamNonBlocking));
-    rterr::stream_add(m->qs, m->device, "SDF query stream");
-  }
-  rterr::stream_mark(m->qs, "rt_sdf_mesh_points");
+  if (int rc = m->qs.create(m->device, "SDF query stream")) return rc;
+  rterr::stream_mark(m->qs.s, "rt_sdf_mesh_points");
   const int64_t want = std::min(n, kQueryBatch);
   if (want <= m->q_cap) return RT_OK;
-  HIP_TRY(hipStreamSynchronize(m->qs));
-  if (m->h_stage) HIP_NOTE(hipHostFree(m->h_stage));
-  if (m->d_p3) HIP_NOTE(hipFree(m->d_p3));
-  if (m->d_out) HIP_NOTE(hipFree(m->d_out));
-  m->h_stage = m->d_p3 = m->d_out = nullptr;
+  HIP_TRY(hipStreamSynchronize(m->qs.s));
   m->q_cap = 0;
   const int64_t cap = std::max<int64_t>(want, 4096);
-  HIP_TRY(hipHostMalloc(&m->h_stage, (size_t)cap * 16, hipHostMallocDefault));
-  HIP_TRY(hipMalloc(&m->d_p3, (size_t)cap * 12));
-  HIP_TRY(hipMalloc(&m->d_out, (size_t)cap * 4));
+  if (int rc = m->h_stage.alloc((size_t)cap * 4, hipHostMallocDefault)) return rc;
+  if (int rc = m->d_p3.alloc((size_t)cap * 3)) return rc;
+  if (int rc = m->d_out.alloc((size_t)cap)) return rc;
   m->q_cap = cap;
   return RT_OK;
 }
@@ -273,34 +259,34 @@ int query_host(rt_sdf_mesh *m, const float *p3, int64_t n, float *out) {
   const std::string stale = rterr::take_stale();  // before any call of ours can overwrite it
   g_stale_seen = stale;
   HIP_TRY(hipSetDevice(m->device));
-  if (const hipError_t e = hipStreamQuery(m->qs ? m->qs : nullptr); e != hipSuccess && e != hipErrorNotReady)
+  if (const hipError_t e = hipStreamQuery(m->qs.s ? m->qs.s : nullptr); e != hipSuccess && e != hipErrorNotReady)
     return rterr::set(RT_E_DEVICE, std::string("device already in error before the SDF query: ") +
                                        hipGetErrorString(e) + (stale.empty() ? "" : "; " + stale));
   int rc = query_staging(m, n);
   if (rc != RT_OK) return rc;
-  if ((rc = wait_updated(m, m->qs)) != RT_OK) return rc;
+  if ((rc = wait_updated(m, m->qs.s)) != RT_OK) return rc;
   for (int64_t i0 = 0; i0 < n; i0 += m->q_cap) {
     const int64_t k = std::min(m->q_cap, n - i0);
-    std::memcpy(m->h_stage, p3 + 3 * i0, (size_t)k * 12);
-    hipError_t e = hipMemcpyAsync(m->d_p3, m->h_stage, (size_t)k * 12, hipMemcpyHostToDevice, m->qs);
+    std::memcpy(m->h_stage.h, p3 + 3 * i0, (size_t)k * 12);
+    hipError_t e = hipMemcpyAsync(m->d_p3.p, m->h_stage.h, (size_t)k * 12, hipMemcpyHostToDevice, m->qs.s);
     const char *step = "hipMemcpyAsync H2D of the points";
     if (e == hipSuccess) {
       hipLaunchKernelGGL(sdf_kernel<false>, dim3((uint32_t)((k + kWave - 1) / kWave)), dim3(kWave), lds_bytes(m),
-                         m->qs, dev_of(m), m->d_p3, k, 0u, 0u, 0u, m->stack_cap, m->d_out);
+                         m->qs.s, dev_of(m), m->d_p3.p, k, 0u, 0u, 0u, m->stack_cap, m->d_out.p);
       e = hipGetLastError();
       step = "sdf_kernel launch";
     }
-    float *h_out = m->h_stage + 3 * m->q_cap;
+    float *h_out = m->h_stage.h + 3 * m->q_cap;
     if (e == hipSuccess) {
-      e = hipMemcpyAsync(h_out, m->d_out, (size_t)k * 4, hipMemcpyDeviceToHost, m->qs);
+      e = hipMemcpyAsync(h_out, m->d_out.p, (size_t)k * 4, hipMemcpyDeviceToHost, m->qs.s);
       step = "hipMemcpyAsync D2H of the distances";
     }
     if (e == hipSuccess) {
-      e = hipStreamSynchronize(m->qs);
+      e = hipStreamSynchronize(m->qs.s);
       step = "hipStreamSynchronize after the query";
     }
     if (e != hipSuccess) {
-      HIP_NOTE(hipStreamSynchronize(m->qs));
+      HIP_NOTE(hipStreamSynchronize(m->qs.s));
       return rterr::set(RT_E_DEVICE, std::string("SDF query of ") + std::to_string(k) + " points: " + step +
                                          ": " + hipGetErrorString(e) + (stale.empty() ? "" : "; " + stale));
     }
@@ -350,9 +336,9 @@ int rt_sdf_mesh_create_ex(const float *vpos4, int64_t nverts, const uint32_t *id
     return rterr::set(RT_E_INVALID, "BVH too deep for the SDF query stack");
   }
   int rc = hipGetDevice(&m->device) == hipSuccess ? RT_OK : rterr::set(RT_E_DEVICE, "no HIP device");
-  if (rc == RT_OK) rc = upload(&m->d_nodes, b.nodes.data(), b.nodes.size());
-  if (rc == RT_OK) rc = upload(&m->d_tri, reinterpret_cast<const float4 *>(m->host.tri.data()), m->host.tri.size() / 4);
-  if (rc == RT_OK) rc = upload(&m->d_pn, reinterpret_cast<const float4 *>(m->host.pn.data()), m->host.pn.size() / 4);
+  if (rc == RT_OK) rc = m->d_nodes.upload(b.nodes.data(), b.nodes.size());
+  if (rc == RT_OK) rc = m->d_tri.upload(reinterpret_cast<const float4 *>(m->host.tri.data()), m->host.tri.size() / 4);
+  if (rc == RT_OK) rc = m->d_pn.upload(reinterpret_cast<const float4 *>(m->host.pn.data()), m->host.pn.size() / 4);
   m->dev_bytes = (int64_t)(b.nodes.size() * sizeof(rtl::GNode) + m->host.tri.size() * 4 + m->host.pn.size() * 4);
   if (rc == RT_OK && m->dynamic) rc = upload_dynamic(m, topo, idx, nidx);
   if (rc != RT_OK) {
@@ -375,12 +361,12 @@ int rt_sdf_mesh_update_vertices(rt_sdf_mesh *m, const float *vpos4, int64_t nver
   HIP_TRY(hipSetDevice(m->device));
   int rc = RT_OK;
   // (the staging buffer may still be read by an earlier update's kernels)
-  hipError_t e = hipEventSynchronize(m->updated);
-  if (e == hipSuccess) e = rtdma::h2d(m->d_vstage, vpos4, 16 * (size_t)nverts, nullptr);
+  hipError_t e = hipEventSynchronize(m->updated.e);
+  if (e == hipSuccess) e = rtdma::h2d(m->d_vstage.p, vpos4, 16 * (size_t)nverts, nullptr);
   if (e != hipSuccess) rc = rterr::set(RT_E_DEVICE, rterr::hip_fail("rt_sdf_mesh_update_vertices: vertex upload", e));
-  if (!rc) rc = update_device(m, reinterpret_cast<const float *>(m->d_vstage), nullptr);
+  if (!rc) rc = update_device(m, reinterpret_cast<const float *>(m->d_vstage.p), nullptr);
   if (!rc) {
-    e = hipEventSynchronize(m->updated);
+    e = hipEventSynchronize(m->updated.e);
     if (e != hipSuccess) rc = rterr::set(RT_E_DEVICE, rterr::hip_fail("rt_sdf_mesh_update_vertices: wait", e));
   }
   HIP_NOTE(hipSetDevice(prev));
@@ -394,7 +380,7 @@ int rt_sdf_mesh_get_pseudonormals(const rt_sdf_mesh *m, float *pn28, int64_t ntr
   HIP_TRY(hipGetDevice(&prev));
   HIP_TRY(hipSetDevice(m->device));
   hipError_t e = hipDeviceSynchronize();
-  if (e == hipSuccess) e = rtdma::d2h(pn28, m->d_pn, (size_t)ntri * 28 * 4, nullptr);
+  if (e == hipSuccess) e = rtdma::d2h(pn28, m->d_pn.p, (size_t)ntri * 28 * 4, nullptr);
   HIP_NOTE(hipSetDevice(prev));
   if (e != hipSuccess) return rterr::set(RT_E_DEVICE, rterr::hip_fail("rt_sdf_mesh_get_pseudonormals", e));
   return RT_OK;
@@ -420,8 +406,8 @@ int rtx_sdf_mesh_download(const rt_sdf_mesh *m, void *nodes224, int64_t *n_inner
     HIP_TRY(hipGetDevice(&prev));
     HIP_TRY(hipSetDevice(m->device));
     hipError_t e = hipDeviceSynchronize();
-    if (e == hipSuccess && ni) e = rtdma::d2h(nodes224, m->d_nodes, (size_t)ni * sizeof(rtl::GNode), nullptr);
-    if (e == hipSuccess && nt) e = rtdma::d2h(tri48, m->d_tri, (size_t)nt * 48, nullptr);
+    if (e == hipSuccess && ni) e = rtdma::d2h(nodes224, m->d_nodes.p, (size_t)ni * sizeof(rtl::GNode), nullptr);
+    if (e == hipSuccess && nt) e = rtdma::d2h(tri48, m->d_tri.p, (size_t)nt * 48, nullptr);
     HIP_NOTE(hipSetDevice(prev));
     if (e != hipSuccess) return rterr::set(RT_E_DEVICE, rterr::hip_fail("rtx_sdf_mesh_download", e));
   }
@@ -443,14 +429,13 @@ int rt_sdf_mesh_grid(rt_sdf_mesh *m, const uint32_t size[3], float *values) {
   g_stale_seen = rterr::take_stale();
   HIP_TRY(hipSetDevice(m->device));
   if (int rc = wait_updated(m, nullptr)) return rc;
-  float *d = nullptr;
-  HIP_TRY(hipMalloc(&d, (size_t)n * 4));
+  rtmem::DevArray<float> d;
+  if (int rc = d.alloc((size_t)n)) return rc;
   hipLaunchKernelGGL(sdf_kernel<true>, dim3(blocks), dim3(kWave), lds_bytes(m), 0, dev_of(m), nullptr,
-                     n, size[0], size[1], size[2], m->stack_cap, d);
+                     n, size[0], size[1], size[2], m->stack_cap, d.p);
   hipError_t e = hipGetLastError();
   if (e == hipSuccess) e = hipDeviceSynchronize();
-  if (e == hipSuccess) e = rtdma::d2h(values, d, (size_t)n * 4, nullptr);
-  HIP_NOTE(hipFree(d));
+  if (e == hipSuccess) e = rtdma::d2h(values, d.p, (size_t)n * 4, nullptr);
   if (e != hipSuccess) return rterr::set(RT_E_DEVICE, std::string("sdf grid: ") + hipGetErrorString(e));
   return RT_OK;
 }
@@ -490,22 +475,7 @@ int rt_sdf_mesh_octree(rt_sdf_mesh *m, int32_t depth, int64_t *count, void *node
 int rt_sdf_mesh_destroy(rt_sdf_mesh *m) {
   if (!m) return RT_OK;
   HIP_NOTE(hipSetDevice(m->device));
-  if (m->qs) {
-    HIP_NOTE(hipStreamSynchronize(m->qs));
-    rterr::stream_remove(m->qs);
-    HIP_NOTE(hipStreamDestroy(m->qs));
-  }
-  if (m->h_stage) HIP_NOTE(hipHostFree(m->h_stage));
-  if (m->d_p3) HIP_NOTE(hipFree(m->d_p3));
-  if (m->d_out) HIP_NOTE(hipFree(m->d_out));
-  if (m->d_nodes) HIP_NOTE(hipFree(m->d_nodes));
-  if (m->d_tri) HIP_NOTE(hipFree(m->d_tri));
-  if (m->d_pn) HIP_NOTE(hipFree(m->d_pn));
-  for (void *p : {(void *)m->d_idx, (void *)m->d_weld, (void *)m->d_tri_edge, (void *)m->d_v_off, (void *)m->d_v_inc,
-                  (void *)m->d_e_off, (void *)m->d_e_inc, (void *)m->d_vstage, (void *)m->d_fn, (void *)m->d_ang,
-                  (void *)m->d_vn, (void *)m->d_en})
-    if (p) HIP_NOTE(hipFree(p));
-  if (m->updated) HIP_NOTE(hipEventDestroy(m->updated));
+  if (m->qs.s) HIP_NOTE(hipStreamSynchronize(m->qs.s));
   delete m;
   return RT_OK;
 }

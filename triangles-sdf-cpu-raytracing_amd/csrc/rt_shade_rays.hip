@@ -87,16 +87,16 @@ int rt_shade_rays_device(rt_scene *s, const rt_ray_batch *b, const rt_render_par
   if (p->reserved != 0) return set_err(RT_E_INVALID, "rt_shade_rays_device: params.reserved must be 0");
   if (b->n == 0) return RT_OK;
   const hipStream_t st = (hipStream_t)stream;
-  if (s->kind == RT_SCENE_INSTANCED) {
+  if (s->info.kind == RT_SCENE_INSTANCED) {
     if (int rc = rti::instanced_sync(s, st)) return rc;
-    const rti::InstArgs a{s->d_inst, s->d_blas, s->ninst, s->maxd, s->d_tlas, s->tlas_leaves};
-    if (s->d_mixed) return rti::shade_mixed_launch(rti::MixedArgs{a, s->d_mixed}, s->plane, *p, *b, d_color, flags, st);
-    return rti::shade_instances_launch(a, s->plane, *p, *b, d_color, flags, st);
+    const rti::InstArgs a{s->inst.recs.p, s->inst.tab.p, s->inst.n, s->info.maxd, s->inst.tlas.p, s->inst.tlas_leaves};
+    if (s->inst.mixed.p) return rti::shade_mixed_launch(rti::MixedArgs{a, s->inst.mixed.p}, s->info.plane, *p, *b, d_color, flags, st);
+    return rti::shade_instances_launch(a, s->info.plane, *p, *b, d_color, flags, st);
   }
   const unsigned blocks = (unsigned)((b->n + kSBlock - 1) / kSBlock);
   if (!dispatch_scene(s, [&](const auto &sc, auto slots) {
         shade_rays_kernel<std::decay_t<decltype(sc)>, decltype(slots)::value>
-            <<<blocks, kSBlock, 0, st>>>(sc, s->plane, *p, *b, d_color, flags);
+            <<<blocks, kSBlock, 0, st>>>(sc, s->info.plane, *p, *b, d_color, flags);
       }))
     return set_err(RT_E_STATE, "scene has no geometry");
   HIP_TRY(hipGetLastError());

@@ -237,6 +237,9 @@ _XSIGS = {
                                         C.POINTER(C.c_int64)]),
     "rtx_sdf_mesh_refit_host": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                           C.POINTER(C.c_int64), C.c_void_p, C.POINTER(C.c_int64), C.c_void_p]),
+    # the live owners behind every handle (csrc/rt_mem.h): device arrays, pinned
+    # host blocks, events, streams
+    "rtx_live_resources": (C.c_int, [C.POINTER(C.c_int64)]),
 }
 
 
