@@ -796,6 +796,74 @@ int rt_sdf_mesh_update_vertices_device(rt_sdf_mesh *m, const float *d_vpos4, int
  * be the handle's triangle count (else RT_E_INVALID). */
 int rt_sdf_mesh_get_pseudonormals(const rt_sdf_mesh *m, float *pn28, int64_t ntri);
 int64_t rt_sdf_mesh_device_bytes(const rt_sdf_mesh *m);   /* RT_E_INVALID for a NULL handle */
+
+/* ---- SDF scenes that follow a deforming mesh on the device ---
+ * A grid scene takes new values from a device buffer, and an octree scene is
+ * rebuilt from an SDF-mesh handle, both in stream order: the calls only launch
+ * on `stream` (hipStream_t or NULL), with no allocation, no copy and no host
+ * wait. The scene keeps its device arrays, so ray queries and frames queued on
+ * the same stream afterwards see the new scene, and so does an instanced scene
+ * that holds it as a bottom-level scene (its table holds the same pointers; it
+ * is not touched). The caller orders a call against work that still uses the
+ * scene on OTHER streams. Copies made by rt_scene_replicate (rt_multi's
+ * included) are snapshots and do not follow.
+ *
+ * rt_scene_update_grid_device: any grid scene, linear or bricked. d_values
+ * holds size[0]*size[1]*size[2] floats of the scene's own size in the layout
+ * (x*sy+y)*sz+z, which is what rt_sdf_mesh_grid_device writes; the scene's
+ * array is rewritten in the layout the scene was created with (a copy kernel,
+ * or the bricking kernel of creation). The scene's device must be the current
+ * one. RT_E_STATE for a scene that is not a grid, RT_E_INVALID for a NULL
+ * argument or another current device.
+ *
+ * rt_scene_create_octree_dynamic: an octree scene with room for max_nodes
+ * nodes of a tree of at most `depth` levels; depth in [0, 12] (the range of
+ * rt_sdf_mesh_octree), max_nodes in [1, 2^32 - 1], checked before anything
+ * touches a device (RT_E_INVALID). Every device buffer a rebuild will ever
+ * need is allocated here and counted in rt_scene_device_bytes: per node of
+ * capacity 40 bytes of scene (8 word + 32 values) and 52 bytes of build
+ * scratch (the same again, 8 for the node's cell, 4 for its refine flag), and
+ * a table of at most 150 KB. The kernel's stack class is the one of a
+ * `depth`-level tree for the scene's life (rt_scene_bvh_stats reports
+ * `depth`), whatever tree it holds. The initial tree is one root that is an
+ * empty leaf (values 1000): every ray misses.
+ *
+ * rt_sdf_mesh_octree_device: the scene becomes the tree rt_sdf_mesh_octree
+ * defines for the handle's current mesh at the scene's depth, as
+ * rt_scene_create_octree would hold it:
+ *   - a node of level d < depth in cell (i, j, k) is refined iff |sdf(centre)|
+ *     <= 1.7320508f * 2^-d, centre = (float)(2i+1) * 2^-d - 1.0f per axis;
+ *     an unrefined node is an empty leaf with eight values of 1000, a refined
+ *     one has values 0;
+ *   - a level-`depth` node holds the SDF at its corners, (float)(i + x) *
+ *     2^(1-depth) - 1.0f per axis, as values[(x<<2)|(y<<1)|z];
+ *   - nodes in BFS order, the eight children of a node contiguous and in the
+ *     order of their parents, so leaf indices (rt_ray_batch prim) are those of
+ *     a fresh scene of the same nodes;
+ *   - a leaf never hits if all its values are > 10, or all == 0, or all >=
+ *     1e-4; the child masks are those of rt_scene_create_octree.
+ * Every distance has the bits rt_sdf_mesh_points gives for the point. A build
+ * is 5 * depth + 5 launches (4 at depth 0) sized by depth and max_nodes, never
+ * by the mesh. Handle and scene must live on the current device
+ * (RT_E_INVALID); a scene not made by
+ * rt_scene_create_octree_dynamic gives RT_E_STATE; a refused call launches
+ * nothing. The caller also orders the build against updates of the handle on
+ * other streams, as for rt_sdf_mesh_points_device.
+ * Overflow: a tree that needs more than max_nodes nodes is dropped on the
+ * device. The scene keeps, bit for bit, the tree it had, and a device flag
+ * records the drop until the next build that fits. Size max_nodes with
+ * rt_sdf_mesh_octree(m, depth, &count, NULL).
+ *
+ * rt_scene_octree_status / rt_scene_get_octree wait for the device first. Any
+ * octree scene: *count = the nodes it holds now, *overflow = 1 if its last
+ * build was dropped (a plain octree: its size, 0). rt_scene_get_octree returns
+ * the 36-byte nodes rebuilt from what the scene holds (values as stored, the
+ * children offset, 0 for a leaf of either kind); two-call protocol on *count. */
+int rt_scene_update_grid_device(rt_scene *s, const float *d_values, void *stream);
+int rt_scene_create_octree_dynamic(int32_t depth, int64_t max_nodes, rt_scene **out);
+int rt_sdf_mesh_octree_device(rt_sdf_mesh *m, rt_scene *s, void *stream);
+int rt_scene_octree_status(rt_scene *s, int64_t *count, int32_t *overflow);
+int rt_scene_get_octree(rt_scene *s, int64_t *count, void *nodes36);
 /* Host-only: midpoint subdivision `levels` times (each triangle -> 4, edge
  * midpoints shared, (a+b)*0.5 on the 4 components): the config-5 stand-in
  * for MotorcycleCylinderHead.obj. Two-call protocol on the counts. */

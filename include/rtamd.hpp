@@ -262,6 +262,12 @@ class SDFGrid : public IScene {  // grid_raytracing.hpp:10-21
     check(rt_scene_create_grid(size, values.data(), &s));
     reset(s);
   }
+  // New values from device memory (size[0]*size[1]*size[2] floats, x-major),
+  // in stream order on `stream` (hipStream_t or nullptr); only launches. The
+  // host copy `values` is not touched.
+  void updateDevice(const float *d_values, void *stream = nullptr) const {
+    check(rt_scene_update_grid_device(handle(), d_values, stream));
+  }
 };
 inline void loadSDFGrid(SDFGrid &g, const std::string &path) {  // grid_raytracing.cpp:127-134
   check(rt_load_grid(path.c_str(), g.size, nullptr));
@@ -277,6 +283,36 @@ class SDFOctree : public IScene {  // octree_raytracing.hpp:20-47
     rt_scene *s = nullptr;
     check(rt_scene_create_octree(nodes.data(), (int64_t)(nodes.size() / 36), &s));
     reset(s);
+  }
+  // A scene with room for maxNodes nodes of a tree of at most `depth` levels,
+  // one empty leaf at first, which buildDevice rebuilds (no reference
+  // counterpart; the host copy `nodes` is not used).
+  void createDynamic(int32_t depth, int64_t maxNodes) {
+    rt_scene *s = nullptr;
+    check(rt_scene_create_octree_dynamic(depth, maxNodes, &s));
+    reset(s);
+  }
+  // Rebuild the scene as the octree of SDF-mesh handle `m` as it is now, in
+  // stream order on `stream` (hipStream_t or nullptr); only launches. A tree
+  // that passes the capacity is dropped: status().
+  void buildDevice(rt_sdf_mesh *m, void *stream = nullptr) const {
+    check(rt_sdf_mesh_octree_device(m, handle(), stream));
+  }
+  // After a wait for the device: the nodes the scene holds / whether its last
+  // build was dropped, and the 36-byte nodes rebuilt from the device arrays.
+  int64_t status(bool *overflow = nullptr) const {
+    int64_t n = 0;
+    int32_t o = 0;
+    check(rt_scene_octree_status(handle(), &n, &o));
+    if (overflow) *overflow = o != 0;
+    return n;
+  }
+  std::vector<uint8_t> deviceNodes() const {
+    int64_t n = 0;
+    check(rt_scene_get_octree(handle(), &n, nullptr));
+    std::vector<uint8_t> out((size_t)n * 36);
+    check(rt_scene_get_octree(handle(), &n, out.data()));
+    return out;
   }
 };
 inline void loadSDFOctree(SDFOctree &o, const std::string &path) {  // octree_raytracing.cpp:8-16

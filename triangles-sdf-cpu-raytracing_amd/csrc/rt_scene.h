@@ -89,6 +89,22 @@ struct Dynamic {
   int64_t bytes = 0;  // what this part added to Common::dev_bytes
 };
 
+// An octree made by rt_scene_create_octree_dynamic: Geometry::child / ovals
+// hold max_nodes entries, of which status[0] are the tree, and the scratch of
+// the device build (rt_sdf_octree.h OctBuildArgs) sits here, allocated once.
+// A plain octree scene and a replica leave all of it empty.
+struct OctDynamic {
+  bool on = false;
+  uint32_t max_nodes = 0;
+  rtmem::DevArray<uint32_t> status;  // {nodes the scene holds, the last build was dropped}
+  rtmem::DevArray<rtl::OctWord> s_child;
+  rtmem::DevArray<rtl::OctVals> s_vals;
+  rtmem::DevArray<uint64_t> cells;
+  rtmem::DevArray<uint32_t> flag, bsum, lvl;
+  rtmem::DevArray<float> top;
+  int64_t bytes = 0;  // what this part added to Common::dev_bytes
+};
+
 // RT_SCENE_INSTANCED: the instance records and the table of the bottom-level
 // scenes' MeshDev on the device; the scenes themselves (not owned) and the
 // update counter each table entry was written from. Nothing here depends on a
@@ -171,6 +187,7 @@ struct rt_scene {
   rts::OctDesc oct;
   rts::Geometry geo;
   rts::Dynamic dyn;
+  rts::OctDynamic octdyn;
   rts::Instanced inst;
   rts::Frame fb;
   rts::Schedule sched;

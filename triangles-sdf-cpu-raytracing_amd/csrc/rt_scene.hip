@@ -2,8 +2,9 @@
 // grids and octrees, replication to another device, vertex updates of dynamic
 // meshes, instanced scenes, destruction, the plane and the getters of
 // include/rtamd.h, and the device views of a scene that the kernel launchers
-// take (mesh_dev, grid_dev, grid_mode; rt_scene.h). Its kernels are the two
-// that prepare scene data (brick_kernel, tri_edge_bound_kernel).
+// take (mesh_dev, grid_dev, grid_mode; rt_scene.h). Its kernels are those
+// that prepare scene data (brick_kernel, grid_copy_kernel,
+// tri_edge_bound_kernel).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -20,6 +21,7 @@
 #include "rt_host.h"
 #include "rt_refit.h"
 #include "rt_scene.h"
+#include "rt_sdf_octree.h"
 #include "rt_shade.h"
 
 using namespace rtd;
@@ -82,6 +84,12 @@ __global__ __launch_bounds__(256) void brick_kernel(const float *__restrict__ sr
   dst[i] = (x < sx && y < sy && z < sz) ? src[((uint64_t)x * sy + y) * sz + z] : 0.0f;
 }
 
+// new values of a linear grid scene (rt_scene_update_grid_device): one sample per thread
+__global__ __launch_bounds__(256) void grid_copy_kernel(const float *__restrict__ src, float *__restrict__ dst, uint64_t n) {
+  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < n) dst[i] = src[i];
+}
+
 }  // namespace
 
 namespace rti {
@@ -101,7 +109,8 @@ int no_instanced(const rt_scene *s, const char *who) {
 
 int instanced_sync(rt_scene *s, hipStream_t stream) {
   for (size_t j = 0; j < s->inst.blas.size(); ++j) {
-    // (only a dynamic mesh's version ever moves: SDF scenes are immutable)
+    // (only a dynamic mesh's version ever moves: an SDF scene that takes new
+    // values keeps its arrays, so its table entry stays right as it is)
     if (s->inst.blas[j]->info.version == s->inst.blas_seen[j]) continue;
     // (a mixed table: the mesh view of the record; kind and variant stay)
     rtd::MeshDev *entry = s->inst.mixed.p ? &(s->inst.mixed.p + j)->mesh : s->inst.tab.p + j;
@@ -424,6 +433,156 @@ int rt_scene_create_octree(const void *nodes36, int64_t count, rt_scene **out) {
   return RT_OK;
 }
 
+int rt_scene_update_grid_device(rt_scene *s, const float *d_values, void *stream) {
+  if (!s) return set_err(RT_E_INVALID, "rt_scene_update_grid_device: scene is NULL");
+  if (!d_values) return set_err(RT_E_INVALID, "rt_scene_update_grid_device: values are NULL");
+  if (s->info.kind != RT_SCENE_GRID) return set_err(RT_E_STATE, "rt_scene_update_grid_device: not a grid scene");
+  int dev = 0;
+  HIP_TRY(hipGetDevice(&dev));
+  if (s->device != dev)
+    return set_err(RT_E_INVALID, "rt_scene_update_grid_device: the scene lives on device " + std::to_string(s->device) +
+                                     ", the current one is " + std::to_string(dev));
+  const hipStream_t st = (hipStream_t)stream;
+  const uint64_t n = grid_samples(s);  // (below 2^32 bricked, at most 2^32 linear)
+  const unsigned blocks = (unsigned)((n + 255) / 256);
+  if (s->grid.bricked)
+    brick_kernel<<<blocks, 256, 0, st>>>(d_values, s->geo.vals.p, s->grid.size[0], s->grid.size[1], s->grid.size[2], n);
+  else
+    grid_copy_kernel<<<blocks, 256, 0, st>>>(d_values, s->geo.vals.p, n);
+  HIP_TRY(hipGetLastError());
+  return RT_OK;
+}
+
+int rt_scene_create_octree_dynamic(int32_t depth, int64_t max_nodes, rt_scene **out) {
+  if (!out) return set_err(RT_E_INVALID, "rt_scene_create_octree_dynamic: out is NULL");
+  if (depth < 0 || depth > 12) return set_err(RT_E_INVALID, "rt_scene_create_octree_dynamic: depth must be in [0, 12]");
+  if (max_nodes < 1 || max_nodes > 0xFFFFFFFFll)
+    return set_err(RT_E_INVALID, "rt_scene_create_octree_dynamic: max_nodes must be in [1, 2^32 - 1]");
+  int32_t maxd = 8;
+  int rc = pick_maxd(depth, maxd);
+  if (rc) return rc;
+  rt_scene *s;
+  if ((rc = new_scene(&s))) return rc;
+  s->info.kind = RT_SCENE_OCTREE;
+  s->info.maxd = maxd;
+  s->oct.depth = depth;
+  rts::OctDynamic &od = s->octdyn;
+  od.on = true;
+  od.max_nodes = (uint32_t)max_nodes;
+  const size_t C = (size_t)max_nodes;
+  // the initial tree: a root that is an empty leaf
+  rtl::OctWord w0{rtl::kOctNeverHits, 0u};
+  rtl::OctVals v0;
+  std::fill(v0.v, v0.v + 8, 1000.0f);
+  const uint32_t st0[2] = {1u, 0u};
+  hipError_t e = hipSuccess;
+  auto put = [&](void *d, const void *h, size_t bytes) {
+    if (rc == RT_OK && e == hipSuccess) e = rtdma::h2d(d, h, bytes, nullptr);
+  };
+  if ((rc = s->geo.child.alloc(C)) == RT_OK && (rc = s->geo.ovals.alloc(C)) == RT_OK) {
+    s->info.dev_bytes += (int64_t)(s->geo.child.bytes() + s->geo.ovals.bytes());
+    put(s->geo.child.p, &w0, sizeof w0);
+    put(s->geo.ovals.p, &v0, sizeof v0);
+  }
+  if (rc == RT_OK) rc = od.status.alloc(2);
+  put(od.status.p, st0, sizeof st0);
+  if (rc == RT_OK) rc = od.s_child.alloc(C);
+  if (rc == RT_OK) rc = od.s_vals.alloc(C);
+  if (rc == RT_OK) rc = od.cells.alloc(C);
+  if (rc == RT_OK) rc = od.flag.alloc(rtsdf::oct_flag_count(od.max_nodes));
+  if (rc == RT_OK) rc = od.bsum.alloc(rtsdf::oct_bsum_count(od.max_nodes));
+  if (rc == RT_OK) rc = od.lvl.alloc(rtsdf::kOctLvlWords);
+  if (rc == RT_OK) rc = od.top.alloc(std::max<size_t>(rtsdf::oct_top_first(rtsdf::oct_top_levels(depth)), 1));
+  if (rc == RT_OK && e != hipSuccess)
+    rc = set_err(RT_E_DEVICE, rterr::hip_fail("rt_scene_create_octree_dynamic: upload of the initial tree", e));
+  if (rc != RT_OK) {
+    rt_scene_destroy(s);
+    return rc;
+  }
+  od.bytes = (int64_t)(od.status.bytes() + od.s_child.bytes() + od.s_vals.bytes() + od.cells.bytes() + od.flag.bytes() +
+                       od.bsum.bytes() + od.lvl.bytes() + od.top.bytes());
+  s->info.dev_bytes += od.bytes;
+  *out = s;
+  return RT_OK;
+}
+
+// What an octree scene holds on the device after a wait for it: the node
+// count and the dropped-build flag (a plain octree: its size, 0).
+static int octree_check(const rt_scene *s, const char *who) {
+  if (!s) return set_err(RT_E_INVALID, std::string(who) + ": scene is NULL");
+  if (s->info.kind != RT_SCENE_OCTREE) return set_err(RT_E_STATE, std::string(who) + ": not an octree scene");
+  return RT_OK;
+}
+static int octree_status(rt_scene *s, const char *who, uint32_t st[2]) {
+  if (int rc = octree_check(s, who)) return rc;
+  HIP_TRY(hipSetDevice(s->device));
+  HIP_TRY(hipDeviceSynchronize());
+  st[0] = (uint32_t)s->geo.child.n;
+  st[1] = 0u;
+  if (s->octdyn.on) HIP_TRY(rtdma::d2h(st, s->octdyn.status.p, 8, nullptr));
+  return RT_OK;
+}
+
+// The scene's device arrays, words and values of its first st[0] nodes.
+static int octree_download(rt_scene *s, const char *who, uint32_t st[2], std::vector<rtl::OctWord> &w,
+                           std::vector<rtl::OctVals> *v) {
+  if (int rc = octree_check(s, who)) return rc;
+  int prev = 0;
+  HIP_TRY(hipGetDevice(&prev));
+  int rc = octree_status(s, who, st);
+  if (rc == RT_OK) {
+    w.resize(st[0]);
+    hipError_t e = rtdma::d2h(w.data(), s->geo.child.p, (size_t)st[0] * sizeof(rtl::OctWord), nullptr);
+    if (e == hipSuccess && v) {
+      v->resize(st[0]);
+      e = rtdma::d2h(v->data(), s->geo.ovals.p, (size_t)st[0] * sizeof(rtl::OctVals), nullptr);
+    }
+    if (e != hipSuccess) rc = set_err(RT_E_DEVICE, rterr::hip_fail(who, e));
+  }
+  HIP_NOTE(hipSetDevice(prev));
+  return rc;
+}
+
+int rt_scene_octree_status(rt_scene *s, int64_t *count, int32_t *overflow) {
+  if (int rc = octree_check(s, "rt_scene_octree_status")) return rc;
+  int prev = 0;
+  HIP_TRY(hipGetDevice(&prev));
+  uint32_t st[2];
+  const int rc = octree_status(s, "rt_scene_octree_status", st);
+  HIP_NOTE(hipSetDevice(prev));
+  if (rc) return rc;
+  if (count) *count = (int64_t)st[0];
+  if (overflow) *overflow = (int32_t)st[1];
+  return RT_OK;
+}
+
+int rt_scene_get_octree(rt_scene *s, int64_t *count, void *nodes36) {
+  if (!count) return set_err(RT_E_INVALID, "rt_scene_get_octree: count is NULL");
+  if (int rc = octree_check(s, "rt_scene_get_octree")) return rc;
+  uint32_t st[2];
+  if (!nodes36) {
+    int prev = 0;
+    HIP_TRY(hipGetDevice(&prev));
+    const int rc = octree_status(s, "rt_scene_get_octree", st);
+    HIP_NOTE(hipSetDevice(prev));
+    if (rc == RT_OK) *count = (int64_t)st[0];
+    return rc;
+  }
+  std::vector<rtl::OctWord> w;
+  std::vector<rtl::OctVals> v;
+  if (int rc = octree_download(s, "rt_scene_get_octree", st, w, &v)) return rc;
+  if (*count < (int64_t)st[0]) return set_err(RT_E_INVALID, "rt_scene_get_octree: node buffer too small");
+  uint8_t *o = static_cast<uint8_t *>(nodes36);
+  for (size_t i = 0; i < w.size(); ++i) {
+    // (both leaf words are offset 0 in the 36-byte format)
+    const uint32_t off = w[i].child == rtl::kOctNeverHits ? 0u : w[i].child;
+    std::memcpy(o + 36 * i, v[i].v, 32);
+    std::memcpy(o + 36 * i + 32, &off, 4);
+  }
+  *count = (int64_t)st[0];
+  return RT_OK;
+}
+
 int rt_scene_replicate(const rt_scene *src, int device, rt_scene **out) {
   if (!src || !out) return set_err(RT_E_INVALID, "bad arguments");
   if (int rc = no_instanced(src, "rt_scene_replicate")) return rc;
@@ -441,7 +600,7 @@ int rt_scene_replicate(const rt_scene *src, int device, rt_scene **out) {
   s->mesh = src->mesh;
   s->grid = src->grid;
   s->oct = src->oct;
-  s->info.dev_bytes = src->info.dev_bytes - src->dyn.bytes;  // (a plain snapshot: not dynamic)
+  s->info.dev_bytes = src->info.dev_bytes - src->dyn.bytes - src->octdyn.bytes;  // (a plain snapshot: not dynamic)
   // the device arrays, copied device to device (over xGMI between GPUs) at the
   // size their owner holds (the triangles with their zero pad)
   hipError_t e = hipSuccess;
@@ -881,6 +1040,23 @@ int rtx_octree_flatten(const void *nodes36, int64_t count, int32_t *max_depth, i
       words[2 * i] = g.child[(size_t)i].child;
       words[2 * i + 1] = g.child[(size_t)i].masks;
     }
+  return RT_OK;
+}
+
+// Diagnostic (not part of include/rtamd.h): the {child, masks} pairs of an
+// octree scene as the device holds them now, after a wait for it, as 2 uint32
+// per node for the scene's first `count` nodes; count must not pass what the
+// scene holds (rt_scene_octree_status).
+int rtx_scene_octree_words(rt_scene *s, uint32_t *words, int64_t count) {
+  if (!words || count < 0) return set_err(RT_E_INVALID, "rtx_scene_octree_words: bad arguments");
+  uint32_t st[2];
+  std::vector<rtl::OctWord> w;
+  if (int rc = octree_download(s, "rtx_scene_octree_words", st, w, nullptr)) return rc;
+  if (count > (int64_t)st[0]) return set_err(RT_E_INVALID, "rtx_scene_octree_words: count passes the scene's nodes");
+  for (int64_t i = 0; i < count; ++i) {
+    words[2 * i] = w[(size_t)i].child;
+    words[2 * i + 1] = w[(size_t)i].masks;
+  }
   return RT_OK;
 }
 

@@ -176,6 +176,11 @@ _SIGS = {
     "rt_sdf_mesh_update_vertices_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "rt_sdf_mesh_get_pseudonormals": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
     "rt_sdf_mesh_device_bytes": (C.c_int64, [C.c_void_p]),
+    "rt_scene_update_grid_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_scene_create_octree_dynamic": (C.c_int, [C.c_int32, C.c_int64, C.POINTER(C.c_void_p)]),
+    "rt_sdf_mesh_octree_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_scene_octree_status": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
+    "rt_scene_get_octree": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.c_void_p]),
     "rt_mesh_subdivide": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p,
                                     C.POINTER(C.c_int64), C.c_void_p, C.POINTER(C.c_int64)]),
     "rt_camera_init": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(CameraState)]),
@@ -240,6 +245,8 @@ _XSIGS = {
     # the live owners behind every handle (csrc/rt_mem.h): device arrays, pinned
     # host blocks, events, streams
     "rtx_live_resources": (C.c_int, [C.POINTER(C.c_int64)]),
+    # the {child, masks} words of an octree scene as the device holds them
+    "rtx_scene_octree_words": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
 }
 
 

@@ -456,6 +456,14 @@ class SDFGrid(IScene):
         self._h = h
         self.size = size
 
+    def update_device(self, ptr: int, stream: int | None = None):
+        """New values from device memory (float32[sx*sy*sz] at ptr in the layout
+        (x*sy+y)*sz+z, e.g. what SDFMesh.grid_device wrote), queued on `stream`:
+        rt_scene_update_grid_device. The call only launches; the scene keeps
+        its device array, so instanced scenes over it follow."""
+        check(lib().rt_scene_update_grid_device(self._handle(), C.c_void_p(ptr) if ptr else None,
+                                                C.c_void_p(stream) if stream else None))
+
 
 class SDFOctree(IScene):
     def __init__(self, nodes36: np.ndarray):
@@ -463,6 +471,33 @@ class SDFOctree(IScene):
         h = C.c_void_p()
         check(lib().rt_scene_create_octree(_p(nodes36), nodes36.nbytes // 36, C.byref(h)))
         self._h = h
+
+    @classmethod
+    def dynamic(cls, depth: int, max_nodes: int) -> "SDFOctree":
+        """An octree scene with room for max_nodes nodes of a tree of at most
+        `depth` levels, which SDFMesh.octree_device rebuilds on the device
+        (rt_scene_create_octree_dynamic). It starts as one empty leaf."""
+        h = C.c_void_p()
+        check(lib().rt_scene_create_octree_dynamic(int(depth), int(max_nodes), C.byref(h)))
+        self = cls.__new__(cls)
+        self._h = h
+        return self
+
+    def status(self):
+        """-> (nodes the scene holds now, 1 if its last device build overflowed
+        and was dropped), after a wait for the device: rt_scene_octree_status."""
+        n, o = C.c_int64(0), C.c_int32(0)
+        check(lib().rt_scene_octree_status(self._handle(), C.byref(n), C.byref(o)))
+        return n.value, o.value
+
+    def nodes(self) -> np.ndarray:
+        """-> raw nodes, uint8 [count*36], rebuilt from what the scene holds on
+        the device now (rt_scene_get_octree)."""
+        n = C.c_int64(0)
+        check(lib().rt_scene_get_octree(self._handle(), C.byref(n), None))
+        buf = np.empty(n.value * 36, np.uint8)
+        check(lib().rt_scene_get_octree(self._handle(), C.byref(n), _p(buf)))
+        return buf[:n.value * 36]
 
 
 def affine_inverse(xform) -> np.ndarray:
@@ -813,6 +848,14 @@ class SDFMesh:
         buf = np.empty(n.value * 36, np.uint8)
         check(lib().rt_sdf_mesh_octree(self._h, int(depth), C.byref(n), _p(buf)))
         return buf
+
+    def octree_device(self, scene: "SDFOctree", stream: int | None = None):
+        """Rebuild `scene` (SDFOctree.dynamic) on the device as the octree of
+        the mesh as it is now, at the scene's depth, queued on `stream`
+        (rt_sdf_mesh_octree_device); the call only launches. A tree that
+        passes the scene's capacity is dropped: scene.status()."""
+        check(lib().rt_sdf_mesh_octree_device(self._h, scene._handle() if scene is not None else None,
+                                              C.c_void_p(stream) if stream else None))
 
     def close(self):
         if getattr(self, "_h", None):

@@ -392,3 +392,43 @@ def sdf_grid(sdf_mesh, size):
     with torch.cuda.device(device):
         sdf_mesh.grid_device(size, g.data_ptr(), stream=torch.cuda.current_stream(device).cuda_stream)
     return g
+
+
+def update_sdf_grid(scene, values) -> None:
+    """New values for an rtamd.SDFGrid from a tensor (SDFGrid.update_device,
+    rt_scene_update_grid_device): `values` is a contiguous float32 tensor on
+    the scene's device with the scene's sx * sy * sz samples in the layout of
+    sdf_grid ([sx, sy, sz] or flat). The copy is queued on
+    torch.cuda.current_stream(), after the torch kernels that produced `values`
+    there and before the frames and ray queries queued there afterwards; the
+    call only launches. Raises ValueError on a bad tensor before anything is
+    launched."""
+    import torch
+
+    device = int(lib().rt_scene_device(scene._handle()))
+    n = int(scene.size[0]) * int(scene.size[1]) * int(scene.size[2])
+    if not isinstance(values, torch.Tensor):
+        raise ValueError(f"values: expected a torch tensor, got {type(values).__name__}")
+    if values.dtype != torch.float32:
+        raise ValueError(f"values: dtype {values.dtype}, expected torch.float32")
+    if values.numel() != n:
+        raise ValueError(f"values: {values.numel()} samples, the scene's size {tuple(int(x) for x in scene.size)} has {n}")
+    if values.device.type != "cuda" or values.device.index != device:
+        raise ValueError(f"values: on {values.device}, the scene is on HIP device {device}")
+    if not values.is_contiguous():
+        raise ValueError("values: not contiguous")
+    with torch.cuda.device(device):
+        scene.update_device(values.data_ptr(), stream=torch.cuda.current_stream(device).cuda_stream)
+
+
+def update_sdf_octree(sdf_mesh, scene) -> None:
+    """Rebuild an rtamd.SDFOctree.dynamic scene from an rtamd.SDFMesh as it is
+    now (SDFMesh.octree_device, rt_sdf_mesh_octree_device), queued on
+    torch.cuda.current_stream(): behind an update_sdf_mesh queued there before,
+    ahead of the ray queries queued there afterwards; the call only launches.
+    scene.status() tells afterwards whether the tree fitted."""
+    import torch
+
+    device = sdf_mesh.device()
+    with torch.cuda.device(device):
+        sdf_mesh.octree_device(scene, stream=torch.cuda.current_stream(device).cuda_stream)
